@@ -8,7 +8,11 @@ commitment is to a degree N*2^24 polynomial: rank r owns bases/scalars
 [r*2^24, (r+1)*2^24) and the per-rank partial sums are combined by one RCCL
 allgather (weak scaling; value = N*2^24 / max-over-ranks time).
 
-Alongside, the sumcheck prover (SumcheckProof::prove, h = g1*g2*g3, degree 3)
+A plain run does only that: it sets up, warms up, times the steps, writes the
+last step's commitment if --dump-outputs is given, and prints the result line.
+Everything below runs only with --full.
+
+With --full, the sumcheck prover (SumcheckProof::prove, h = g1*g2*g3, degree 3)
 at 2^20 variables is reported in `sumcheck` with its own HBM roofline (with N
 ranks the 2^20 tables are sharded by the high index bits: strong scaling), and
 configs C4 (ML-PCS commit + open, 2^22), the Logup column and C5 (HyperPlonk
@@ -16,7 +20,7 @@ prove, 2^20-row traces) get their own entries.  The CPU baseline is the oracle's
 restatement of the reference algorithm (single thread, like the reference,
 which has no rayon), timed on a bounded sample on rank 0.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N > 1 via torch.distributed.run, one process per GPU)
 """
 import argparse
@@ -47,6 +51,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg and check: the commitment "
+                         "check, the Fq-mul microbenchmark, the PMC traffic passes, sumcheck, "
+                         "zero-check, the other MSM legs, ML-PCS open, Logup, HyperPlonk and "
+                         "the CPU baselines (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--log-msm", type=int, default=24)
     ap.add_argument("--log-msm-small", type=int, default=20,
                     help="config 2: a resident 2^k MSM with its own SRS (window size chosen "
@@ -227,6 +238,10 @@ def main():
     args = parse()
     if args.traffic_probe:
         return traffic_probe(args)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
+    full = args.full
     plan = launch_plan(args.gpus, os.environ)
     if plan == "launch":
         # a fresh child per rank, started before this process makes any GPU call
@@ -242,7 +257,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     traffic = None
-    if world == 1 and not args.no_traffic:
+    if full and world == 1 and not args.no_traffic:
         traffic = measure_traffic(args)  # child processes, before this one touches the GPU
     import quill_amd as q
     dev, dist = setup_rank(q, rank, world, local_rank)
@@ -286,7 +301,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = world * n * args.steps / dt
 
-    verified = verify_commitment(scalars, res, n, rank, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     kern = {}
     for name in ("msm_bucketing", "msm_accumulate", "msm_reduce"):
         ms, cnt = dev.kernel_time(name)
@@ -297,11 +313,7 @@ def main():
     dev.enable_timing(False)
     acc_ms = max_over_ranks(kern["msm_accumulate"]["ms_per_msm"])
     achieved = MSM_BYTES_PER_SCALAR * n / (acc_ms * 1e-3) / 1e9
-    fq_peak = dev.microbench_fq_mul()
     c_bits, n_win = srs.window_info()
-    # executed: one mixed XYZZ add (8M + 2S = 10 Fq mults) per nonzero digit,
-    # W digits per scalar, in msm_accumulate (bucketing/reduce excluded)
-    exec_mults = 10 * n_win * n
 
     out = {
         "metric": "G1 MSM scalars/sec at 2^24 + sumcheck-prover ms at 2^20 vars (1/8 GPU)",
@@ -332,39 +344,68 @@ def main():
                                      "the cooperative kernel's whole-row reads need no rescale)",
                      "algorithmic_bytes": MSM_BYTES_PER_SCALAR * n,
                      "note": "MSM is integer-VALU bound (no MFMA form): see compute"},
-        "compute": {"fq_mul_per_s_peak_microbench": fq_peak,
-                    "survey_fq_mul_equiv_per_scalar": MSM_FQMUL_PER_SCALAR,
-                    "survey_equiv_fq_mul_per_s_whole_step": MSM_FQMUL_PER_SCALAR * n / (ms_per_step * 1e-3),
-                    "windows": n_win, "window_bits": c_bits,
-                    "accumulate_fq_mul_per_s": exec_mults / (acc_ms * 1e-3),
-                    "frac": exec_mults / (acc_ms * 1e-3) / fq_peak,
-                    "frac_note": "msm_accumulate's executed Fq mults (10 per digit x W digits "
-                                 "per scalar) / microbenchmarked Fq-mul peak",
-                    "issue_bound_fq_mul_per_s": VMAD_LANE_OPS_PER_S / MADS_PER_FQ_MUL,
-                    "frac_issue_bound": exec_mults / (acc_ms * 1e-3)
-                    / (VMAD_LANE_OPS_PER_S / MADS_PER_FQ_MUL),
-                    "issue_bound_note": "v_mad_u64_u32 lane-ops/s measured with every CU "
-                                        "issuing (profiles/r01_isa_rates.json) / 162 partial "
-                                        "products per 29-bit Montgomery multiply: a hardware "
-                                        "bound, independent of the microbenchmark",
-                    "row_gathers_per_s": n_win * n / (acc_ms * 1e-3),
-                    "frac_gather_capacity": n_win * n / (acc_ms * 1e-3) / COOP_GATHER_ROWS_PER_S,
-                    "gather_note": "random 128-B table rows gathered per second (one per digit) / "
-                                   "the chip's measured capacity for whole-row coalesced "
-                                   "gathers over a 16 GiB table (micro/gather_bench.hip, "
-                                   "profiles/r05_gather_bench.txt)"},
         "kernels_ms": kern,
         "setup_s": setup_s,
         "commitment_x_low64": hex(0 if res is None else res[0] & ((1 << 64) - 1)),
-        "commitment_verified": verified["ok"],
-        "commitment_check": verified,
         # bucket-scan plan copies re-read synchronously (stale generation tag); 0
         # while the event ordering holds
         "msm_plan_refetch": dev.counter("msm_plan_refetch"),
     }
 
+    if full:
+        verified = verify_commitment(scalars, res, n, rank, world)
+        out["commitment_verified"] = verified["ok"]
+        out["commitment_check"] = verified
+        fq_peak = dev.microbench_fq_mul()
+        # executed: one mixed XYZZ add (8M + 2S = 10 Fq mults) per nonzero digit,
+        # W digits per scalar, in msm_accumulate (bucketing/reduce excluded)
+        exec_mults = 10 * n_win * n
+        out["compute"] = {"fq_mul_per_s_peak_microbench": fq_peak,
+                          "survey_fq_mul_equiv_per_scalar": MSM_FQMUL_PER_SCALAR,
+                          "survey_equiv_fq_mul_per_s_whole_step":
+                              MSM_FQMUL_PER_SCALAR * n / (ms_per_step * 1e-3),
+                          "windows": n_win, "window_bits": c_bits,
+                          "accumulate_fq_mul_per_s": exec_mults / (acc_ms * 1e-3),
+                          "frac": exec_mults / (acc_ms * 1e-3) / fq_peak,
+                          "frac_note": "msm_accumulate's executed Fq mults (10 per digit x W "
+                                       "digits per scalar) / microbenchmarked Fq-mul peak",
+                          "issue_bound_fq_mul_per_s": VMAD_LANE_OPS_PER_S / MADS_PER_FQ_MUL,
+                          "frac_issue_bound": exec_mults / (acc_ms * 1e-3)
+                          / (VMAD_LANE_OPS_PER_S / MADS_PER_FQ_MUL),
+                          "issue_bound_note": "v_mad_u64_u32 lane-ops/s measured with every CU "
+                                              "issuing (profiles/r01_isa_rates.json) / 162 partial "
+                                              "products per 29-bit Montgomery multiply: a hardware "
+                                              "bound, independent of the microbenchmark",
+                          "row_gathers_per_s": n_win * n / (acc_ms * 1e-3),
+                          "frac_gather_capacity":
+                              n_win * n / (acc_ms * 1e-3) / COOP_GATHER_ROWS_PER_S,
+                          "gather_note": "random 128-B table rows gathered per second (one per "
+                                         "digit) / the chip's measured capacity for whole-row "
+                                         "coalesced gathers over a 16 GiB table "
+                                         "(micro/gather_bench.hip, profiles/r05_gather_bench.txt)"}
     if traffic is not None:
         out["pmc"] = traffic
+    if full:
+        run_full_legs(q, dev, args, out, srs, scalars, res, ms_per_step, traffic, barrier_sync,
+                      max_over_ranks, rank, world)
+    out["msm_plan_refetch"] = dev.counter("msm_plan_refetch")  # over every leg
+    # MSM batches whose event-ordered side-stream hand-over the device guard
+    # found unordered (recomputed in stream order); 0 while the ordering holds
+    out["msm_handover_violation"] = dev.counter("msm_handover_violation")
+    if rank == 0:
+        if full:
+            write_detail(out, args.detail_out)
+        print(json.dumps(compact(out), separators=(",", ":")), flush=True)
+    srs.close()
+    scalars.close()
+    dev.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def run_full_legs(q, dev, args, out, srs, scalars, res, ms_per_step, traffic, barrier_sync,
+                  max_over_ranks, rank, world):
+    """--full: every leg after the headline, each into its own entry of `out`"""
     if not args.no_sumcheck:
         _progress(rank, "sumcheck")
         dev.trace_marker(LEG_TAGS["sumcheck"])
@@ -421,18 +462,6 @@ def main():
             out["sumcheck"]["cpu_baseline"] = cpu_baseline_sumcheck(args)
         if args.log_mle > 0 and isinstance(out.get("mle_open"), dict):
             out["mle_open"]["cpu_baseline"] = cpu_baseline_mle(args)
-    out["msm_plan_refetch"] = dev.counter("msm_plan_refetch")  # over every leg
-    # MSM batches whose event-ordered side-stream hand-over the device guard
-    # found unordered (recomputed in stream order); 0 while the ordering holds
-    out["msm_handover_violation"] = dev.counter("msm_handover_violation")
-    if rank == 0:
-        write_detail(out, args.detail_out)
-        print(json.dumps(compact(out), separators=(",", ":")), flush=True)
-    srs.close()
-    scalars.close()
-    dev.close()
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 # ---------------------------------------------------------------- report
@@ -506,6 +535,20 @@ def compact(out, limit=LINE_MAX_BYTES):
         if key in line:
             line[key] = "shed: see detail"
     return line
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: what the last timed step returned, the commitment (an
+    affine BN254 G1 point), as DIR/commitment.npy: float64[33] = the 16-bit
+    little-endian limbs of canonical x (16), of canonical y (16), then the
+    infinity flag (limbs 0 when set).  Every entry is an integer below 2^16,
+    so float64 holds it exactly."""
+    import numpy as np
+    x, y = (0, 0) if res is None else res
+    limbs = [(v >> (16 * i)) & 0xFFFF for v in (x, y) for i in range(16)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "commitment.npy"),
+            np.array(limbs + [1 if res is None else 0], dtype=np.float64))
 
 
 def write_detail(out, path):

@@ -1,5 +1,5 @@
-"""Per-kernel HBM table from bench.py's PMC probe (the `pmc` object of the
---detail-out JSON, or of a bench log's JSON line): PMC bytes per launch
+"""Per-kernel HBM table from the PMC probe of `bench.py --full` (the `pmc` object of
+the --detail-out JSON, or of a bench log's JSON line): PMC bytes per launch
 (FETCH_SIZE x2 KiB-corrected + WRITE_SIZE, separate passes), clean average
 duration from a kernel-trace-only pass, achieved GB/s and fraction of the
 8 TB/s HBM peak.  Rows are kernel#leg (the probe phase from its

@@ -3,7 +3,8 @@
 set -o pipefail
 export TMPDIR=/tmp
 tag=$1
-mkdir -p gpurun_out
+out=${OUT:-bench_out}  # where the logs and reports go
+mkdir -p "$out"
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
-  > gpurun_out/${tag}_gpu_tests.log 2>&1 || exit 1
-timeout -k 10 900 python -u bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || exit 1
+  > $out/${tag}_gpu_tests.log 2>&1 || exit 1
+timeout -k 10 900 python -u bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1

@@ -6,7 +6,7 @@ out=$1; shift
 for rep in 1 2; do
   for v in "$@"; do
     echo "== QG_MSM_EQSPLIT=$v"
-    QG_MSM_EQSPLIT=$v timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-traffic \
+    QG_MSM_EQSPLIT=$v timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-traffic \
       --no-cpu-baseline --no-scaling-modes --no-sumcheck --log-mle 0 --log-logup 0 \
       --log-msm-small 0 --no-host-input --detail-out "" 2>/dev/null | python3 -c "
 import json, sys

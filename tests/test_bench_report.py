@@ -91,6 +91,41 @@ def test_launch_cmd_reruns_this_script_per_rank():
     assert os.path.basename(cmd[-5]) == "bench.py"
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """without --full the bench runs the headline only; --dump-outputs is off"""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_steps_must_be_positive(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    assert bench.main() == 2  # refused before any GPU call
+
+
+@pytest.mark.parametrize("point", [
+    (0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD46, 2),
+    (1, 0xFFFF0000FFFF),
+    None,
+])
+def test_dump_outputs_holds_the_commitment_exactly(tmp_path, point):
+    import numpy as np
+    d = tmp_path / "nested" / "dump"
+    bench.dump_outputs(str(d), point)
+    assert os.listdir(d) == ["commitment.npy"]
+    a = np.load(d / "commitment.npy")
+    assert a.dtype == np.float64 and a.shape == (33,)
+    limbs = [int(v) for v in a]
+    assert all(float(v) == w and 0 <= v < 1 << 16 for v, w in zip(limbs, a))
+    x = sum(v << (16 * i) for i, v in enumerate(limbs[:16]))
+    y = sum(v << (16 * i) for i, v in enumerate(limbs[16:32]))
+    assert (None if limbs[32] else (x, y)) == point
+    assert limbs[32] in (0, 1) and (point is not None or (x, y) == (0, 0))
+
+
 def test_hbm_by_kernel_prefers_leg_keys():
     pmc = {"k_msm_accumulate": {"hbm_gbps": 1.0, "frac_hbm_peak": 0.1, "avg_us": 9.0,
                                 "launches": 2},
