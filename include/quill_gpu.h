@@ -478,8 +478,28 @@ int qg_trace_marker(qg_ctx* ctx, uint32_t tag);
  * did not carry their run's generation tag and were re-read synchronously.
  * "msm_handover_violation": MSM batches whose event-ordered hand-over between
  * the context stream and the side streams the device guard found unordered
- * (each was recomputed in stream order; 0 while the event ordering holds). */
+ * (each was recomputed in stream order; 0 while the event ordering holds).
+ * "open_checks": KZG quotients checked against p(sigma) - y == q(sigma)(sigma - x)
+ * (kzg.rs:85); "open_check_failures": those that failed (each failing call
+ * returned QG_ERR_ASSERT, "Polynomial division failed"). */
 int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value);
+/* DensePolynomial::evaluate (pcs/src/kzg.rs:78) on a device vector:
+ * out = sum_{i < n} poly[i] * x^(shift + i) (Montgomery in and out), by the
+ * evaluation kernel the opening check uses.  `shift` is the power offset of a
+ * slice of a sharded polynomial.  n == 0 gives 0; n > qg_buf_len or a null
+ * handle gives QG_ERR_INVALID.  QG_EVAL_BLOCKS=<k> (read per call) caps the
+ * kernel's grid. */
+int qg_poly_eval_dev(qg_ctx* ctx, const qg_buf* poly, size_t n, const uint64_t x[4],
+                     uint64_t shift, uint64_t out[4]);
+/* TEST ONLY (like qg_selftest_inverse): arms a one-shot fault that the next
+ * opening call on this context consumes, so the tests can show that the
+ * quotient check catches it; afterwards the context is clean.  kind 0 disarms;
+ * 1 SHORT_TRIM: the first nonzero trimmed length the call computes is reduced
+ * by `value` (at least 1 remains; on a sharded context the local length, before
+ * the exchange); 2 QUOTIENT: 1 is added to coefficient `value mod len` of the
+ * call's first non-empty quotient; 3 STAMP: `value` is written into the
+ * trimmed-length scan's stamp word at once. */
+int qg_debug_open_fault(qg_ctx* ctx, uint32_t kind, uint64_t value);
 /* Self-test of the binary-GCD field inversion the Logup column uses per block
  * (csrc/bingcd.h): out[i] = in[i]^-1 (plain canonical integers, 4 x u64 LE;
  * 0 -> 0) in Fr (field = 0) or Fq (field = 1), on the host (ctx may be NULL)

@@ -173,6 +173,10 @@ int qg_ctx_create(int device, qg_ctx** out) {
   qg_ctx* ctx = new qg_ctx();
   ctx->arena.backend.drain = &qg_ctx::drain_streams;
   ctx->arena.backend.owner = ctx;
+  {  // the opening check's point generator (common.h: open_rng)
+    std::random_device rd;
+    ctx->open_rng.seed(((uint64_t)rd() << 32) ^ (uint64_t)rd());
+  }
   int rc = qg_guard(ctx, [&] {
     int ndev = 0;
     QG_HIP(hipGetDeviceCount(&ndev));
@@ -281,6 +285,8 @@ int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value) {
   const std::string n(name);
   *value = n == "msm_plan_refetch"         ? ctx->msm_plan_refetch
            : n == "msm_handover_violation" ? ctx->msm_handover_violation
+           : n == "open_checks"            ? ctx->open_checks
+           : n == "open_check_failures"    ? ctx->open_check_failures
                                            : 0;
   return QG_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <map>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -114,8 +115,19 @@ struct qg_ctx {
   // MSM batches whose event-ordered cross-stream hand-over the device guard
   // found unordered (recomputed in stream order; msm.hip, msm_device_batch)
   uint64_t msm_handover_violation = 0;
-  // trim_launch's call generation (mlpcs.hip: the tail launch's stamp)
-  uint64_t trim_gen = 0;
+  // the quotient check of every KZG opening (mlpcs.hip, kzg.rs:85): sigma comes
+  // from open_rng, seeded from std::random_device when the context is created
+  // (never from the transcript); a sharded group reseeds it once with rank 0's
+  // seed and steps it in lockstep, one draw per (collective) opening call
+  std::mt19937_64 open_rng;
+  bool open_rng_shared = false;
+  qg::Fr open_sigma;               // this call's point (Montgomery)
+  uint64_t open_checks = 0;        // quotients checked
+  uint64_t open_check_failures = 0;
+  // test-only one-shot fault (qg_debug_open_fault): armed -> live for exactly
+  // the next opening call, consumed by the first site of its kind
+  uint32_t open_fault_armed = 0, open_fault_live = 0;
+  uint64_t open_fault_value = 0;
 
   // every stream of this context, synchronized (scratch release, destroy)
   static void drain_streams(void* self) {

@@ -262,7 +262,8 @@ struct ShIn {
 };
 
 static L9 x261_of(const Fr& x) {
-  const Fr t = from_mont(to_mont(from_mont(x)) * to_mont(pow2_mod_plain<FrP>(261)));
+  static const Fr k261 = to_mont(pow2_mod_plain<FrP>(261));  // (261 doublings: once)
+  const Fr t = from_mont(to_mont(from_mont(x)) * k261);
   const F29<FrP> r = to29(t);
   L9 o{};
   for (int i = 0; i < 9; i++) o.v[i] = r.l[i];
@@ -302,6 +303,284 @@ static void suffix_horner_batch(qg_ctx* ctx, const std::vector<ShIn>& in, int de
   suffix_horner_batch(ctx, up, depth + 1);
   hipLaunchKernelGGL(k_sh_apply_b, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
   QG_LAUNCH_CHECK();
+}
+
+// ---------------------------------------------------------------- polynomial evaluation
+// DensePolynomial::evaluate (kzg.rs:78) as a reduction: sum_i c_i x^i of up to
+// EV_MAXJ vectors per launch (blockIdx.y = job, like ShJobs) in the 29-bit
+// limbs of k_sh_local_b.  A thread runs Horner over a contiguous strip of S
+// coefficients; a block combines its 256 strip values with powers of x^S
+// (shuffle tree inside a wave: lane l takes x^(S 2^k) times lane l + 2^k;
+// then the four wave values through LDS) and writes one value per block span
+// (256 S coefficients); a grid-stride loop covers the spans.  The last stage
+// is the same kernel over the span values (x -> x^span, one block), which also
+// multiplies by x^shift (a slice's sigma-power offset).  One Fr product per
+// coefficient against the 32 bytes it reads: multiply-bound.
+static constexpr int EV_S = 32;    // first-stage thread strip
+static constexpr int EV_T = 256;   // threads per block
+static constexpr size_t EV_SPAN = (size_t)EV_S * EV_T;  // first-stage block span
+static constexpr int EV_MAXJ = 8;
+struct EvJob {
+  const Fr* c;  // coefficients (arkworks form)
+  size_t n;
+  size_t S;     // strip length (>= 1)
+  L9 x;         // x 2^261 mod p
+  L9 xp[7];     // x^(S 2^k) 2^261, k = 0..6
+  L9 sh;        // last stage: (first-stage x)^shift 2^261
+  int last;
+  Fr* out;      // out[g] = value of span g (arkworks form); last stage: out[0]
+};
+struct EvJobs {
+  EvJob j[EV_MAXJ];
+};
+
+QG_DEV F29<FrP> shfl_down29(const F29<FrP>& a, int d) {
+  F29<FrP> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = __shfl_down(a.l[i], d, 64);
+  return r;
+}
+
+__global__ void __launch_bounds__(EV_T) k_poly_eval(EvJobs jb) {
+  const EvJob& J = jb.j[blockIdx.y];
+  __shared__ uint32_t lds[EV_T / 64][9];
+  const F29<FrP> x = F29<FrP>::from_l9(J.x);
+  const size_t span = J.S * EV_T;
+  const size_t nspans = (J.n + span - 1) / span;
+  if (J.last && nspans == 0 && blockIdx.x == 0 && threadIdx.x == 0) J.out[0] = Fr::zero();
+  for (size_t g = blockIdx.x; g < nspans; g += gridDim.x) {  // block-uniform
+    const size_t s = g * span + (size_t)threadIdx.x * J.S;
+    F29<FrP> acc = F29<FrP>::zero();
+    if (s < J.n) {
+      const size_t e = J.S < J.n - s ? s + J.S : J.n;
+#pragma unroll 4
+      for (size_t i = e; i-- > s;) acc = red2p29(add29(to29(J.c[i]), mul29(x, acc)));
+    }
+    // lane l += x^(S m) * lane (l + m), m = 1, 2, .., 32: lane 0 ends with the
+    // wave's 64 strips (a strip past n is 0)
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const F29<FrP> o = shfl_down29(acc, 1 << k);
+      acc = red2p29(add29(acc, mul29(F29<FrP>::from_l9(J.xp[k]), o)));
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) lds[wid][i] = acc.l[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const F29<FrP> pw = F29<FrP>::from_l9(J.xp[6]);  // x^(64 S)
+      F29<FrP> r = F29<FrP>::zero();
+      for (int w = EV_T / 64 - 1; w >= 0; w--) {
+        F29<FrP> v;
+#pragma unroll
+        for (int i = 0; i < 9; i++) v.l[i] = lds[w][i];
+        r = red2p29(add29(v, mul29(pw, r)));
+      }
+      if (J.last) r = mul29(F29<FrP>::from_l9(J.sh), r);
+      J.out[g] = from29(canon29(r));
+    }
+    __syncthreads();
+  }
+}
+
+struct EvIn {
+  const Fr* c;
+  size_t n;
+  uint64_t shift;
+};
+
+// d_out[j] = sum_{i < n_j} c_j[i] x^(shift_j + i), queued on the context stream
+// (x Montgomery).  QG_EVAL_BLOCKS=<k> caps the first stage's grid (read per
+// call: tests make the grid-stride loop wrap at a small length).
+static void poly_eval_queue(qg_ctx* ctx, const std::vector<EvIn>& in, const Fr& x, Fr* d_out) {
+  const char* eb = getenv("QG_EVAL_BLOCKS");
+  const size_t cap = eb && atoi(eb) > 0 ? (size_t)atoi(eb) : 4096;
+  const L9 x261 = x261_of(x);
+  const Fr X = fpow_small(x, EV_SPAN);
+  const L9 X261 = x261_of(X);
+  auto strip_powers = [](Fr b, L9 (&o)[7]) {  // b^(2^k), k = 0..6
+    for (int k = 0; k < 7; k++, b = b * b) o[k] = x261_of(b);
+  };
+  L9 xp1[7];
+  strip_powers(fpow_small(x, EV_S), xp1);
+  // the span values of one launch: one slot, sized once per call for its
+  // largest launch (a slot that grows drains the streams; callers that queue
+  // several calls reserve it first, poly_eval_reserve)
+  size_t need = 1;
+  for (size_t b = 0; b < in.size(); b += EV_MAXJ) {
+    size_t tot = 0;
+    for (size_t q = b; q < std::min(in.size(), b + EV_MAXJ); q++)
+      tot += (in[q].n + EV_SPAN - 1) / EV_SPAN;
+    need = std::max(need, tot);
+  }
+  Fr* part = ctx->scratch_as<Fr>("ev_part", need);
+  for (size_t b = 0; b < in.size(); b += EV_MAXJ) {
+    const size_t nj = std::min<size_t>(EV_MAXJ, in.size() - b);
+    size_t nsp[EV_MAXJ], off[EV_MAXJ], tot = 0, maxsp = 0;
+    for (size_t q = 0; q < nj; q++) {
+      nsp[q] = (in[b + q].n + EV_SPAN - 1) / EV_SPAN;
+      off[q] = tot;
+      tot += nsp[q];
+      maxsp = std::max(maxsp, nsp[q]);
+    }
+    EvJobs j1{}, j2{};
+    for (size_t q = 0; q < nj; q++) {
+      const EvIn& I = in[b + q];
+      EvJob& a = j1.j[q];
+      a.c = I.c, a.n = I.n, a.S = EV_S, a.x = x261, a.last = 0, a.out = part + off[q];
+      for (int k = 0; k < 7; k++) a.xp[k] = xp1[k];
+      EvJob& z = j2.j[q];
+      z.c = part + off[q], z.n = nsp[q], z.S = std::max<size_t>(1, (nsp[q] + EV_T - 1) / EV_T);
+      z.x = X261, z.sh = x261_of(fpow_small(x, I.shift)), z.last = 1, z.out = d_out + b + q;
+      strip_powers(fpow_small(X, z.S), z.xp);
+    }
+    if (maxsp) {
+      hipLaunchKernelGGL(k_poly_eval, dim3((unsigned)std::min(maxsp, cap), (unsigned)nj),
+                         dim3(EV_T), 0, ctx->stream, j1);
+      QG_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_poly_eval, dim3(1, (unsigned)nj), dim3(EV_T), 0, ctx->stream, j2);
+    QG_LAUNCH_CHECK();
+  }
+}
+
+// ev_part for later poly_eval_queue calls of at most `jobs` vectors of at most
+// `nmax` coefficients per launch (a batch reserves for its largest item up front)
+static void poly_eval_reserve(qg_ctx* ctx, size_t jobs, size_t nmax) {
+  ctx->scratch_as<Fr>("ev_part", std::min<size_t>(jobs, EV_MAXJ) * ((nmax + EV_SPAN - 1) / EV_SPAN) + 1);
+}
+
+// ---------------------------------------------------------------- quotient check
+// KZG::open asserts q (X - x) == p - y after its division (kzg.rs:85,
+// "Polynomial division failed").  Here: p(sigma) - y == q(sigma) (sigma - x) at
+// the context's random point sigma (common.h: open_rng; exact in Fr, so it
+// fails only with probability <= n / r for a wrong quotient), p over the
+// caller's UNtrimmed length, q over the coefficients the MSM reads.
+static bool open_check_on() {
+  const char* e = getenv("QG_OPEN_CHECK");  // read per call; 0: A/B timing only
+  return !(e && atoi(e) == 0);
+}
+
+struct OpenCk {
+  const Fr* p;  // nullptr: nothing to check (no coefficients at all)
+  size_t pn;
+  const Fr* q;  // nullptr: the trimmed length was 0 - no quotient, y = 0, and the
+  size_t qn;    // check is p(sigma) == 0 over the untrimmed length (a trim that
+  const Fr* d_y;  // wrongly returned 0 would otherwise give a silent infinity proof)
+  Fr x;
+};
+struct OpenFin {
+  const Fr* ev;
+  const Fr* y[4];
+  Fr d[4];  // sigma - x
+  int pi[4], qi[4];
+  uint32_t* w;
+};
+// w[i] = p_i(sigma) - y_i != q_i(sigma) (sigma - x_i)
+__global__ void k_open_check_fin(OpenFin f) {
+  const int i = threadIdx.x;
+  if (i >= 4) return;
+  uint32_t bad = 0;
+  if (f.pi[i] >= 0) {
+    Fr r = f.ev[f.pi[i]];
+    if (f.qi[i] >= 0) r = r - *f.y[i] - f.ev[f.qi[i]] * f.d[i];
+    bad = r.is_zero() ? 0u : 1u;
+  }
+  f.w[i] = bad;
+}
+
+// queue the check of up to four quotients; d_w receives four words (nonzero:
+// failed).  Equal (p, pn) are evaluated once.
+static void open_check_queue(qg_ctx* ctx, const OpenCk ck[4], uint32_t* d_w) {
+  QgTimed tm(ctx, "kzg_open_check");
+  const Fr sigma = ctx->open_sigma;
+  std::vector<EvIn> in;
+  OpenFin f{};
+  for (int i = 0; i < 4; i++) {
+    f.pi[i] = f.qi[i] = -1;
+    if (!ck[i].p) continue;
+    for (int k = 0; k < i; k++)
+      if (ck[k].p == ck[i].p && ck[k].pn == ck[i].pn) f.pi[i] = f.pi[k];
+    if (f.pi[i] < 0) {
+      f.pi[i] = (int)in.size();
+      in.push_back({ck[i].p, ck[i].pn, 0});
+    }
+    if (!ck[i].q) continue;
+    f.qi[i] = (int)in.size();
+    in.push_back({ck[i].q, ck[i].qn, 0});
+    f.y[i] = ck[i].d_y;
+    f.d[i] = sigma - ck[i].x;
+  }
+  Fr* d_ev = ctx->scratch_as<Fr>("open_ck_ev", 8);
+  if (!in.empty()) poly_eval_queue(ctx, in, sigma, d_ev);
+  f.ev = d_ev;
+  f.w = d_w;
+  hipLaunchKernelGGL(k_open_check_fin, dim3(1), dim3(64), 0, ctx->stream, f);
+  QG_LAUNCH_CHECK();
+}
+
+static const char* const OPEN_QNAME[4] = {"poly at r", "poly at 1/r", "S at r", "S at 1/r"};
+static const char* const OPEN_UNAME[1] = {"univariate"};
+
+// after the path's synchronization: count, and raise on the first failed word
+// (bad[per k + i]: quotient i of opening k, `per` quotients per opening, named
+// qname[i]; checked[.]: CK_QUOT it had a quotient - counted in open_checks -,
+// CK_ZERO its trimmed length was 0 and p(sigma) == 0 was checked, 0 nothing).
+// A failed call leaves no trimmed length remembered.
+enum : uint8_t { CK_NONE = 0, CK_QUOT = 1, CK_ZERO = 2 };
+static void open_check_settle(qg_ctx* ctx, const std::vector<uint32_t>& bad,
+                              const std::vector<uint8_t>& checked, size_t per,
+                              const char* const* qname) {
+  size_t first = bad.size(), nbad = 0;
+  for (size_t j = 0; j < bad.size(); j++) {
+    if (!checked[j]) continue;
+    if (checked[j] == CK_QUOT) ctx->open_checks++;
+    if (bad[j]) {
+      nbad++;
+      if (first == bad.size()) first = j;
+    }
+  }
+  if (!nbad) return;
+  ctx->open_check_failures += nbad;
+  ctx->arena.memo["mle_poly_len"].clear();
+  QG_CHECK(false, QG_ERR_ASSERT,
+           "Polynomial division failed: opening " + std::to_string(first / per) + " of " +
+               std::to_string(bad.size() / per) + ", quotient " + std::to_string(first % per) +
+               " (" + qname[first % per] + ")");
+}
+
+// host form of the decision (sharded paths: the ranks' partial values summed)
+static bool open_check_host(const Fr& P, const Fr& y, const Fr& Q, const Fr& sigma, const Fr& x) {
+  return !(P - y - Q * (sigma - x)).is_zero();
+}
+
+// ---- test-only faults (qg_debug_open_fault): consumed by the first site of
+// their kind in the opening call that follows the arming
+static size_t fault_short_trim(qg_ctx* ctx, size_t len) {
+  if (ctx->open_fault_live != 1 || len == 0) return len;
+  ctx->open_fault_live = 0;
+  return len > ctx->open_fault_value ? len - (size_t)ctx->open_fault_value : 1;
+}
+__global__ void k_fault_add_one(Fr* q) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *q = *q + Fr::one();
+}
+static void fault_quotient(qg_ctx* ctx, Fr* q, size_t len) {
+  if (ctx->open_fault_live != 2 || len == 0) return;
+  ctx->open_fault_live = 0;
+  hipLaunchKernelGGL(k_fault_add_one, dim3(1), dim3(64), 0, ctx->stream,
+                     q + (size_t)(ctx->open_fault_value % len));
+  QG_LAUNCH_CHECK();
+}
+// the first nonzero of cnt device lengths, shortened (batched sharded path)
+__global__ void k_fault_short_len(unsigned long long* len, size_t cnt, unsigned long long by) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  for (size_t i = 0; i < cnt; i++)
+    if (len[i]) {
+      len[i] = len[i] > by ? len[i] - by : 1;
+      return;
+    }
 }
 
 // ---------------------------------------------------------------- NTT
@@ -994,9 +1273,9 @@ static void s_poly_device(qg_ctx* ctx, const Fr* f, size_t nf, const Fr* g, size
 // highest nonzero index + 1: per-thread max over a grid-stride range of
 // [lo, hi), wave max by shuffles, one atomic per wave (a contended atomic per
 // element cost 0.75 ms at 2^22) into *out.  The tail launch (the last 16K
-// entries) also stamps *tail with (call generation << 40 | its max); the body
-// launch skips a block when *tail holds this call's generation and a nonzero
-// max: the tail covered the higher indices, so any body index is below the
+// entries) also posts its max into *tail, which trim_launch zeroed in stream
+// order just before it; the body launch skips a block when *tail is nonzero:
+// the tail covered the higher indices, so any body index is below the
 // answer (a full body scan at 2^23 is 110 us; most vectors end in a nonzero
 // value).
 //
@@ -1012,10 +1291,9 @@ static void s_poly_device(qg_ctx* ctx, const Fr* f, size_t nf, const Fr* g, size
 // transcript, so only a verifier or a proof-by-proof comparison sees it.
 __global__ void __launch_bounds__(256)
     k_last_nonzero(const Fr* __restrict__ a, size_t lo, size_t hi, unsigned long long* tail,
-                   uint64_t gen, int body, unsigned long long* out) {
+                   int body, unsigned long long* out) {
   if (body) {
-    const unsigned long long t = __hip_atomic_load(tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((t >> 40) == gen && (t & ((1ull << 40) - 1)) != 0) return;
+    if (__hip_atomic_load(tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
   }
   unsigned long long m = 0;
   for (size_t i = lo + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi;
@@ -1025,9 +1303,9 @@ __global__ void __launch_bounds__(256)
     const unsigned long long o = __shfl_xor(m, k, 64);
     m = o > m ? o : m;
   }
-  if ((threadIdx.x & 63) == 0) {
-    if (m) atomicMax(out, m);
-    if (!body) atomicMax(tail, (gen << 40) | m);  // this call's stamp, even when m = 0
+  if ((threadIdx.x & 63) == 0 && m) {
+    atomicMax(out, m);
+    if (!body) atomicMax(tail, m);
   }
 }
 
@@ -1038,18 +1316,20 @@ static void trim_launch(qg_ctx* ctx, const Fr* a, size_t n, unsigned long long* 
   if (n == 0) return;
   constexpr size_t TAIL = 16384;
   const size_t body = n > TAIL ? n - TAIL : 0;
-  // one stamp word per context, reused in stream order; generations only grow,
-  // so a stamp of an earlier call never matches (a wrapped counter only costs
-  // the skip)
+  // one stamp word per context, reused in stream order: zeroed before every
+  // tail launch, which alone writes it (the largest nonzero index + 1 it saw),
+  // so the body launch reads this call's tail result and nothing else - no
+  // generation to collide or wrap, and no dependence on what the word held
+  // when it was allocated
   unsigned long long* tail = ctx->scratch_as<unsigned long long>("trim_tail", 1);
-  const uint64_t gen = (++ctx->trim_gen) & 0xffffffull;
+  if (body) QG_HIP(hipMemsetAsync(tail, 0, sizeof(unsigned long long), ctx->stream));
   hipLaunchKernelGGL(k_last_nonzero, dim3((unsigned)std::min<size_t>(8, div_up(n - body, 256))),
-                     dim3(256), 0, ctx->stream, a, body, n, tail, gen, 0, d);
+                     dim3(256), 0, ctx->stream, a, body, n, tail, 0, d);
   QG_LAUNCH_CHECK();
   if (body) {
     const unsigned blocks = (unsigned)std::min<size_t>(2048, div_up(body, 256));
     hipLaunchKernelGGL(k_last_nonzero, dim3(blocks), dim3(256), 0, ctx->stream, a, (size_t)0,
-                       body, tail, gen, 1, d);
+                       body, tail, 1, d);
     QG_LAUNCH_CHECK();
   }
 }
@@ -1071,9 +1351,19 @@ static size_t trimmed_len(qg_ctx* ctx, const Fr* a, size_t n) {
 // synchronization (the quotient MSMs')
 // `slot` keeps the quotient buffers of several openings apart (a batch of
 // openings commits all of its quotients at once, mle_open_batch_device).
+// The quotient check (open_check_queue) over the untrimmed lengths `ns` is
+// queued behind the h_y copy: four words into pinned h_w, read by the caller
+// after that same synchronization (ck: d_w / h_w / checked, or d_w == nullptr
+// with QG_OPEN_CHECK=0).
+struct OpenCkOut {
+  uint32_t* d_w = nullptr;
+  uint32_t* h_w = nullptr;
+  uint8_t* checked = nullptr;  // [4]
+};
 static void kzg_quotients_batch(qg_ctx* ctx, const qg_srs* srs, const Fr* const polys[4],
-                                const size_t Lt[4], const Fr xs[4], qg_kzg_opening* const outs[4],
-                                std::vector<const Fr*>& qs, std::vector<size_t>& qns, Fr* h_y,
+                                const size_t ns[4], const size_t Lt[4], const Fr xs[4],
+                                qg_kzg_opening* const outs[4], std::vector<const Fr*>& qs,
+                                std::vector<size_t>& qns, Fr* h_y, const OpenCkOut& ck,
                                 size_t slot = 0) {
   std::vector<ShIn> jobs;
   Fr* s[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1088,12 +1378,25 @@ static void kzg_quotients_batch(qg_ctx* ctx, const qg_srs* srs, const Fr* const 
     QgTimed tm(ctx, "kzg_division");
     suffix_horner_batch(ctx, jobs);
   }
+  for (int i = 0; i < 4; i++)
+    if (s[i]) fault_quotient(ctx, s[i] + 1, Lt[i] - 1);
   Fr* d_y = ctx->scratch_as<Fr>("open_y#" + std::to_string(slot), 4);
   QG_HIP(hipMemsetAsync(d_y, 0, 4 * sizeof(Fr), ctx->stream));
   for (int i = 0; i < 4; i++)
     if (s[i])
       QG_HIP(hipMemcpyAsync(d_y + i, s[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
   QG_HIP(hipMemcpyAsync(h_y, d_y, 4 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+  if (ck.d_w) {
+    OpenCk c4[4];
+    for (int i = 0; i < 4; i++) {
+      c4[i] = {ns[i] ? polys[i] : nullptr, ns[i], s[i] ? s[i] + 1 : nullptr,
+               s[i] ? Lt[i] - 1 : 0,       d_y + i, xs[i]};
+      ck.checked[i] = s[i] ? CK_QUOT : ns[i] ? CK_ZERO : CK_NONE;
+    }
+    open_check_queue(ctx, c4, ck.d_w);
+    QG_HIP(hipMemcpyAsync(ck.h_w, ck.d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          ctx->stream));
+  }
   qs.clear();
   qns.clear();
   for (int i = 0; i < 4; i++) {
@@ -1106,7 +1409,8 @@ static void kzg_quotients_batch(qg_ctx* ctx, const qg_srs* srs, const Fr* const 
 static void kzg_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t L, const Fr& x,
                             qg_kzg_opening* out) {
   fr_export(x, out->x);
-  size_t Lt = trimmed_len(ctx, c, L);  // DensePolynomial::from_coefficients_slice trims
+  // DensePolynomial::from_coefficients_slice trims
+  size_t Lt = fault_short_trim(ctx, trimmed_len(ctx, c, L));
   Fr y = Fr::zero();
   G1Affine pi = G1Affine::infinity();
   if (Lt > 0) {
@@ -1115,11 +1419,30 @@ static void kzg_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t 
       QgTimed tm(ctx, "kzg_division");
       suffix_horner(ctx, c, Lt, x, s);
     }
+    fault_quotient(ctx, s + 1, Lt - 1);
     QG_HIP(hipMemcpyAsync(&y, s, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    // kzg.rs:85: p over all L coefficients, q as the MSM will read it
+    const bool check = open_check_on();
+    uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
+    if (check) {
+      uint32_t* d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
+      const OpenCk c4[4] = {{c, L, s + 1, Lt - 1, s, x}, {}, {}, {}};
+      open_check_queue(ctx, c4, d_w);
+      QG_HIP(hipMemcpyAsync(h_w, d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
     ctx->sync();
+    if (check) open_check_settle(ctx, {h_w[0]}, {CK_QUOT}, 1, OPEN_UNAME);
     // q_i = s_{i+1}, i < Lt - 1; commit(q) (kzg.rs:88-89)
     QG_CHECK(Lt - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
     pi = msm_device(ctx, srs, s + 1, Lt - 1);
+  } else if (L > 0 && open_check_on()) {  // trimmed to nothing: all L coefficients must be 0
+    uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
+    uint32_t* d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
+    const OpenCk c4[4] = {{c, L, nullptr, 0, nullptr, x}, {}, {}, {}};
+    open_check_queue(ctx, c4, d_w);
+    QG_HIP(hipMemcpyAsync(h_w, d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    open_check_settle(ctx, {h_w[0]}, {CK_ZERO}, 1, OPEN_UNAME);
   }
   fr_export(y, out->y);
   g1_export(pi, out->proof_xy, &out->proof_inf);
@@ -1151,7 +1474,7 @@ static void allgather_host(qg_ctx* ctx, const void* src, size_t bytes, void* dst
 
 // global trimmed length of a vector sliced as [rank * L, rank * L + nloc)
 static size_t trimmed_len_global(qg_ctx* ctx, const Fr* a, size_t nloc, size_t L) {
-  const uint64_t loc = nloc ? trimmed_len(ctx, a, nloc) : 0;
+  const uint64_t loc = nloc ? fault_short_trim(ctx, trimmed_len(ctx, a, nloc)) : 0;
   const uint64_t mine = loc ? (uint64_t)ctx->rank * L + loc : 0;
   std::vector<uint64_t> all(ctx->world);
   allgather_host(ctx, &mine, sizeof mine, all.data());
@@ -1162,8 +1485,10 @@ static size_t trimmed_len_global(qg_ctx* ctx, const Fr* a, size_t nloc, size_t L
 
 // KZG::open of a sharded polynomial (global trimmed length Lt, slices of L):
 // every rank gets the same opening; the quotient MSM is sharded.
+// With d_qev set, this rank's part of q(sigma) (its slice's sigma-power offset
+// included) is queued into *d_qev for the caller's quotient check.
 static void kzg_open_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t L, size_t Lt,
-                             const Fr& x, qg_kzg_opening* out) {
+                             const Fr& x, qg_kzg_opening* out, Fr* d_qev = nullptr) {
   const int world = ctx->world, rank = ctx->rank;
   const size_t off = (size_t)rank * L;
   const size_t le = Lt > off ? std::min(L, Lt - off) : 0;  // this rank's live coefficients
@@ -1199,6 +1524,11 @@ static void kzg_open_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t
   // q_i = s_{i+1} for global i < Lt - 1; this rank's part starts at s + 1
   const size_t qn = (Lt > 0 && Lt - 1 > off) ? std::min(le, Lt - 1 - off) : 0;
   QG_CHECK(qn <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+  fault_quotient(ctx, s + 1, qn);
+  if (d_qev) {
+    QgTimed tm(ctx, "kzg_open_check");
+    poly_eval_queue(ctx, {{s + 1, qn, (uint64_t)off}}, ctx->open_sigma, d_qev);
+  }
   const G1Affine pi = msm_device(ctx, srs, s + 1, qn);
   fr_export(y, out->y);
   g1_export(pi, out->proof_xy, &out->proof_inf);
@@ -1494,10 +1824,42 @@ static void mle_open_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* dpoly, si
   fr_export(evaluation, out->evaluation);
   g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
   const size_t Lt = trimmed_len_global(ctx, dpoly, L, L);
-  kzg_open_sharded(ctx, srs, dpoly, L, Lt, r, &out->poly_opening);
-  kzg_open_sharded(ctx, srs, dpoly, L, Lt, r_inv, &out->poly_opening_inv);
-  kzg_open_sharded(ctx, srs, Sl, L, Slen, r, &out->s_opening);
-  kzg_open_sharded(ctx, srs, Sl, L, Slen, r_inv, &out->s_opening_inv);
+  // the quotient check: this rank's parts of p(sigma), S(sigma) over its whole
+  // slices and of the four q(sigma), one exchange, the same sums and so the
+  // same decision on every rank
+  const bool check = open_check_on();
+  Fr* d_ev = check ? ctx->scratch_as<Fr>("open_ck_ev_sh", 6) : nullptr;
+  if (check) {
+    QgTimed tm(ctx, "kzg_open_check");
+    poly_eval_queue(ctx, {{dpoly, L, (uint64_t)off}, {Sl, L, (uint64_t)off}}, ctx->open_sigma, d_ev);
+  }
+  kzg_open_sharded(ctx, srs, dpoly, L, Lt, r, &out->poly_opening, check ? d_ev + 2 : nullptr);
+  kzg_open_sharded(ctx, srs, dpoly, L, Lt, r_inv, &out->poly_opening_inv, check ? d_ev + 3 : nullptr);
+  kzg_open_sharded(ctx, srs, Sl, L, Slen, r, &out->s_opening, check ? d_ev + 4 : nullptr);
+  kzg_open_sharded(ctx, srs, Sl, L, Slen, r_inv, &out->s_opening_inv, check ? d_ev + 5 : nullptr);
+  if (check) {
+    const size_t W = (size_t)ctx->world;
+    Fr* d_all = ctx->scratch_as<Fr>("open_ck_ev_all", 6 * W);
+    comm_allgather_bytes(ctx, d_ev, d_all, 6 * sizeof(Fr));
+    std::vector<Fr> all(6 * W);
+    QG_HIP(hipMemcpyAsync(all.data(), d_all, 6 * W * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    const qg_kzg_opening* o4[4] = {&out->poly_opening, &out->poly_opening_inv, &out->s_opening,
+                                   &out->s_opening_inv};
+    const size_t glt[4] = {Lt, Lt, Slen, Slen};
+    std::vector<uint32_t> bad(4, 0);
+    std::vector<uint8_t> checked(4, 0);
+    for (int i = 0; i < 4; i++) {
+      Fr P = Fr::zero(), Q = Fr::zero();
+      for (size_t rk = 0; rk < W; rk++) {
+        P = P + all[6 * rk + (i < 2 ? 0 : 1)];
+        Q = Q + all[6 * rk + 2 + i];
+      }
+      checked[i] = glt[i] ? CK_QUOT : CK_ZERO;  // length 0: y = 0, q = 0, so p(sigma) == 0
+      bad[i] = open_check_host(P, fr_import(o4[i]->y), Q, ctx->open_sigma, fr_import(o4[i]->x));
+    }
+    open_check_settle(ctx, bad, checked, 4, OPEN_QNAME);
+  }
 }
 
 struct MleOpenItem {
@@ -1587,6 +1949,12 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
       QG_HIP(hipMemsetAsync(Sl[k], 0, L * sizeof(Fr), ctx->stream));
     }
     trim_launch(ctx, Sl[k], L, d_len + 2 * k + 1);
+  }
+  if (ctx->open_fault_live == 1) {  // test-only: this rank's first nonzero local length
+    ctx->open_fault_live = 0;
+    hipLaunchKernelGGL(k_fault_short_len, dim3(1), dim3(64), 0, ctx->stream, d_len, 2 * K,
+                       (unsigned long long)ctx->open_fault_value);
+    QG_LAUNCH_CHECK();
   }
   // exchange 1: dot parts and local lengths of every rank
   uint8_t* d_all = ctx->scratch_as<uint8_t>("mlebs_small_all", sm_bytes * W);
@@ -1705,8 +2073,47 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
     qn[j] = (glt[j] > 0 && glt[j] - 1 > off) ? std::min(le[j], glt[j] - 1 - off) : 0;
     QG_CHECK(qn[j] <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
     qs[j] = sq[j] + 1;
+    fault_quotient(ctx, sq[j] + 1, qn[j]);
+  }
+  // the quotient check: per item this rank's parts of p(sigma), S(sigma) and the
+  // four q(sigma); ONE more allgather per batch carries them (they exist only
+  // after the carries, which need exchange 2)
+  const bool check = open_check_on();
+  Fr* d_ev = check ? ctx->scratch_as<Fr>("open_ck_ev_sh", 6 * K) : nullptr;
+  if (check) {
+    QgTimed tm(ctx, "kzg_open_check");
+    std::vector<EvIn> in;
+    for (size_t k = 0; k < K; k++) {
+      const uint64_t off = (uint64_t)(rank * items[k].n);
+      in.push_back({items[k].poly, items[k].n, off});
+      in.push_back({Sl[k], items[k].n, off});
+      for (int i = 0; i < 4; i++) in.push_back({qs[4 * k + i], qn[4 * k + i], off});
+    }
+    poly_eval_queue(ctx, in, ctx->open_sigma, d_ev);
   }
   const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qn);
+  if (check) {
+    Fr* d_evall = ctx->scratch_as<Fr>("open_ck_ev_all", 6 * K * W);
+    comm_allgather_bytes(ctx, d_ev, d_evall, 6 * K * sizeof(Fr));
+    std::vector<Fr> all(6 * K * W);
+    QG_HIP(hipMemcpyAsync(all.data(), d_evall, all.size() * sizeof(Fr), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    ctx->sync();
+    std::vector<uint32_t> bad(J, 0);
+    std::vector<uint8_t> checked(J, 0);
+    for (size_t j = 0; j < J; j++) {
+      const size_t k = j / 4, i = j % 4;
+      Fr P = Fr::zero(), Q = Fr::zero();
+      for (size_t rk = 0; rk < W; rk++) {
+        P = P + all[6 * (rk * K + k) + (i < 2 ? 0 : 1)];
+        Q = Q + all[6 * (rk * K + k) + 2 + i];
+      }
+      checked[j] = glt[j] ? CK_QUOT : CK_ZERO;
+      bad[j] = open_check_host(P, ys[j], Q, ctx->open_sigma, xs[j]);
+    }
+    open_batch_trim_scratch(ctx, K);  // (before a failure leaves the call)
+    open_check_settle(ctx, bad, checked, 4, OPEN_QNAME);
+  }
   for (size_t k = 0; k < K; k++) {
     qg_kzg_opening* o4[4] = {&outs[k].poly_opening, &outs[k].poly_opening_inv,
                              &outs[k].s_opening, &outs[k].s_opening_inv};
@@ -1776,14 +2183,15 @@ static void mle_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* dpoly, siz
   G1Affine s_comm = msm_device(ctx, srs, dS, s_msm);
   ctx->sync();  // (drained already unless the MSM was empty)
   const Fr evaluation = *h_eval;
-  const size_t Slen = (size_t)h_len[1];
   size_t Lt = 0;
   if (lt_known) {
     Lt = (size_t)std::stoull(lt_memo.substr(lt_key.size()));
   } else {
     Lt = (size_t)h_len[0];
     lt_memo = poly_id ? lt_key + std::to_string(Lt) : std::string();
+    Lt = fault_short_trim(ctx, Lt);  // (after the memo: a faulted length is never remembered)
   }
+  const size_t Slen = fault_short_trim(ctx, (size_t)h_len[1]);
   // transcript: point (Vec<Fr>), evaluation, s_comm; draw r (mlpcs.rs:100-107)
   std::vector<uint8_t> msg(8 + 32 * nvars);
   u64_to_bytes(nvars, msg.data());
@@ -1804,14 +2212,24 @@ static void mle_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* dpoly, siz
   qg_kzg_opening* outs[4] = {&out->poly_opening, &out->poly_opening_inv, &out->s_opening,
                              &out->s_opening_inv};
   const Fr* polys[4] = {dpoly, dpoly, dS, dS};
+  const size_t ns[4] = {n, n, Sn, Sn};
   const size_t lts[4] = {Lt, Lt, Slen, Slen};
   const Fr xs[4] = {r, r_inv, r, r_inv};
   std::vector<const Fr*> qs;
   std::vector<size_t> qns;
   Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("open_y_h", 4 * sizeof(Fr)));
-  kzg_quotients_batch(ctx, srs, polys, lts, xs, outs, qs, qns, h_y);
+  OpenCkOut ck;
+  std::vector<uint8_t> checked(4, 0);
+  if (open_check_on()) {
+    ck.d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
+    ck.h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
+    ck.checked = checked.data();
+  }
+  kzg_quotients_batch(ctx, srs, polys, ns, lts, xs, outs, qs, qns, h_y, ck);
   const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
   ctx->sync();  // (drained already unless every quotient was empty)
+  if (ck.d_w)
+    open_check_settle(ctx, std::vector<uint32_t>(ck.h_w, ck.h_w + 4), checked, 4, OPEN_QNAME);
   for (int i = 0; i < 4; i++) {
     fr_export(h_y[i], outs[i]->y);
     g1_export(pis[i], outs[i]->proof_xy, &outs[i]->proof_inf);
@@ -1906,13 +2324,16 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
   ctx->sync();  // (drained already unless every MSM was empty)
   // the transcript steps in item order (mlpcs.rs:100-107)
   std::vector<Fr> rs(K), rinv(K);
-  std::vector<size_t> Lt(K);
+  std::vector<size_t> Lt(K), Lq(K);  // Lq: the length the quotients use (Lt unless faulted)
   for (size_t k = 0; k < K; k++) {
     const MleOpenItem& it = items[k];
-    if (lt_known[k])
+    if (lt_known[k]) {
       Lt[k] = k == 0 ? (size_t)std::stoull(memo_in.substr(lt_key[k].size())) : Lt[k - 1];
-    else
+      Lq[k] = Lt[k];
+    } else {
       Lt[k] = (size_t)h_len[2 * k];
+      Lq[k] = fault_short_trim(ctx, Lt[k]);
+    }
     lt_memo = it.id ? lt_key[k] + std::to_string(Lt[k]) : std::string();
     const Fr evaluation = h_eval[k];
     std::vector<uint8_t> msg(8 + 32 * it.nvars);
@@ -1935,21 +2356,37 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
   Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("mleb_y_h", 4 * K * sizeof(Fr)));
   std::vector<const Fr*> qs_all;
   std::vector<size_t> qns_all;
+  const bool check = open_check_on();
+  std::vector<uint8_t> checked(4 * K, 0);
+  uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 4 * K) : nullptr;
+  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * K * sizeof(uint32_t)));
+  if (check) {  // the evaluation's span scratch at its largest before anything is queued
+    size_t nmax = 0;
+    for (size_t k = 0; k < K; k++) nmax = std::max(nmax, std::max(items[k].n, Sn[k]));
+    poly_eval_reserve(ctx, 6, nmax);
+  }
   for (size_t k = 0; k < K; k++) {
     qg_kzg_opening* o4[4] = {&outs[k].poly_opening, &outs[k].poly_opening_inv,
                              &outs[k].s_opening, &outs[k].s_opening_inv};
     const Fr* polys[4] = {items[k].poly, items[k].poly, dS[k], dS[k]};
-    const size_t slen = (size_t)h_len[2 * k + 1];
-    const size_t lts[4] = {Lt[k], Lt[k], slen, slen};
+    const size_t slen = fault_short_trim(ctx, (size_t)h_len[2 * k + 1]);
+    const size_t ns[4] = {items[k].n, items[k].n, Sn[k], Sn[k]};
+    const size_t lts[4] = {Lq[k], Lq[k], slen, slen};
     const Fr xs[4] = {rs[k], rinv[k], rs[k], rinv[k]};
     std::vector<const Fr*> qs;
     std::vector<size_t> qns;
-    kzg_quotients_batch(ctx, srs, polys, lts, xs, o4, qs, qns, h_y + 4 * k, k);
+    OpenCkOut ck;
+    if (check) ck.d_w = d_w + 4 * k, ck.h_w = h_w + 4 * k, ck.checked = checked.data() + 4 * k;
+    kzg_quotients_batch(ctx, srs, polys, ns, lts, xs, o4, qs, qns, h_y + 4 * k, ck, k);
     qs_all.insert(qs_all.end(), qs.begin(), qs.end());
     qns_all.insert(qns_all.end(), qns.begin(), qns.end());
   }
   const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs_all, qns_all);
   ctx->sync();  // (drained already unless every quotient was empty)
+  if (check) {
+    open_batch_trim_scratch(ctx, K);  // (before a failure leaves the call)
+    open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + 4 * K), checked, 4, OPEN_QNAME);
+  }
   for (size_t k = 0; k < K; k++) {
     qg_kzg_opening* o4[4] = {&outs[k].poly_opening, &outs[k].poly_opening_inv,
                              &outs[k].s_opening, &outs[k].s_opening_inv};
@@ -1961,9 +2398,76 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
   open_batch_trim_scratch(ctx, K);
 }
 
+// One opening call: draws its check point sigma and makes an armed test fault
+// live for exactly this call.  sigma never touches the transcript.  The ranks
+// of a sharded group need the same sigma: at the first sharded opening rank
+// 0's seed is shared once (allgather_host) and every rank reseeds with it;
+// opening calls are collective, so the generators then step in lockstep.
+// QG_OPEN_CHECK_SEED=<u64> (read per call) fixes the point instead.
+// The share runs whether or not QG_OPEN_CHECK is on, and a fixed seed does not
+// step the context generator, so lockstep assumes what the other per-call
+// switches assume already: every rank of a group - in a multi-process group,
+// every process - runs with the same QG_OPEN_CHECK* environment.
+struct OpenCall {
+  qg_ctx* c;
+  explicit OpenCall(qg_ctx* ctx) : c(ctx) {
+    c->open_fault_live = c->open_fault_armed;
+    c->open_fault_armed = 0;
+    try {
+      if (c->sharded && !c->open_rng_shared) {
+        const uint64_t mine = c->open_rng();
+        std::vector<uint64_t> all((size_t)c->world);
+        allgather_host(c, &mine, sizeof mine, all.data());
+        c->open_rng.seed(all[0]);
+        c->open_rng_shared = true;
+      }
+    } catch (...) {
+      c->open_fault_live = 0;
+      throw;
+    }
+    const char* e = getenv("QG_OPEN_CHECK_SEED");
+    std::mt19937_64 fixed(e ? strtoull(e, nullptr, 0) : 0);
+    std::mt19937_64& g = e ? fixed : c->open_rng;
+    uint64_t w[4];
+    for (uint64_t& v : w) v = g();
+    w[3] &= (1ull << 61) - 1;  // < 2^253 < r: a valid representative, uniform over 2^253 values
+    c->open_sigma = fr_import(w);
+  }
+  ~OpenCall() { c->open_fault_live = 0; }
+};
+
 }  // namespace qg
 
 extern "C" {
+
+int qg_poly_eval_dev(qg_ctx* ctx, const qg_buf* poly, size_t n, const uint64_t x[4],
+                     uint64_t shift, uint64_t out[4]) {
+  if (!ctx || !poly || n > poly->n || !x || !out) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    QG_HIP(hipSetDevice(ctx->device));
+    Fr* d = ctx->scratch_as<Fr>("ev_out", 1);
+    poly_eval_queue(ctx, {{poly->d, n, shift}}, fr_import(x), d);
+    Fr r;
+    QG_HIP(hipMemcpyAsync(&r, d, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    fr_export(r, out);
+  });
+}
+
+int qg_debug_open_fault(qg_ctx* ctx, uint32_t kind, uint64_t value) {
+  if (!ctx || kind > 3) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    QG_HIP(hipSetDevice(ctx->device));
+    ctx->open_fault_armed = kind == 3 ? 0 : kind;
+    ctx->open_fault_value = value;
+    if (kind == 3) {  // poison trim_launch's stamp word (nothing else remains of the stamp)
+      unsigned long long* tail = ctx->scratch_as<unsigned long long>("trim_tail", 1);
+      const unsigned long long v = value;
+      QG_HIP(hipMemcpyAsync(tail, &v, sizeof v, hipMemcpyHostToDevice, ctx->stream));
+      ctx->sync();
+    }
+  });
+}
 
 int qg_inner_product(qg_ctx* ctx, const uint64_t* f, size_t nf, const uint64_t* g, size_t ng,
                      uint64_t out[4]) {
@@ -2002,6 +2506,7 @@ int qg_kzg_open(qg_ctx* ctx, const qg_srs* srs, const uint64_t* poly, size_t n, 
   if (!ctx || !srs || (!poly && n) || !x || !out) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] {
     QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
     Fr* d = ctx->scratch_as<Fr>("open_in", n ? n : 1);
     fr_upload(ctx, d, poly, n);
     kzg_open_device(ctx, srs, d, n, fr_import(x), out);
@@ -2014,6 +2519,7 @@ int qg_mle_open(qg_ctx* ctx, const qg_srs* srs, const uint64_t* poly, size_t n,
   return qg_guard(ctx, [&] {
     QG_CHECK(nvars <= 30, QG_ERR_INVALID, "too many variables");
     QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
     Fr* dpoly = ctx->scratch_as<Fr>("mle_poly", n ? n : 1);
     fr_upload(ctx, dpoly, poly, n);
     mle_open_device(ctx, srs, dpoly, n, point, nvars, state, out);
@@ -2027,6 +2533,7 @@ int qg_mle_open_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_t n
   return qg_guard(ctx, [&] {
     QG_CHECK(nvars <= 30, QG_ERR_INVALID, "too many variables");
     QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
     mle_open_device(ctx, srs, poly->d, n, point, nvars, state, out);
   });
 }
@@ -2041,6 +2548,7 @@ int qg_mle_open_batch_dev(qg_ctx* ctx, const qg_srs* srs, const qg_mle_open_item
   return qg_guard(ctx, [&] {
     QG_CHECK(k <= 256, QG_ERR_UNSUPPORTED, "too many openings in one batch (at most 256)");
     QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
     std::vector<MleOpenItem> v(k);
     for (size_t i = 0; i < k; i++)
       v[i] = {items[i].poly->d, items[i].n, items[i].point, items[i].nvars,
@@ -2059,6 +2567,7 @@ int qg_mle_open_dev_ex(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_
   return qg_guard(ctx, [&] {
     QG_CHECK(nvars <= 30, QG_ERR_INVALID, "too many variables");
     QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
     mle_open_device(ctx, srs, poly->d, n, point, nvars, state, out,
                     (flags & QG_OPEN_UNCHANGED) != 0, poly->alloc_id, poly->base_off);
   });

@@ -165,6 +165,8 @@ PROTOTYPES = {
     "qg_ctx_phase_split": (C.c_int, [P, C.POINTER(C.c_char_p), SZ, C.POINTER(C.c_double)]),
     "qg_trace_marker": (C.c_int, [P, C.c_uint32]),
     "qg_ctx_counter": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "qg_poly_eval_dev": (C.c_int, [P, P, SZ, U64P, C.c_uint64, U64P]),
+    "qg_debug_open_fault": (C.c_int, [P, C.c_uint32, C.c_uint64]),
 }
 
 _lib = None

@@ -77,6 +77,11 @@ class Device:
         check(lib().qg_ctx_counter(self.h, name.encode(), C.byref(v)), self.h)
         return v.value
 
+    def debug_open_fault(self, kind: int, value: int = 0):
+        """TEST ONLY: arm a one-shot fault for the next opening call
+        (qg_debug_open_fault; 1 short trim, 2 quotient, 3 stamp word, 0 disarm)"""
+        check(lib().qg_debug_open_fault(self.h, kind, value), self.h)
+
     def attach_loopback(self, group, rank: int, world: int = None):
         check(lib().qg_ctx_attach_loopback(self.h, group, rank), self.h)
         self.rank = rank
@@ -242,6 +247,15 @@ class DeviceVec:
     def fill_random(self, seed: int):
         check(lib().qg_buf_fill_random(self.h, seed), self.dev.h)
         return self
+
+    def evaluate(self, x: int, n: int = None, shift: int = 0) -> int:
+        """sum_{i<n} self[i] * x^(shift+i) on the device (qg_poly_eval_dev;
+        DensePolynomial::evaluate, kzg.rs:78)"""
+        from .field import fr_from_mont_limbs
+        n = self.n if n is None else n
+        out = (C.c_uint64 * 4)()
+        check(lib().qg_poly_eval_dev(self.dev.h, self.h, n, fr_c(x), shift, out), self.dev.h)
+        return fr_from_mont_limbs(list(out))
 
     def to_numpy(self, n=None):
         """raw Montgomery limbs, shape (n, 4) uint64"""
