@@ -507,6 +507,84 @@ int qg_debug_open_fault(qg_ctx* ctx, uint32_t kind, uint64_t value);
 int qg_selftest_inverse(qg_ctx* ctx, int field, int on_device, const uint64_t* in, uint64_t* out,
                         size_t n);
 
+/* ---- TEST ONLY: the 29-bit-limb layer, one primitive at a time -------------
+ * Field elements cross as their raw 9 x uint32 limbs (csrc/field29.h F29), so
+ * a test can pass non-canonical representatives and almost-normalized / lazy
+ * limb shapes, and reads back the representation, not only the residue.  Every
+ * entry runs one thread (or one quad of lanes) per case, addresses nothing
+ * with the data, and returns QG_ERR_INVALID for null pointers, an unknown op
+ * or field, or more than 65536 cases. */
+
+/* ops of qg_selftest_field29; operands a0..a7, results r0..r3 (unused: 0) */
+#define QG_F29_MUL 0           /* r0 = mul29(a0, a1) */
+#define QG_F29_SQR 1           /* r0 = sqr29(a0) */
+#define QG_F29_MULSUB 2        /* r0 = mulsub29(a0, a1, a2, a3) */
+#define QG_F29_MULT 3          /* r0 = mul29t(a0, a1)                (device only) */
+#define QG_F29_SQRT 4          /* r0 = sqr29t(a0)                    (device only) */
+#define QG_F29_MULSUBT 5       /* r0 = mulsub29t(a0, a1, a2, a3)     (device only) */
+#define QG_F29_MULT2 6         /* mul29t2(a0, a1, a2, a3, r0, r1)    (device only) */
+#define QG_F29_SQRT2 7         /* sqr29t2(a0, a1, r0, r1)            (device only) */
+#define QG_F29_MULTN3 8        /* mul29tn<3>: r[i] = a[i] a[4 + i]   (device only) */
+#define QG_F29_MULTN4 9        /* mul29tn<4>                         (device only) */
+#define QG_F29_MULTN3_ALIAS 10 /* mul29tn<3> with r aliasing a       (device only) */
+#define QG_F29_MULTN4_ALIAS 11 /* mul29tn<4> with r aliasing a       (device only) */
+#define QG_F29_NORM 12         /* r0 = norm29(a0) */
+#define QG_F29_NORMFULL 13     /* r0 = normfull29(a0) */
+#define QG_F29_RED2P 14        /* r0 = red2p29(a0) */
+#define QG_F29_RED6P 15        /* r0 = red6p29(a0) */
+#define QG_F29_RED16P 16       /* r0 = red16p29(a0) */
+#define QG_F29_CANON 17        /* r0 = canon29(a0) */
+#define QG_F29_ISZERO8 18      /* r0 limb 0 = is_zero_mod29_fast<8>(a0) */
+#define QG_F29_ISZERO20 19     /* r0 limb 0 = is_zero_mod29_fast<20>(a0) */
+#define QG_F29_RELIMB 20       /* r0 = to29(from29(a0)) */
+#define QG_F29_OP_COUNT 21
+#define QG_SELFTEST_F29_IN 72  /* uint32 per case in `in`: a0..a7 */
+#define QG_SELFTEST_F29_OUT 36 /* uint32 per case in `out`: r0..r3 */
+/* field 0 = Fr, 1 = Fq.  on_device = 0 runs the host build of the primitives
+ * (ctx may be NULL; the device-only forms give QG_ERR_UNSUPPORTED), on_device
+ * = 1 their gfx950 build on ctx, one thread per case. */
+int qg_selftest_field29(qg_ctx* ctx, int field, int op, int on_device, const uint32_t* in, size_t n,
+                        uint32_t* out);
+
+/* ops of qg_selftest_curve29 (csrc/curve29.h, csrc/msm.hip; Fq, R = 2^261).
+ * A case's input is two points p, q of 4 x 9 limbs each (X, Y, ZZ, ZZZ); an
+ * affine operand is q's X, Y. */
+#define QG_X29_ADD 0        /* x29_add(p, q) */
+#define QG_X29_DBL 1        /* x29_dbl(p) */
+#define QG_X29_ADD_AFFINE 2 /* x29_add_affine(p, (q.X, q.Y)) */
+#define QG_X29_ACC_FINISH 3 /* x29_acc_finish(p) */
+#define QG_X29_RAW 4        /* x29_unraw(x29_raw(p)) */
+#define QG_X29_ACC_MADD 5   /* x29_acc_madd_tp(p, q.X, q.Y), then x29_acc_madd_exc when it
+                               returned false, as k_msm_accumulate does    (device only) */
+#define QG_X29_ADD_Q4 6     /* x29_add_q4(p, q) on one quad of lanes      (device only) */
+#define QG_X29_DBL_Q4 7     /* x29_dbl_q4(p) on one quad of lanes         (device only) */
+#define QG_X29_OP_COUNT 8
+#define QG_SELFTEST_X29_IN 72     /* uint32 per case in `in` */
+#define QG_SELFTEST_X29_OUT 36    /* uint32 per case in `out` (one point) ... */
+#define QG_SELFTEST_X29_OUT_Q4 144 /* ... or the point every lane 0..3 of the quad returned */
+#define QG_X29_FLAG_MAIN 1u /* x29_acc_madd_tp returned true */
+#define QG_X29_FLAG_EXC 2u  /* x29_acc_madd_exc ran */
+#define QG_X29_FLAG_INF 4u  /* ... and reported infinity (the accumulator is then stale) */
+/* flags[i] (one uint32 per case) is written for every op, nonzero only for
+ * QG_X29_ACC_MADD.  Cases keep their order: case i of a _Q4 op runs on lanes
+ * 4 i .. 4 i + 3, so neighbouring cases share a wave.  The host path (ctx may
+ * be NULL) gives QG_ERR_UNSUPPORTED for the device-only ops. */
+int qg_selftest_curve29(qg_ctx* ctx, int op, int on_device, const uint32_t* in, size_t n,
+                        uint32_t* out, uint32_t* flags);
+
+/* One level of the MSM's bucket-reduction fold: launches k_msm_wfold (quad-
+ * cooperative when q4, groups of 16 elements; else single-lane, groups of 64)
+ * on m <= 65536 elements (A_e, Y_e) per MSM of `batch` <= 16, element e of
+ * MSM b at index b istride + e (istride >= m), in the kernel's input layout:
+ * XYZZ of 4 x 8 uint32 words per point, plain integers < 2p in the R = 2^261
+ * domain, ZZ == 0 for infinity.  Group w writes A_out[b mo + w] = sum_g A_g +
+ * g Y_g over its elements (mo = ceil(m / group)) and, when want_y, Y_out[...] =
+ * group sum_g Y_g in the same layout; without want_y (the last level) Y_out
+ * is ignored and A_out is canonical in the host's R = 2^256 Montgomery form. */
+int qg_selftest_msm_fold(qg_ctx* ctx, int q4, const uint32_t* A, const uint32_t* Y, uint32_t m,
+                         uint32_t batch, size_t istride, int want_y, uint32_t* A_out,
+                         uint32_t* Y_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,10 @@ PROTOTYPES = {
     "qg_ctx_counter": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_uint64)]),
     "qg_poly_eval_dev": (C.c_int, [P, P, SZ, U64P, C.c_uint64, U64P]),
     "qg_debug_open_fault": (C.c_int, [P, C.c_uint32, C.c_uint64]),
+    "qg_selftest_field29": (C.c_int, [P, C.c_int, C.c_int, C.c_int, U32P, C.c_size_t, U32P]),
+    "qg_selftest_curve29": (C.c_int, [P, C.c_int, C.c_int, U32P, C.c_size_t, U32P, U32P]),
+    "qg_selftest_msm_fold": (C.c_int, [P, C.c_int, U32P, U32P, C.c_uint32, C.c_uint32,
+                                       C.c_size_t, C.c_int, U32P, U32P]),
 }
 
 _lib = None

@@ -124,6 +124,28 @@ def test_invalid_arguments_return_status(L):
     assert L.qg_sumcheck_prove_cb(None, 1, 0, None, prog, 1, None, 0, C.cast(None, L.qg_sumcheck_prove_cb.argtypes[8]),
                                   None, None, None, None, None) == -1
     assert L.qg_ctx_phase_split(None, None, 0, None) == -1
+    # the 29-bit-limb self-tests: null pointers, unknown op / field, too many
+    # cases, a device run without a context -> QG_ERR_INVALID, never a fault
+    w = (C.c_uint32 * 144)()
+    fl = (C.c_uint32 * 1)()
+    assert L.qg_selftest_field29(None, 1, 0, 0, None, 1, w) == -1
+    assert L.qg_selftest_field29(None, 1, 0, 0, w, 1, None) == -1
+    assert L.qg_selftest_field29(None, 2, 0, 0, w, 1, w) == -1
+    assert L.qg_selftest_field29(None, -1, 0, 0, w, 1, w) == -1
+    assert L.qg_selftest_field29(None, 1, 21, 0, w, 1, w) == -1
+    assert L.qg_selftest_field29(None, 1, -1, 0, w, 1, w) == -1
+    assert L.qg_selftest_field29(None, 1, 0, 0, w, 65537, w) == -1
+    assert L.qg_selftest_field29(None, 1, 0, 1, w, 1, w) == -1
+    assert L.qg_selftest_field29(None, 1, 0, 0, w, 1, w) == 0
+    assert L.qg_selftest_curve29(None, 0, 0, None, 1, w, fl) == -1
+    assert L.qg_selftest_curve29(None, 0, 0, w, 1, None, fl) == -1
+    assert L.qg_selftest_curve29(None, 0, 0, w, 1, w, None) == -1
+    assert L.qg_selftest_curve29(None, 8, 0, w, 1, w, fl) == -1
+    assert L.qg_selftest_curve29(None, -1, 0, w, 1, w, fl) == -1
+    assert L.qg_selftest_curve29(None, 0, 0, w, 65537, w, fl) == -1
+    assert L.qg_selftest_curve29(None, 0, 1, w, 1, w, fl) == -1
+    assert L.qg_selftest_curve29(None, 0, 0, w, 1, w, fl) == 0
+    assert L.qg_selftest_msm_fold(None, 1, w, w, 1, 1, 1, 0, w, None) == -1
 
 
 def test_no_device_is_an_error_not_a_fallback():
