@@ -435,6 +435,37 @@ int qg_logup_column_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const qg_
                         const uint64_t* m_consts, size_t m_nconsts, const uint64_t beta[4],
                         qg_buf* out, uint64_t out_sum[4]);
 
+/* Multiplicities of a Logup lookup (the column the reference's callers build by
+ * hand, hyperplonk/src/piops/lookup.rs:186-193): out_m[j] = #{ i : src row i ==
+ * table row j } as Fr, for `ncols` source columns of `src_len` entries and
+ * `ncols` table columns of `tab_len` entries.  A row is the tuple of its ncols
+ * entries; two rows are equal only if every column is.  Inputs must be
+ * canonical Montgomery words (values < r, as everywhere in this ABI): rows are
+ * compared as 32-byte words.  Duplicate table rows: a tuple the table holds at
+ * several rows is counted whole at the LOWEST such row and the others get 0 (a
+ * valid Logup assignment; out_m is a function of the inputs alone and equal
+ * from run to run).
+ * `first_missing` (nullable) receives -1 when every source row is in the table
+ * (QG_OK).  Otherwise the call returns QG_ERR_ASSERT (the prover would emit a
+ * proof that cannot verify), *first_missing is the lowest source row that is in
+ * no table row, qg_last_error names it, and the contents of out_m are
+ * undefined.  out_m must not alias an input column (QG_ERR_INVALID).
+ * Limits: 1 <= ncols <= 16, 1 <= tab_len < 2^31, 1 <= src_len < 2^32: zero
+ * lengths, null pointers and buffers shorter than their stated length return
+ * QG_ERR_INVALID, anything over the caps QG_ERR_UNSUPPORTED.  A context with a
+ * communicator attached (sharded) returns QG_ERR_UNSUPPORTED.
+ * QG_LOOKUP_HASH_BITS=<b> (read per call) keeps only the low b bits of the row
+ * hash (b = 0: one probe chain; a test switch, the result does not change). */
+int qg_lookup_multiplicities(qg_ctx* ctx, uint32_t ncols,
+                             const uint64_t* const* src_cols, size_t src_len,
+                             const uint64_t* const* tab_cols, size_t tab_len,
+                             uint64_t* out_m, int64_t* first_missing);
+/* Same with device-resident columns and output. */
+int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols,
+                                 const qg_buf* const* src_cols, size_t src_len,
+                                 const qg_buf* const* tab_cols, size_t tab_len,
+                                 qg_buf* out_m, int64_t* first_missing);
+
 /* Circuit::check_constraints for one constraint expression
  * (hyperplonk/src/frontend/transition_circuit.rs:153-172): `first_row`
  * receives the first row x of the hypercube (this rank's block) with

@@ -1,0 +1,372 @@
+// Multiplicities of a Logup lookup for gfx950 - the column the reference's
+// callers build by hand (hyperplonk/src/piops/lookup.rs:186-193, a byte-table
+// index trick in test code):
+//     m[j] = #{ i : source row i == table row j }
+// for a table of any content.  A row is the tuple of its ncols entries; the
+// inputs are canonical Montgomery words, so equality of the 32-byte words is
+// equality in Fr.  A tuple the table holds at several rows is counted at the
+// LOWEST of them (the others get 0): a valid Logup assignment, and m is then a
+// function of the inputs alone.
+//
+//  * k_lookup_build: an open-addressing table in HBM of cap = 2^ceil(log2(2 x
+//    tab_len)) uint32 slots (filled with 0xffffffff every call).  One thread
+//    per table row hashes its 8 x ncols limbs and probes linearly with
+//    atomicCAS(slot, EMPTY, j); a slot that already holds an equal row gets
+//    atomicMin(slot, j).  A slot's tuple never changes once set and no thread
+//    walks past an empty slot, so every tuple ends in exactly one slot, which
+//    holds its lowest row - whatever the order the threads ran in.
+//  * k_lookup_count (a separate launch: the slots are complete and visible at
+//    the kernel boundary): one thread per source row (grid stride) walks the
+//    same probe sequence to the first slot whose row equals its tuple and
+//    counts there; an empty slot first means the tuple is in no table row
+//    (atomicMin into first_missing, one lane per wave).
+//    Contention: a byte table under 2^22 source rows would put every atomic on
+//    256 addresses.  Tables of up to LK_LDS_ROWS rows are counted in per-block
+//    LDS counters, each nonzero one flushed to HBM once per block.  Above that
+//    the lanes of a wave that hit the leading lane's row are merged into one
+//    atomicAdd, for LK_MERGE_ROUNDS leaders (takes the heavy rows of a skewed
+//    source); the rest add on their own.  Integer adds commute: the counts are
+//    the same from run to run.
+//  * k_lookup_finish: m[j] = Fr::from(count[j]).
+//  * No thread waits on another: every probe loop is bounded by cap steps
+//    (cap >= 2 x tab_len, so an empty slot always exists) and running out sets
+//    an error word instead of running on.
+//  * QG_LOOKUP_HASH_BITS=<b> (read per call) keeps only the low b bits of the
+//    hash: b = 0 sends every row down one probe chain (tests).
+//    QG_LOOKUP_BLOCKS=<k> caps the count kernel's grid.
+#include <stdlib.h>
+
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+using namespace qg;
+
+namespace qg {
+
+static constexpr uint32_t LK_MAXCOLS = 16;
+static constexpr uint32_t LK_EMPTY = 0xffffffffu;
+static constexpr int LK_BLOCK = 256;        // build / finish
+static constexpr int LK_CBLOCK = 1024;      // count: two blocks fill a CU's 32 wave slots
+static constexpr uint32_t LK_LDS_ROWS = 16384;  // 64 KB of uint32 counters per block
+static constexpr int LK_MERGE_ROUNDS = 4;
+
+struct LkCols {
+  const Fr* c[LK_MAXCOLS];
+};
+
+// device words of one call: [0..1] first missing source row (u64), [2] error
+struct LkState {
+  unsigned long long first_missing;
+  uint32_t err;
+  uint32_t pad;
+};
+
+struct LkWord {
+  uint4 lo, hi;
+};
+QG_DEV LkWord lk_load(const Fr* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  return {q[0], q[1]};
+}
+QG_DEV bool lk_same(const LkWord& a, const LkWord& b) {
+  return ((a.lo.x ^ b.lo.x) | (a.lo.y ^ b.lo.y) | (a.lo.z ^ b.lo.z) | (a.lo.w ^ b.lo.w) |
+          (a.hi.x ^ b.hi.x) | (a.hi.y ^ b.hi.y) | (a.hi.z ^ b.hi.z) | (a.hi.w ^ b.hi.w)) == 0;
+}
+
+QG_DEV uint32_t lk_mix(uint32_t h, uint32_t k) {  // murmur3 body
+  k *= 0xcc9e2d51u;
+  k = (k << 15) | (k >> 17);
+  k *= 0x1b873593u;
+  h ^= k;
+  h = (h << 13) | (h >> 19);
+  return h * 5u + 0xe6546b64u;
+}
+
+// hash of row `row` of `cols` (all 8 limbs of every column), cut to hash_mask
+QG_DEV uint32_t lk_hash(const LkCols& cols, uint32_t ncols, size_t row, uint32_t hash_mask) {
+  uint32_t h = 0x9747b28cu;
+  for (uint32_t c = 0; c < ncols; c++) {
+    const LkWord w = lk_load(cols.c[c] + row);
+    h = lk_mix(h, w.lo.x);
+    h = lk_mix(h, w.lo.y);
+    h = lk_mix(h, w.lo.z);
+    h = lk_mix(h, w.lo.w);
+    h = lk_mix(h, w.hi.x);
+    h = lk_mix(h, w.hi.y);
+    h = lk_mix(h, w.hi.z);
+    h = lk_mix(h, w.hi.w);
+  }
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h & hash_mask;
+}
+
+// row a of A == row b of B, column by column
+QG_DEV bool lk_rows_equal(const LkCols& A, size_t a, const LkCols& B, size_t b, uint32_t ncols) {
+  for (uint32_t c = 0; c < ncols; c++)
+    if (!lk_same(lk_load(A.c[c] + a), lk_load(B.c[c] + b))) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_build(LkCols tab, uint32_t ncols,
+                                                           uint32_t tab_len,
+                                                           uint32_t* __restrict__ slots,
+                                                           uint64_t cap, uint32_t hash_mask,
+                                                           LkState* __restrict__ st) {
+  const uint64_t j64 = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (j64 >= tab_len) return;
+  const uint32_t j = (uint32_t)j64;
+  const uint64_t mask = cap - 1;
+  uint64_t s = lk_hash(tab, ncols, j, hash_mask) & mask;
+  for (uint64_t it = 0; it < cap; it++, s = (s + 1) & mask) {
+    const uint32_t prev = atomicCAS(&slots[s], LK_EMPTY, j);
+    if (prev == LK_EMPTY) return;
+    // prev < tab_len: only build threads write slots, and only row indices
+    if (prev < tab_len && lk_rows_equal(tab, prev, tab, j, ncols)) {
+      atomicMin(&slots[s], j);
+      return;
+    }
+  }
+  atomicOr(&st->err, 1u);
+}
+
+// LDS = true: tab_len <= LK_LDS_ROWS, per-block counters in LDS
+template <bool LDS>
+__global__ __launch_bounds__(LK_CBLOCK) void k_lookup_count(LkCols src, LkCols tab, uint32_t ncols,
+                                                            uint64_t src_len, uint32_t tab_len,
+                                                            const uint32_t* __restrict__ slots,
+                                                            uint64_t cap, uint32_t hash_mask,
+                                                            uint32_t* __restrict__ count,
+                                                            LkState* __restrict__ st) {
+  __shared__ uint32_t lc[LDS ? LK_LDS_ROWS : 1];
+  if (LDS) {
+    for (uint32_t j = threadIdx.x; j < tab_len; j += LK_CBLOCK) lc[j] = 0;
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63;
+  const uint64_t mask = cap - 1;
+  const uint64_t stride = (uint64_t)gridDim.x * LK_CBLOCK;
+  // every lane of a wave runs the same number of rounds (the ballots below)
+  const uint64_t rounds = (src_len + stride - 1) / stride;
+  uint64_t i = (uint64_t)blockIdx.x * LK_CBLOCK + threadIdx.x;
+  for (uint64_t r = 0; r < rounds; r++, i += stride) {
+    const bool live = i < src_len;
+    uint32_t hit = LK_EMPTY;
+    bool missing = false;
+    if (live) {
+      uint64_t s = lk_hash(src, ncols, i, hash_mask) & mask;
+      bool done = false;
+      for (uint64_t it = 0; it < cap; it++, s = (s + 1) & mask) {
+        const uint32_t k = slots[s];
+        if (k == LK_EMPTY) {
+          missing = done = true;
+          break;
+        }
+        if (k < tab_len && lk_rows_equal(tab, k, src, i, ncols)) {
+          hit = k;
+          done = true;
+          break;
+        }
+      }
+      if (!done) atomicOr(&st->err, 1u);
+    }
+    // lowest missing row: i grows with the lane, so the first lane that
+    // missed holds this wave's lowest; skip what cannot lower the word
+    const unsigned long long miss = __ballot(missing);
+    if (miss && lane == __ffsll(miss) - 1 &&
+        i < __hip_atomic_load(&st->first_missing, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMin(&st->first_missing, (unsigned long long)i);
+    if (LDS) {
+      if (hit != LK_EMPTY) atomicAdd(&lc[hit], 1u);
+    } else {
+      unsigned long long todo = __ballot(hit != LK_EMPTY);
+      for (int m = 0; m < LK_MERGE_ROUNDS && todo; m++) {
+        const int leader = __ffsll(todo) - 1;
+        const uint32_t lr = __shfl(hit, leader, 64);
+        const unsigned long long same = __ballot(hit == lr);  // lr != EMPTY: hits only
+        if (lane == leader) atomicAdd(&count[lr], (uint32_t)__popcll(same));
+        todo &= ~same;
+      }
+      if ((todo >> lane) & 1) atomicAdd(&count[hit], 1u);
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < tab_len; j += LK_CBLOCK) {
+      const uint32_t c = lc[j];
+      if (c) atomicAdd(&count[j], c);
+    }
+  }
+}
+
+// m[j] = Fr::from(count[j])
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_finish(const uint32_t* __restrict__ count,
+                                                            uint32_t tab_len,
+                                                            Fr* __restrict__ out) {
+  const uint64_t j = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (j >= tab_len) return;
+  Fr x = Fr::zero();
+  x.v[0] = count[j];
+  out[j] = to_mont(x);
+}
+
+// QG_LOOKUP_HASH_BITS=<b>, read per call: keep the low b bits of the hash
+static uint32_t lookup_hash_mask() {
+  const char* hb = getenv("QG_LOOKUP_HASH_BITS");
+  if (!hb || !hb[0]) return 0xffffffffu;
+  const int b = atoi(hb);
+  if (b <= 0) return 0u;
+  return b >= 32 ? 0xffffffffu : (1u << b) - 1u;
+}
+
+// QG_LOOKUP_BLOCKS=<k>, read per call: caps the count kernel's grid (default two
+// blocks per CU), so a small input runs several grid-stride rounds
+static size_t lookup_count_blocks(qg_ctx* ctx) {
+  const char* lb = getenv("QG_LOOKUP_BLOCKS");
+  const int k = lb ? atoi(lb) : 0;
+  return k > 0 ? (size_t)k : 2 * (size_t)ctx->num_cus();
+}
+
+static void lookup_check_lengths(const qg_ctx* ctx, uint32_t ncols, size_t src_len,
+                                 size_t tab_len) {
+  QG_CHECK(ncols >= 1 && src_len >= 1 && tab_len >= 1, QG_ERR_INVALID,
+           "lookup multiplicities need at least one column, source row and table row");
+  QG_CHECK(ncols <= LK_MAXCOLS, QG_ERR_UNSUPPORTED, "lookup multiplicities: more than 16 columns");
+  QG_CHECK((uint64_t)tab_len < (1ull << 31), QG_ERR_UNSUPPORTED,
+           "lookup multiplicities: table of 2^31 rows or more");
+  QG_CHECK((uint64_t)src_len < (1ull << 32), QG_ERR_UNSUPPORTED,
+           "lookup multiplicities: 2^32 source rows or more");
+  QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
+           "lookup multiplicities are not supported on a sharded context (communicator attached)");
+}
+
+// d_out[j] = multiplicity of table row j; returns the lowest source row that is
+// in no table row, or -1
+static int64_t lookup_run(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t src_len,
+                          const LkCols& tab, size_t tab_len, Fr* d_out) {
+  uint64_t cap = 2;
+  while (cap < 2 * (uint64_t)tab_len) cap <<= 1;
+  const uint32_t hash_mask = lookup_hash_mask();
+  uint32_t* d_slots = ctx->scratch_as<uint32_t>("lk_slots", cap);
+  uint32_t* d_count = ctx->scratch_as<uint32_t>("lk_count", tab_len);
+  LkState* d_st = ctx->scratch_as<LkState>("lk_state", 1);
+  const uint32_t tl = (uint32_t)tab_len;
+  {
+    QgTimed tm(ctx, "lookup_build");
+    // nothing of an earlier call survives: slots, counters and the state words
+    QG_HIP(hipMemsetAsync(d_slots, 0xff, cap * sizeof(uint32_t), ctx->stream));
+    QG_HIP(hipMemsetAsync(&d_st->first_missing, 0xff, sizeof(unsigned long long), ctx->stream));
+    QG_HIP(hipMemsetAsync(&d_st->err, 0, 2 * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(k_lookup_build, dim3(div_up(tab_len, LK_BLOCK)), dim3(LK_BLOCK), 0,
+                       ctx->stream, tab, ncols, tl, d_slots, cap, hash_mask, d_st);
+    QG_LAUNCH_CHECK();
+  }
+  {
+    QgTimed tm(ctx, "lookup_count");
+    QG_HIP(hipMemsetAsync(d_count, 0, tab_len * sizeof(uint32_t), ctx->stream));
+    const size_t want = div_up(src_len, LK_CBLOCK);
+    const unsigned grid = (unsigned)std::min<size_t>(want, lookup_count_blocks(ctx));
+    if (tab_len <= LK_LDS_ROWS)
+      hipLaunchKernelGGL(k_lookup_count<true>, dim3(grid), dim3(LK_CBLOCK), 0, ctx->stream, src,
+                         tab, ncols, (uint64_t)src_len, tl, d_slots, cap, hash_mask, d_count, d_st);
+    else
+      hipLaunchKernelGGL(k_lookup_count<false>, dim3(grid), dim3(LK_CBLOCK), 0, ctx->stream, src,
+                         tab, ncols, (uint64_t)src_len, tl, d_slots, cap, hash_mask, d_count, d_st);
+    QG_LAUNCH_CHECK();
+  }
+  {
+    QgTimed tm(ctx, "lookup_finish");
+    hipLaunchKernelGGL(k_lookup_finish, dim3(div_up(tab_len, LK_BLOCK)), dim3(LK_BLOCK), 0,
+                       ctx->stream, d_count, tl, d_out);
+    QG_LAUNCH_CHECK();
+  }
+  LkState h;
+  QG_HIP(hipMemcpyAsync(&h, d_st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  QG_CHECK(!h.err, QG_ERR_DEVICE, "lookup multiplicities: probe sequence exhausted");
+  return h.first_missing >= (unsigned long long)src_len ? -1 : (int64_t)h.first_missing;
+}
+
+static void lookup_report(int64_t miss, int64_t* first_missing) {
+  if (first_missing) *first_missing = miss;
+  QG_CHECK(miss < 0, QG_ERR_ASSERT,
+           "lookup source row " + std::to_string(miss) + " is in no table row");
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+template <class T>
+static bool lk_overlap(const T* a, size_t na, const T* b, size_t nb) {
+  return a < b + nb && b < a + na;
+}
+
+}  // namespace qg
+
+// ---------------------------------------------------------------- C-ABI
+extern "C" {
+
+int qg_lookup_multiplicities(qg_ctx* ctx, uint32_t ncols, const uint64_t* const* src_cols,
+                             size_t src_len, const uint64_t* const* tab_cols, size_t tab_len,
+                             uint64_t* out_m, int64_t* first_missing) {
+  if (!ctx) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
+    lookup_check_lengths(ctx, ncols, src_len, tab_len);
+    for (uint32_t c = 0; c < ncols; c++) {
+      QG_CHECK(src_cols[c] && tab_cols[c], QG_ERR_INVALID, "null column");
+      QG_CHECK(!lk_overlap(out_m, 4 * tab_len, src_cols[c], 4 * src_len) &&
+                   !lk_overlap(out_m, 4 * tab_len, tab_cols[c], 4 * tab_len),
+               QG_ERR_INVALID, "output aliases an input column");
+    }
+    QG_HIP(hipSetDevice(ctx->device));
+    Fr* d = ctx->scratch_as<Fr>("lk_in", (size_t)ncols * (src_len + tab_len) + tab_len);
+    LkCols src{}, tab{};
+    for (uint32_t c = 0; c < ncols; c++) {
+      Fr* s = d + (size_t)c * src_len;
+      Fr* t = d + (size_t)ncols * src_len + (size_t)c * tab_len;
+      fr_upload(ctx, s, src_cols[c], src_len);
+      fr_upload(ctx, t, tab_cols[c], tab_len);
+      src.c[c] = s;
+      tab.c[c] = t;
+    }
+    Fr* d_out = d + (size_t)ncols * (src_len + tab_len);
+    if (first_missing) *first_missing = -1;
+    const int64_t miss = lookup_run(ctx, ncols, src, src_len, tab, tab_len, d_out);
+    lookup_report(miss, first_missing);
+    fr_download(ctx, out_m, d_out, tab_len);
+    ctx->sync();
+  });
+}
+
+int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols, const qg_buf* const* src_cols,
+                                 size_t src_len, const qg_buf* const* tab_cols, size_t tab_len,
+                                 qg_buf* out_m, int64_t* first_missing) {
+  if (!ctx) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
+    lookup_check_lengths(ctx, ncols, src_len, tab_len);
+    QG_CHECK(out_m->n >= tab_len, QG_ERR_INVALID, "output buffer too short");
+    LkCols src{}, tab{};
+    for (uint32_t c = 0; c < ncols; c++) {
+      QG_CHECK(src_cols[c] && src_cols[c]->n >= src_len, QG_ERR_INVALID,
+               "source column buffer missing or too short");
+      QG_CHECK(tab_cols[c] && tab_cols[c]->n >= tab_len, QG_ERR_INVALID,
+               "table column buffer missing or too short");
+      QG_CHECK(!lk_overlap(out_m->d, tab_len, src_cols[c]->d, src_len) &&
+                   !lk_overlap(out_m->d, tab_len, tab_cols[c]->d, tab_len),
+               QG_ERR_INVALID, "output aliases an input column");
+      src.c[c] = src_cols[c]->d;
+      tab.c[c] = tab_cols[c]->d;
+    }
+    QG_HIP(hipSetDevice(ctx->device));
+    if (first_missing) *first_missing = -1;
+    const int64_t miss = lookup_run(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
+    lookup_report(miss, first_missing);
+  });
+}
+
+}  // extern "C"

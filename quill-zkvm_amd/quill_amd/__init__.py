@@ -12,7 +12,7 @@ from .pcs import (KZG, EvaluationClaim, KZGOpeningProof, MLEvalProof, g2_generat
                   g2_mul, pairing)
 from .transcript import Transcript  # noqa: F401
 from .logup import (LookupMode, LookupProof, MultisetEqualityProof,  # noqa: F401
-                    PermutationCheckProof, SetInclusionProof)
+                    PermutationCheckProof, SetInclusionProof, lookup_multiplicities)
 from .frontend import StateCell, TransitionCircuit, TransitionCircuitTarget  # noqa: F401
 from .proof import (HyperPlonk, HyperPlonkProof, TracePK, TraceProof, TraceVK,  # noqa: F401
                     TraceWitness)

@@ -152,6 +152,10 @@ PROTOTYPES = {
     "qg_logup_column_dev": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(P),
                                       C.POINTER(ExprOp), SZ, U64P, SZ, C.POINTER(ExprOp), SZ,
                                       U64P, SZ, U64P, P, U64P]),
+    "qg_lookup_multiplicities": (C.c_int, [P, C.c_uint32, C.POINTER(U64P), SZ, C.POINTER(U64P),
+                                           SZ, U64P, C.POINTER(C.c_int64)]),
+    "qg_lookup_multiplicities_dev": (C.c_int, [P, C.c_uint32, C.POINTER(P), SZ, C.POINTER(P), SZ,
+                                               P, C.POINTER(C.c_int64)]),
     "qg_expr_first_nonzero_dev": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(P),
                                             C.POINTER(ExprOp), SZ, U64P, SZ,
                                             C.POINTER(C.c_int64)]),

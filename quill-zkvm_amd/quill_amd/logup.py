@@ -14,7 +14,7 @@ import numpy as np
 
 from ._lib import check, lib
 from .device import Device, DeviceVec
-from .field import R_MOD, eq_eval, fr_c, fr_from_mont_limbs, fr_list, u64p
+from .field import R_MOD, eq_eval, fr_c, fr_from_mont_limbs, fr_inv, fr_list, u64p
 from .hyperplonk import (SumcheckProof, VirtualPolyExpr, VirtualPolynomialStore, _default_device,
                          _program_c, _tables_c)
 from .pcs import EvaluationClaim
@@ -70,6 +70,58 @@ def logup_column_device(dev: Device, num_vars: int, tables, h_expr: VirtualPolyE
                                     hp[3], mp[0], mp[1], mp[2], mp[3], fr_c(beta), out.h, s),
           dev.h)
     return fr_from_mont_limbs(list(s))
+
+
+def _input_columns(store: VirtualPolynomialStore, cols):
+    """table indices of virtual polynomials that are plain Input(k) expressions"""
+    out = []
+    for c in cols:
+        e = store.virtual_polys[c]
+        if e.kind != "in":
+            raise ValueError("lookup_multiplicities: column %d is not a plain Input(k) expression "
+                             "(there is no column materialiser)" % c)
+        out.append(e.args[0])
+    return out
+
+
+def lookup_multiplicities(source_store: VirtualPolynomialStore, source_cols,
+                          dest_store: VirtualPolynomialStore, dest_cols, dev: Device = None):
+    """The multiplicity column of a Logup lookup (what lookup.rs:186-193 builds
+    by hand): m[j] = number of source rows equal to table row j, a row being the
+    tuple of its columns; a tuple the table holds at several rows is counted at
+    the lowest of them.  `source_cols` / `dest_cols` are virtual-polynomial
+    indices that must be plain Input(k) expressions (ValueError otherwise).
+    Host stores return a list of ints (qg_lookup_multiplicities), device stores
+    a DeviceVec (qg_lookup_multiplicities_dev).  A source row that is in no
+    table row raises QuillGpuError(QG_ERR_ASSERT) naming the lowest such row."""
+    if len(source_cols) != len(dest_cols):
+        raise ValueError("The number of source and destination columns must be equal")
+    if source_store.on_device != dest_store.on_device:
+        raise ValueError("lookup_multiplicities: source and destination stores must both be "
+                         "host stores or both device stores")
+    sc, dc = _input_columns(source_store, source_cols), _input_columns(dest_store, dest_cols)
+    k = len(sc)
+    ns, nt = source_store.local_len, dest_store.local_len
+    miss = C.c_int64(-1)
+    if source_store.on_device:
+        d = dest_store.dev
+        out = DeviceVec(d, nt, pooled=True)
+        sp = (C.c_void_p * max(k, 1))(*[source_store.polynomials[i].h.value for i in sc])
+        tp = (C.c_void_p * max(k, 1))(*[dest_store.polynomials[i].h.value for i in dc])
+        try:
+            check(lib().qg_lookup_multiplicities_dev(d.h, k, sp, ns, tp, nt, out.h,
+                                                     C.byref(miss)), d.h)
+        except Exception:
+            out.close()
+            raise
+        return out
+    dev = dev or _default_device()
+    sa, sp = _tables_c([source_store.polynomials[i] for i in sc])
+    ta, tp = _tables_c([dest_store.polynomials[i] for i in dc])
+    out = np.zeros((max(nt, 1), 4), dtype=np.uint64)
+    check(lib().qg_lookup_multiplicities(dev.h, k, sp, ns, tp, nt, u64p(out), C.byref(miss)),
+          dev.h)
+    return fr_list(out[:nt])
 
 
 def _eq_for(store: VirtualPolynomialStore, dev: Device, z):
@@ -218,6 +270,46 @@ class SetInclusionProof:
         orr = pcs.open(right, clr.point, transcript)
         return SetInclusionProof(cl, cr, scl, scr, ol, orr), (cll.point, clr.point)
 
+    def verify(self, transcript: Transcript, pcs, h_left_claim: EvaluationClaim,
+               h_right_claim: EvaluationClaim, multiplicities_claim: EvaluationClaim):
+        """set_inclusion.rs:237-347; raises ValueError with the reference's Err.
+        The claims are assumed checked separately, as in the reference."""
+        nl, nr = len(h_left_claim.point), len(h_right_claim.point)
+        gamma = transcript.draw_field_element()  # logup_eval_point
+        transcript.append_g1(self.denom_left_commitment)
+        transcript.append_g1(self.denom_right_commitment)
+        z1 = [transcript.draw_field_element() for _ in range(nl)]
+        alpha = transcript.draw_field_element()
+        left = self.sumcheck_proof_left.verify(transcript)
+        z2 = [transcript.draw_field_element() for _ in range(nr)]
+        beta = transcript.draw_field_element()
+        right = self.sumcheck_proof_right.verify(transcript)
+        if not pcs.verify(self.denom_left_commitment, self.opening_proof_denom_left, transcript):
+            raise ValueError("Left denominator opening proof failed")
+        if not pcs.verify(self.denom_right_commitment, self.opening_proof_denom_right,
+                          transcript):
+            raise ValueError("Right denominator opening proof failed")
+        dl = self.opening_proof_denom_left.evaluation
+        dr = self.opening_proof_denom_right.evaluation
+        if left.point != self.opening_proof_denom_left.point():
+            raise ValueError("Left sumcheck point does not match PCS opening point")
+        if (list(h_left_claim.point) != left.point or list(h_right_claim.point) != right.point
+                or list(multiplicities_claim.point) != right.point):
+            raise ValueError("Mismatched evaluation points for set inclusion")
+        if right.point != self.opening_proof_denom_right.point():
+            raise ValueError("Right sumcheck point does not match PCS opening point")
+        lz = dl * (gamma + h_left_claim.evaluation) - 1
+        if (lz * eq_eval(left.point, z1) + alpha * dl - left.evaluation) % R_MOD != 0:
+            raise ValueError("Left sumcheck evaluation mismatch")
+        rz = dr * (gamma + h_right_claim.evaluation) - multiplicities_claim.evaluation
+        if (rz * eq_eval(right.point, z2) + beta * dr - right.evaluation) % R_MOD != 0:
+            raise ValueError("Right sumcheck evaluation mismatch")
+        # division by a challenge: ark's `/` panics on zero, like fr_inv here
+        v1 = self.sumcheck_proof_left.claimed_sum * fr_inv(alpha) % R_MOD
+        v2 = self.sumcheck_proof_right.claimed_sum * fr_inv(beta) % R_MOD
+        if v1 != v2:
+            raise ValueError("Log-derivative sums do not match")
+
 
 @dataclass
 class PermutationCheckProof:
@@ -264,10 +356,19 @@ class LookupProof:
     @staticmethod
     def prove(source_store: VirtualPolynomialStore, source_cols, dest_store: VirtualPolynomialStore,
               dest_cols, multiplicities, transcript: Transcript, pcs):
-        """lookup.rs:28-84 -> (proof, (source point, dest point))."""
+        """lookup.rs:28-84 -> (proof, (source point, dest point)).
+        multiplicities=None: the column is counted on the device
+        (lookup_multiplicities), allocated in `dest_store` and made a virtual
+        polynomial before anything reaches the transcript, so the proof and the
+        transcript are those of a caller who supplied the same column; a source
+        row that is in no table row raises there."""
         assert len(source_cols) == len(dest_cols), \
             "The number of source and destination columns must be equal"
         n = len(source_cols)
+        if multiplicities is None:
+            assert n > 0, "Lookup must be applied to at least one column"
+            m = lookup_multiplicities(source_store, source_cols, dest_store, dest_cols, pcs.dev)
+            multiplicities = dest_store.new_virtual_from_input(dest_store.allocate_polynomial(m))
         transcript.append_u64(n)
         assert n > 0, "Lookup must be applied to at least one column"
         alpha = transcript.draw_field_element()
@@ -284,6 +385,27 @@ class LookupProof:
                                              transcript, pcs)
         return LookupProof(proof), pts
 
+    def verify(self, transcript: Transcript, pcs, source_claims, dest_claims,
+               multiplicities_claim: EvaluationClaim):
+        """lookup.rs:87-141 (claims are EvaluationClaim, assumed checked
+        separately); raises ValueError with the reference's Err"""
+        n = len(source_claims)
+        if len(dest_claims) != n:
+            raise ValueError("Mismatched lookup evaluation vector lengths")
+        transcript.append_u64(n)
+        alpha = transcript.draw_field_element()
+        ap = [pow(alpha, i, R_MOD) for i in range(n)]
+        # indexing claim 0 panics on an empty vector in the reference
+        sp, dp = list(source_claims[0].point), list(dest_claims[0].point)
+        for c in source_claims:  # lookup.rs:106-112 compares the source points (twice)
+            if list(c.point) != sp:
+                raise ValueError("Lookup evaluation points for columns are inconsistent")
+        se = sum(c.evaluation * a for c, a in zip(source_claims, ap)) % R_MOD
+        de = sum(c.evaluation * a for c, a in zip(dest_claims, ap)) % R_MOD
+        self.set_inclusion_proof.verify(transcript, pcs, EvaluationClaim(sp, se),
+                                        EvaluationClaim(dp, de), multiplicities_claim)
 
-__all__ = ["LookupMode", "logup_column", "logup_column_device", "MultisetEqualityProof",
+
+__all__ = ["LookupMode", "logup_column", "logup_column_device", "lookup_multiplicities",
+           "MultisetEqualityProof",
            "SetInclusionProof", "PermutationCheckProof", "LookupProof", "EvaluationClaim"]
