@@ -271,6 +271,49 @@ typedef struct qg_mle_open_item {
 int qg_mle_open_batch_dev(qg_ctx* ctx, const qg_srs* srs, const qg_mle_open_item* items,
                           size_t k, uint8_t state[32], qg_mle_proof* outs);
 
+/* ---------------------------------------------------------------- inner-product argument */
+/* InnerProductProof (pcs/src/ipa.rs:40-53), fields in the reference's order. */
+typedef struct qg_ipa_proof {
+  uint64_t inner_product[4];
+  uint64_t s_comm_xy[8];
+  uint8_t s_comm_inf;
+  uint8_t _pad[7];
+  qg_kzg_opening f_opening;
+  qg_kzg_opening f_opening_inv;
+  qg_kzg_opening g_opening;
+  qg_kzg_opening g_opening_inv;
+  qg_kzg_opening s_opening;
+  qg_kzg_opening s_opening_inv;
+} qg_ipa_proof;
+
+/* InnerProductProof::prove (ipa.rs:59-112) for the coefficient vectors f (nf)
+ * and g (ng): inner_product = sum_i f[i] g[i] over min(nf, ng); S is the
+ * polynomial of the zero-padded pair (ipa.rs:122-157), trimmed before its
+ * commitment and its openings; the transcript appends inner_product, then
+ * s_comm, and draws r; the six KZG::open of f, g and S at r and 1/r come from
+ * the trimmed polynomials, each quotient checked like every opening's
+ * ("open_checks"); last the assertion of ipa.rs:94-100 on the six y.
+ * Like the reference, the commitments to f and g are the caller's to absorb
+ * into the transcript beforehand.
+ * QG_ERR_INVALID: nf == 0 && ng == 0 (the reference underflows 2 max_len - 1),
+ * a null handle or pointer, a length beyond the buffer, a quotient or S longer
+ * than the SRS ("Polynomial degree exceeds max degree").  QG_ERR_ASSERT: r == 0,
+ * a failed quotient check ("Polynomial division failed", naming which of
+ * "f at r", "f at 1/r", "g at r", "g at 1/r", "S at r", "S at 1/r"), or
+ * "Inner product verification equation failed".  QG_ERR_UNSUPPORTED: a context
+ * with a communicator attached (the sharded S polynomial takes an eq-table g
+ * only).
+ * The call transforms f in the scratch the ML opening keeps its transform in:
+ * a QG_OPEN_UNCHANGED opening after it recomputes its transform.
+ * QG_IPA_PAIRED=1 (read per call) runs the six quotients as three paired
+ * suffix-Horner jobs (one pass over each polynomial for r and 1/r) instead of
+ * six single ones; the proof is identical. */
+int qg_ipa_prove(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf, const uint64_t* g,
+                 size_t ng, uint8_t state[32], qg_ipa_proof* out);
+/* Same, on device-resident vectors (the first nf / ng entries). */
+int qg_ipa_prove_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf, const qg_buf* g,
+                     size_t ng, uint8_t state[32], qg_ipa_proof* out);
+
 /* ---------------------------------------------------------------- verifiers (host) */
 /* BN254 G2 affine points on the D-type twist E'/Fq2 (y^2 = x^3 + 3/(9 + u)):
  * x.c0, x.c1, y.c0, y.c1, each 4 u64 Montgomery limbs (like G1's Fq). */
@@ -309,6 +352,15 @@ int qg_kzg_verify(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_i
  * inner-product equation at r.  `state` advances exactly as the prover's. */
 int qg_mle_verify(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
                   const uint64_t* point, size_t nvars, const qg_mle_proof* proof,
+                  uint8_t state[32], int* ok);
+/* InnerProductProof::verify (ipa.rs:160-202) against the commitments to f
+ * (comm1) and g (comm2): the six KZG checks first; if one fails, *ok = 0 and
+ * `state` is left untouched (the reference returns before it appends).
+ * Otherwise appends inner_product and s_comm, draws r and checks the equation
+ * at r; `state` then advances exactly as the prover's.  Like the reference,
+ * the openings' own x are not compared with r. */
+int qg_ipa_verify(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                  const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
                   uint8_t state[32], int* ok);
 
 /* Building blocks of the opening, exposed for testing and for callers that

@@ -305,6 +305,173 @@ static void suffix_horner_batch(qg_ctx* ctx, const std::vector<ShIn>& in, int de
   QG_LAUNCH_CHECK();
 }
 
+// more than four scans: groups of four, one after the other in stream order
+// (the groups share the recursion's chunk scratch, which no group reads after
+// its own apply pass)
+static void suffix_horner_many(qg_ctx* ctx, const std::vector<ShIn>& in) {
+  for (size_t b = 0; b < in.size(); b += 4)
+    suffix_horner_batch(
+        ctx, std::vector<ShIn>(in.begin() + b, in.begin() + std::min(in.size(), b + 4)));
+}
+
+// Paired form: one job is (c, L, x0, x1), the two scans of ONE polynomial that
+// the inner-product argument opens at r and 1/r (ipa.rs:87-92, and its TODO
+// at :86).  A thread carries two accumulators over the same coefficient strip
+// and writes two suffix vectors: the coefficient loads and their to29
+// conversions are shared, and the per-chunk Horner chain - the latency the
+// comment above names - runs as two independent chains per thread.  Each
+// chain performs exactly the steps of the single-job kernels, so the outputs
+// are bit-identical to two single jobs.
+struct ShJob2 {
+  const Fr* c;
+  size_t L;
+  L9 x[2];         // x_k 2^261 mod p
+  Fr* A[2];        // chunk values (local pass)
+  const Fr* T[2];  // chunk carries (apply pass)
+  size_t nch;
+  Fr* s[2];        // output suffixes
+};
+static constexpr int SH_P = 3;  // paired jobs per launch (f, g, S)
+struct ShJobs2 {
+  ShJob2 j[SH_P];
+};
+
+__device__ __forceinline__ void sh_apply_chunk2(const Fr* __restrict__ c, Fr* __restrict__ out0,
+                                                Fr* __restrict__ out1, size_t s, size_t e,
+                                                const F29<FrP>& x0, const F29<FrP>& x1,
+                                                F29<FrP> a0, F29<FrP> a1) {
+  if (e - s == SH_B) {
+    Fr cur[SH_G], nxt[SH_G];
+#pragma unroll
+    for (int j = 0; j < SH_G; j++) cur[j] = c[s + SH_B - SH_G + j];
+#pragma unroll
+    for (int g = SH_B / SH_G - 1; g >= 0; g--) {
+      if (g > 0) {
+#pragma unroll
+        for (int j = 0; j < SH_G; j++) nxt[j] = c[s + (size_t)(g - 1) * SH_G + j];
+      }
+      asm volatile("" ::: "memory");  // (as in sh_apply_chunk)
+#pragma unroll
+      for (int j = SH_G - 1; j >= 0; j--) {
+        const F29<FrP> cj = to29(cur[j]);
+        a0 = red2p29(add29(cj, mul29(x0, a0)));
+        a1 = red2p29(add29(cj, mul29(x1, a1)));
+        out0[s + (size_t)g * SH_G + j] = from29(canon29(a0));
+        out1[s + (size_t)g * SH_G + j] = from29(canon29(a1));
+      }
+      if (g > 0) {
+#pragma unroll
+        for (int j = 0; j < SH_G; j++) cur[j] = nxt[j];
+      }
+    }
+  } else {
+    for (size_t i = e; i-- > s;) {
+      const F29<FrP> ci = to29(c[i]);
+      a0 = red2p29(add29(ci, mul29(x0, a0)));
+      a1 = red2p29(add29(ci, mul29(x1, a1)));
+      out0[i] = from29(canon29(a0));
+      out1[i] = from29(canon29(a1));
+    }
+  }
+}
+
+__global__ void k_sh_local_b2(ShJobs2 jb) {
+  const ShJob2& J = jb.j[blockIdx.y];
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t s = k * SH_B;
+  if (s >= J.L) return;
+  const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
+  const F29<FrP> x0 = F29<FrP>::from_l9(J.x[0]), x1 = F29<FrP>::from_l9(J.x[1]);
+  F29<FrP> a0 = F29<FrP>::zero(), a1 = F29<FrP>::zero();
+#pragma unroll 4
+  for (size_t i = e; i-- > s;) {
+    const F29<FrP> ci = to29(J.c[i]);
+    a0 = red2p29(add29(ci, mul29(x0, a0)));
+    a1 = red2p29(add29(ci, mul29(x1, a1)));
+  }
+  J.A[0][k] = from29(canon29(a0));
+  J.A[1][k] = from29(canon29(a1));
+}
+
+__global__ void k_sh_apply_b2(ShJobs2 jb) {
+  const ShJob2& J = jb.j[blockIdx.y];
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t s = k * SH_B;
+  if (s >= J.L) return;
+  const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
+  const F29<FrP> x0 = F29<FrP>::from_l9(J.x[0]), x1 = F29<FrP>::from_l9(J.x[1]);
+  const bool carry = k + 1 < J.nch;
+  const F29<FrP> a0 = carry ? to29(J.T[0][k + 1]) : F29<FrP>::zero();
+  const F29<FrP> a1 = carry ? to29(J.T[1][k + 1]) : F29<FrP>::zero();
+  sh_apply_chunk2(J.c, J.s[0], J.s[1], s, e, x0, x1, a0, a1);
+}
+
+__global__ void k_sh_serial_b2(ShJobs2 jb) {
+  const ShJob2& J = jb.j[blockIdx.y];
+  if (threadIdx.x != 0) return;
+  const F29<FrP> x0 = F29<FrP>::from_l9(J.x[0]), x1 = F29<FrP>::from_l9(J.x[1]);
+  F29<FrP> a0 = F29<FrP>::zero(), a1 = F29<FrP>::zero();
+  for (size_t i = J.L; i-- > 0;) {
+    const F29<FrP> ci = to29(J.c[i]);
+    a0 = red2p29(add29(ci, mul29(x0, a0)));
+    a1 = red2p29(add29(ci, mul29(x1, a1)));
+    J.s[0][i] = from29(canon29(a0));
+    J.s[1][i] = from29(canon29(a1));
+  }
+}
+
+struct ShIn2 {
+  const Fr* c;
+  size_t L;
+  Fr x[2];  // Montgomery
+  Fr* s[2];
+};
+
+// s^k_i = c_i + x_k s^k_{i+1}, k = 0, 1, for up to SH_P polynomials at once.
+// The chunk values of the two points are two different vectors, so the levels
+// above run as single jobs (suffix_horner_many).
+static void suffix_horner_pairs(qg_ctx* ctx, const std::vector<ShIn2>& in) {
+  QG_CHECK(in.size() <= (size_t)SH_P, QG_ERR_ASSERT, "suffix-Horner pair batch of at most 3");
+  std::vector<ShIn2> small, big;
+  for (const ShIn2& q : in)
+    if (q.L > SH_B) big.push_back(q);
+    else if (q.L > 0) small.push_back(q);
+  if (!small.empty()) {
+    ShJobs2 jb{};
+    for (size_t q = 0; q < small.size(); q++) {
+      ShJob2& j = jb.j[q];
+      j.c = small[q].c, j.L = small[q].L;
+      for (int k = 0; k < 2; k++) j.x[k] = x261_of(small[q].x[k]), j.s[k] = small[q].s[k];
+    }
+    hipLaunchKernelGGL(k_sh_serial_b2, dim3(1, (unsigned)small.size()), dim3(64), 0, ctx->stream,
+                       jb);
+    QG_LAUNCH_CHECK();
+  }
+  if (big.empty()) return;
+  ShJobs2 jb{};
+  std::vector<ShIn> up;
+  size_t maxch = 0;
+  for (size_t q = 0; q < big.size(); q++) {
+    const size_t nch = (big[q].L + SH_B - 1) / SH_B;
+    ShJob2& j = jb.j[q];
+    j.c = big[q].c, j.L = big[q].L, j.nch = nch;
+    for (int k = 0; k < 2; k++) {
+      const std::string tag = std::to_string(2 * q + k);
+      Fr* A = ctx->scratch_as<Fr>("shp_A" + tag, nch);
+      Fr* T = ctx->scratch_as<Fr>("shp_T" + tag, nch);
+      j.x[k] = x261_of(big[q].x[k]), j.A[k] = A, j.T[k] = T, j.s[k] = big[q].s[k];
+      up.push_back({A, nch, fpow_small(big[q].x[k], SH_B), T});  // T_k = A_k + x^B T_{k+1}
+    }
+    maxch = std::max(maxch, nch);
+  }
+  const dim3 grid((unsigned)div_up(maxch, ML_BLOCK), (unsigned)big.size());
+  hipLaunchKernelGGL(k_sh_local_b2, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
+  QG_LAUNCH_CHECK();
+  suffix_horner_many(ctx, up);
+  hipLaunchKernelGGL(k_sh_apply_b2, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
+  QG_LAUNCH_CHECK();
+}
+
 // ---------------------------------------------------------------- polynomial evaluation
 // DensePolynomial::evaluate (kzg.rs:78) as a reduction: sum_i c_i x^i of up to
 // EV_MAXJ vectors per launch (blockIdx.y = job, like ShJobs) in the 29-bit
@@ -2436,6 +2603,149 @@ struct OpenCall {
   ~OpenCall() { c->open_fault_live = 0; }
 };
 
+// ---------------------------------------------------------------- inner-product argument
+// InnerProductProof::prove (ipa.rs:59-112) on two device-resident coefficient
+// vectors, shaped like mle_open_device: two host round trips, one for the S
+// commitment the transcript absorbs, one for the six quotient commitments.
+// The trimmed lengths, the inner product and the six values y are queued into
+// pinned memory and read after those synchronizations.  S is computed by the
+// general-g branch of s_poly_device; it is called without a buffer identity,
+// so it clears the "ntt_F_src" memo: after this call no QG_OPEN_UNCHANGED
+// opening finds a transform to reuse (ntt_F now holds f's).
+// The six openings are three polynomials at r and 1/r (the TODO at ipa.rs:86):
+// six single suffix-Horner jobs, or with QG_IPA_PAIRED=1 (read per call) three
+// paired ones (suffix_horner_pairs); the same bits either way.  Measured
+// (profiles/ipa_cost.json): the single jobs' kzg_division is
+// 2-3 % shorter at 2^20 coefficients; at 2^22 the two are within 2 %.
+static const char* const IPA_QNAME[6] = {"f at r", "f at 1/r", "g at r",
+                                         "g at 1/r", "S at r", "S at 1/r"};
+
+static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_t nf,
+                             const Fr* dg, size_t ng, uint8_t state[32], qg_ipa_proof* out) {
+  const size_t M = nf > ng ? nf : ng;  // >= 1 (the caller's check)
+  const size_t Sn = M - 1;
+  unsigned long long* h_len = reinterpret_cast<unsigned long long*>(
+      ctx->pinned_get("ipa_len_h", 3 * sizeof(unsigned long long)));
+  unsigned long long* d_len = ctx->scratch_as<unsigned long long>("ipa_len", 3);
+  // DensePolynomial::from_coefficients_slice trims what KZG::open is given (kzg.rs:77)
+  trim_launch(ctx, df, nf, d_len);
+  trim_launch(ctx, dg, ng, d_len + 1);
+  // <f, g> over the common prefix (ipa.rs:66-69)
+  Fr* d_ip = ctx->scratch_as<Fr>("ipa_ip", 1);
+  Fr* h_ip = reinterpret_cast<Fr*>(ctx->pinned_get("ipa_ip_h", sizeof(Fr)));
+  dot_to_device(ctx, df, dg, nf < ng ? nf : ng, d_ip);
+  QG_HIP(hipMemcpyAsync(h_ip, d_ip, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+  // S of the zero-padded pair (ipa.rs:72, :122-157); an empty operand gives S = 0
+  Fr* dS = ctx->scratch_as<Fr>("ipa_S", Sn ? Sn : 1);
+  if (Sn) {
+    if (nf && ng) s_poly_device(ctx, df, nf, dg, ng, dS);
+    else QG_HIP(hipMemsetAsync(dS, 0, Sn * sizeof(Fr), ctx->stream));
+  }
+  trim_launch(ctx, dS, Sn, d_len + 2);
+  QG_HIP(hipMemcpyAsync(h_len, d_len, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                        ctx->stream));
+  // its commitment (ipa.rs:73), as mle_open_device commits its S
+  size_t s_msm = Sn;
+  if (Sn > srs->n) {
+    ctx->sync();
+    s_msm = (size_t)h_len[2];
+    QG_CHECK(s_msm <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+  }
+  const G1Affine s_comm = msm_device(ctx, srs, dS, s_msm);
+  ctx->sync();  // (drained already unless the MSM was empty)
+  const Fr ip = *h_ip;
+  const size_t Lf = fault_short_trim(ctx, (size_t)h_len[0]);
+  const size_t Lg = fault_short_trim(ctx, (size_t)h_len[1]);
+  const size_t Ls = fault_short_trim(ctx, (size_t)h_len[2]);
+  // transcript: inner_product, s_comm; draw r (ipa.rs:76-83)
+  uint8_t b32[32], b64[64];
+  fr_to_bytes(ip, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr r = transcript_draw_fr(state);
+  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  const Fr r_inv = finv(r);
+  fr_export(ip, out->inner_product);
+  g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
+  // six KZG::open (ipa.rs:87-92): the quotients, then their commitments as one MSM batch
+  qg_kzg_opening* outs[6] = {&out->f_opening, &out->f_opening_inv, &out->g_opening,
+                             &out->g_opening_inv, &out->s_opening, &out->s_opening_inv};
+  const Fr* polys[3] = {df, dg, dS};
+  const size_t ns[3] = {nf, ng, Sn};
+  const size_t lts[3] = {Lf, Lg, Ls};
+  const Fr xs[2] = {r, r_inv};
+  Fr* s[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 6; i++) {
+    fr_export(xs[i & 1], outs[i]->x);
+    const size_t L = lts[i >> 1];
+    if (L == 0) continue;
+    QG_CHECK(L - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+    s[i] = ctx->scratch_as<Fr>("ipa_s#" + std::to_string(i), L);
+  }
+  const char* pe = getenv("QG_IPA_PAIRED");
+  const bool paired = pe && atoi(pe) != 0;
+  {
+    QgTimed tm(ctx, "kzg_division");
+    if (paired) {
+      std::vector<ShIn2> jobs;
+      for (int p = 0; p < 3; p++)
+        if (lts[p]) jobs.push_back({polys[p], lts[p], {r, r_inv}, {s[2 * p], s[2 * p + 1]}});
+      suffix_horner_pairs(ctx, jobs);
+    } else {
+      std::vector<ShIn> jobs;
+      for (int i = 0; i < 6; i++)
+        if (s[i]) jobs.push_back({polys[i >> 1], lts[i >> 1], xs[i & 1], s[i]});
+      suffix_horner_many(ctx, jobs);
+    }
+  }
+  for (int i = 0; i < 6; i++)
+    if (s[i]) fault_quotient(ctx, s[i] + 1, lts[i >> 1] - 1);
+  Fr* d_y = ctx->scratch_as<Fr>("ipa_y", 6);
+  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("ipa_y_h", 6 * sizeof(Fr)));
+  QG_HIP(hipMemsetAsync(d_y, 0, 6 * sizeof(Fr), ctx->stream));
+  for (int i = 0; i < 6; i++)
+    if (s[i])
+      QG_HIP(hipMemcpyAsync(d_y + i, s[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+  QG_HIP(hipMemcpyAsync(h_y, d_y, 6 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+  // every quotient through kzg.rs:85's check, as two groups of open_check_queue:
+  // (f, g) at r and 1/r, then S at r and 1/r
+  const bool check = open_check_on();
+  std::vector<uint8_t> checked(6, CK_NONE);
+  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("ipa_ck_h", 8 * sizeof(uint32_t)));
+  if (check) {
+    uint32_t* d_w = ctx->scratch_as<uint32_t>("ipa_ck_w", 8);
+    OpenCk c8[8] = {};
+    for (int i = 0; i < 6; i++) {
+      const size_t n = ns[i >> 1];
+      c8[i] = {n ? polys[i >> 1] : nullptr, n, s[i] ? s[i] + 1 : nullptr,
+               s[i] ? lts[i >> 1] - 1 : 0, d_y + i, xs[i & 1]};
+      checked[i] = s[i] ? CK_QUOT : n ? CK_ZERO : CK_NONE;
+    }
+    open_check_queue(ctx, c8, d_w);
+    open_check_queue(ctx, c8 + 4, d_w + 4);
+    QG_HIP(hipMemcpyAsync(h_w, d_w, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  std::vector<const Fr*> qs;
+  std::vector<size_t> qns;
+  for (int i = 0; i < 6; i++) {
+    qs.push_back(s[i] ? s[i] + 1 : nullptr);
+    qns.push_back(s[i] ? lts[i >> 1] - 1 : 0);
+  }
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
+  ctx->sync();  // (drained already unless every quotient was empty)
+  if (check) open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + 6), checked, 6, IPA_QNAME);
+  Fr y[6];
+  for (int i = 0; i < 6; i++) {
+    y[i] = h_y[i];
+    fr_export(y[i], outs[i]->y);
+    g1_export(pis[i], outs[i]->proof_xy, &outs[i]->proof_inf);
+  }
+  // ipa.rs:94-100
+  QG_CHECK(y[0] * y[3] + y[1] * y[2] == r * y[4] + r_inv * y[5] + from_u64<FrP>(2) * ip,
+           QG_ERR_ASSERT, "Inner product verification equation failed");
+}
+
 }  // namespace qg
 
 extern "C" {
@@ -2570,6 +2880,42 @@ int qg_mle_open_dev_ex(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_
     OpenCall call(ctx);
     mle_open_device(ctx, srs, poly->d, n, point, nvars, state, out,
                     (flags & QG_OPEN_UNCHANGED) != 0, poly->alloc_id, poly->base_off);
+  });
+}
+
+// a general sharded g has no S polynomial here (s_poly_sharded builds its g
+// operand from the eq-table product formula only); checked before OpenCall,
+// whose constructor is collective on a sharded context
+static void ipa_entry_checks(qg_ctx* ctx, size_t nf, size_t ng) {
+  QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
+           "the inner-product argument is not supported on a sharded context (communicator "
+           "attached)");
+  QG_CHECK(nf || ng, QG_ERR_INVALID, "inner-product argument of two empty polynomials");
+}
+
+int qg_ipa_prove(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf, const uint64_t* g,
+                 size_t ng, uint8_t state[32], qg_ipa_proof* out) {
+  if (!ctx || !srs || (!f && nf) || (!g && ng) || !state || !out) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    ipa_entry_checks(ctx, nf, ng);
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    Fr* df = ctx->scratch_as<Fr>("ipa_f", nf ? nf : 1);
+    Fr* dg = ctx->scratch_as<Fr>("ipa_g", ng ? ng : 1);
+    fr_upload(ctx, df, f, nf);
+    fr_upload(ctx, dg, g, ng);
+    ipa_prove_device(ctx, srs, df, nf, dg, ng, state, out);
+  });
+}
+
+int qg_ipa_prove_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf, const qg_buf* g,
+                     size_t ng, uint8_t state[32], qg_ipa_proof* out) {
+  if (!ctx || !srs || !f || !g || nf > f->n || ng > g->n || !state || !out) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    ipa_entry_checks(ctx, nf, ng);
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    ipa_prove_device(ctx, srs, f->d, nf, g->d, ng, state, out);
   });
 }
 

@@ -481,4 +481,44 @@ int qg_mle_verify(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_i
   }
 }
 
+int qg_ipa_verify(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                  const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
+                  uint8_t state[32], int* ok) {
+  if (!vk || !comm1_xy || !comm2_xy || !proof || !state || !ok) return QG_ERR_INVALID;
+  try {
+    const Vk v = vk_in(vk);
+    const G1Affine comm1 = g1_in(comm1_xy, comm1_inf), comm2 = g1_in(comm2_xy, comm2_inf);
+    const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
+    // the six openings first (ipa.rs:179-188): a failure returns before the
+    // transcript is touched
+    *ok = 0;
+    if (!kzg_verify_abi(v, comm1, proof->f_opening) ||
+        !kzg_verify_abi(v, comm1, proof->f_opening_inv) ||
+        !kzg_verify_abi(v, comm2, proof->g_opening) ||
+        !kzg_verify_abi(v, comm2, proof->g_opening_inv) ||
+        !kzg_verify_abi(v, s_comm, proof->s_opening) ||
+        !kzg_verify_abi(v, s_comm, proof->s_opening_inv))
+      return QG_OK;
+    // inner_product, s_comm; draw r (ipa.rs:191-195)
+    uint8_t b32[32], b64[64];
+    const Fr ip = fr_import(proof->inner_product);
+    fr_to_bytes(ip, b32);
+    transcript_append(state, b32, 32);
+    g1_serialize(s_comm, b64);
+    transcript_append(state, b64, 64);
+    const Fr r = transcript_draw_fr(state);
+    QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+    const Fr r_inv = finv(r);
+    // ipa.rs:198-201; like the reference, the openings' own x are not compared with r
+    const Fr lhs = fr_import(proof->f_opening.y) * fr_import(proof->g_opening_inv.y) +
+                   fr_import(proof->f_opening_inv.y) * fr_import(proof->g_opening.y);
+    const Fr rhs = r * fr_import(proof->s_opening.y) + r_inv * fr_import(proof->s_opening_inv.y) +
+                   from_u64<FrP>(2) * ip;
+    *ok = lhs == rhs ? 1 : 0;
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
 }  // extern "C"

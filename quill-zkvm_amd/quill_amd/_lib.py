@@ -40,6 +40,14 @@ class MleProof(C.Structure):
                 ("s_opening", KzgOpening), ("s_opening_inv", KzgOpening)]
 
 
+class IpaProof(C.Structure):
+    _fields_ = [("inner_product", C.c_uint64 * 4), ("s_comm_xy", C.c_uint64 * 8),
+                ("s_comm_inf", C.c_uint8), ("_pad", C.c_uint8 * 7),
+                ("f_opening", KzgOpening), ("f_opening_inv", KzgOpening),
+                ("g_opening", KzgOpening), ("g_opening_inv", KzgOpening),
+                ("s_opening", KzgOpening), ("s_opening_inv", KzgOpening)]
+
+
 class MleOpenItem(C.Structure):
     _fields_ = [("poly", C.c_void_p), ("n", C.c_size_t), ("point", C.POINTER(C.c_uint64)),
                 ("nvars", C.c_size_t), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
@@ -126,6 +134,10 @@ PROTOTYPES = {
                                      C.POINTER(MleProof)]),
     "qg_mle_open_batch_dev": (C.c_int, [P, P, C.POINTER(MleOpenItem), SZ, U8P,
                                         C.POINTER(MleProof)]),
+    "qg_ipa_prove": (C.c_int, [P, P, U64P, SZ, U64P, SZ, U8P, C.POINTER(IpaProof)]),
+    "qg_ipa_prove_dev": (C.c_int, [P, P, P, SZ, P, SZ, U8P, C.POINTER(IpaProof)]),
+    "qg_ipa_verify": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,
+                                C.POINTER(IpaProof), U8P, C.POINTER(C.c_int)]),
     "qg_eq_table": (C.c_int, [P, U64P, SZ, U64P]),
     "qg_eq_table_dev": (C.c_int, [P, U64P, SZ, P]),
     "qg_s_polynomial": (C.c_int, [P, U64P, SZ, U64P, SZ, U64P]),

@@ -10,7 +10,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import KzgOpening, KzgVk, MleOpenItem, MleProof, QuillGpuError, check, lib
+from ._lib import (IpaProof, KzgOpening, KzgVk, MleOpenItem, MleProof, QuillGpuError, check,
+                   lib)
 from .device import Device, DeviceVec, Srs
 from .field import (fq_from_mont_limbs, fr_array, fr_c, fr_from_mont_limbs, g1_from_abi,
                     g1_to_abi, g2_from_abi, g2_to_abi, u64p)
@@ -109,6 +110,72 @@ class MLEvalProof:
 
     def evaluation_claim(self):
         return EvaluationClaim(self.point(), self.evaluation)
+
+
+def _ipa_proof_c(p: "InnerProductProof") -> IpaProof:
+    c = IpaProof()
+    C.memmove(c.inner_product, fr_c(p.inner_product), 32)
+    xy, inf = g1_to_abi(p.s_comm)
+    C.memmove(c.s_comm_xy, xy, 64)
+    c.s_comm_inf = inf
+    for name in _IPA_OPENINGS:
+        setattr(c, name, _opening_c(getattr(p, name)))
+    return c
+
+
+_IPA_OPENINGS = ("f_opening", "f_opening_inv", "g_opening", "g_opening_inv", "s_opening",
+                 "s_opening_inv")
+
+
+@dataclass
+class InnerProductProof:
+    """pcs/src/ipa.rs:40-53: <f, g> over the common prefix of two committed
+    coefficient vectors, by the S polynomial and six KZG openings at r, 1/r"""
+    inner_product: int
+    s_comm: object
+    f_opening: KZGOpeningProof
+    f_opening_inv: KZGOpeningProof
+    g_opening: KZGOpeningProof
+    g_opening_inv: KZGOpeningProof
+    s_opening: KZGOpeningProof
+    s_opening_inv: KZGOpeningProof
+
+    @classmethod
+    def prove(cls, poly1, poly2, kzg: "KZG", transcript: Transcript) -> "InnerProductProof":
+        """ipa.rs:59-112 (qg_ipa_prove; qg_ipa_prove_dev when both operands are
+        DeviceVecs).  Like the reference, the commitments to poly1 and poly2
+        are the caller's to absorb into the transcript beforehand."""
+        out = IpaProof()
+        dev = kzg.dev
+        if isinstance(poly1, DeviceVec) and isinstance(poly2, DeviceVec):
+            rc = lib().qg_ipa_prove_dev(dev.h, kzg.srs_for(max(len(poly1), len(poly2))).h,
+                                        poly1.h, len(poly1), poly2.h, len(poly2),
+                                        transcript.c_state(), C.byref(out))
+        else:
+            if isinstance(poly1, DeviceVec) or isinstance(poly2, DeviceVec):
+                raise QuillGpuError(-1, "InnerProductProof.prove: both operands on the device, "
+                                        "or both on the host")
+            a = fr_array(poly1) if len(poly1) else np.zeros((1, 4), dtype=np.uint64)
+            b = fr_array(poly2) if len(poly2) else np.zeros((1, 4), dtype=np.uint64)
+            rc = lib().qg_ipa_prove(dev.h, kzg.srs_for(max(len(poly1), len(poly2))).h, u64p(a),
+                                    len(poly1), u64p(b), len(poly2), transcript.c_state(),
+                                    C.byref(out))
+        check(rc, dev.h)
+        return cls(fr_from_mont_limbs(list(out.inner_product)),
+                   g1_from_abi(out.s_comm_xy, out.s_comm_inf),
+                   *[_opening(getattr(out, name)) for name in _IPA_OPENINGS])
+
+    def verify(self, comm1, comm2, kzg: "KZG", transcript: Transcript) -> bool:
+        """ipa.rs:160-202 (host pairing checks, qg_ipa_verify): the six KZG
+        checks first - a failure leaves the transcript untouched -, then the
+        transcript replay and the equation at r"""
+        xy1, inf1 = g1_to_abi(comm1)
+        xy2, inf2 = g1_to_abi(comm2)
+        ok = C.c_int()
+        check(lib().qg_ipa_verify(C.byref(kzg._vk()), xy1, inf1, xy2, inf2,
+                                  C.byref(_ipa_proof_c(self)), transcript.c_state(),
+                                  C.byref(ok)))
+        return bool(ok.value)
 
 
 class KZG:

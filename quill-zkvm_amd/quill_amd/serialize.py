@@ -15,6 +15,12 @@ Structs (field order of the reference):
   KZGOpeningProof        x, y, proof                      (kzg.rs:25-32)
   MLEvalProof            evaluation_point, evaluation, s_comm, poly_opening,
                          poly_opening_inv, s_opening, s_opening_inv (mlpcs.rs:32-44)
+  InnerProductProof      inner_product, s_comm, f_opening, f_opening_inv,
+                         g_opening, g_opening_inv, s_opening, s_opening_inv
+                         (ipa.rs:40-53; the reference derives no
+                         CanonicalSerialize for this type, so nothing outside
+                         this module pins its format: it is the convention
+                         above applied to the struct's declaration order)
   SumcheckProof          num_vars, claimed_sum, r_polys   (sumcheck.rs:15-19)
   ZeroCheckProof         num_vars, sumcheck_proof         (zerocheck.rs:8-11)
   MultisetEqualityProof  denom_left_commitment, denom_right_commitment,
@@ -36,7 +42,7 @@ import struct
 from .field import P_MOD, R_MOD
 from .hyperplonk import SumcheckProof, ZeroCheckProof
 from .logup import MultisetEqualityProof, PermutationCheckProof
-from .pcs import KZGOpeningProof, MLEvalProof
+from .pcs import InnerProductProof, KZGOpeningProof, MLEvalProof
 from .proof import HyperPlonkProof, TraceProof
 
 _INF, _NEG = 0x40, 0x80
@@ -79,6 +85,13 @@ def _mle(p: MLEvalProof) -> bytes:
             + _kzg_opening(p.s_opening) + _kzg_opening(p.s_opening_inv))
 
 
+def _ipa(p: InnerProductProof) -> bytes:
+    return (_fr(p.inner_product) + _g1(p.s_comm)
+            + _kzg_opening(p.f_opening) + _kzg_opening(p.f_opening_inv)
+            + _kzg_opening(p.g_opening) + _kzg_opening(p.g_opening_inv)
+            + _kzg_opening(p.s_opening) + _kzg_opening(p.s_opening_inv))
+
+
 def _sumcheck(p: SumcheckProof) -> bytes:
     return _u64(p.num_vars) + _fr(p.claimed_sum) + _vec(list(p.r_polys), _poly)
 
@@ -105,6 +118,7 @@ def _hyperplonk(p: HyperPlonkProof) -> bytes:
 
 
 _ENCODERS = [(HyperPlonkProof, _hyperplonk), (TraceProof, _trace), (MLEvalProof, _mle),
+             (InnerProductProof, _ipa),
              (SumcheckProof, _sumcheck), (ZeroCheckProof, _zerocheck),
              (MultisetEqualityProof, _multiset),
              (PermutationCheckProof, lambda p: _multiset(p.multiset_equality_proof)),
@@ -172,6 +186,10 @@ class _Reader:
         return MLEvalProof(pt, ev, s, self.kzg_opening(), self.kzg_opening(),
                            self.kzg_opening(), self.kzg_opening())
 
+    def ipa(self):
+        ip, s = self.fr(), self.g1()
+        return InnerProductProof(ip, s, *[self.kzg_opening() for _ in range(6)])
+
     def sumcheck(self):
         nv, cs = self.u64(), self.fr()
         return SumcheckProof(nv, cs, self.vec(lambda: self.vec(self.fr)))
@@ -197,6 +215,7 @@ class _Reader:
 
 
 _DECODERS = {HyperPlonkProof: "hyperplonk", TraceProof: "trace", MLEvalProof: "mle",
+             InnerProductProof: "ipa",
              SumcheckProof: "sumcheck", ZeroCheckProof: "zerocheck",
              MultisetEqualityProof: "multiset", KZGOpeningProof: "kzg_opening"}
 
