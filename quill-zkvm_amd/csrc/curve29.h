@@ -149,6 +149,99 @@ QG_HD void x29_acc_madd_exc(X29& p, const Q29& ax, const Q29& ay, bool* inf) {
   }
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// dst = src in dst's own register: the tied operand keeps a value that only
+// some lanes replace (a run start, a doubling) in the loop-carried register,
+// where a plain assignment lets the register coalescer pick the source's
+// register and copy every limb back for all lanes
+__device__ __forceinline__ void mov29_ip(uint32_t& dst, uint32_t src) {
+  asm("v_mov_b32 %0, %1" : "+v"(dst) : "v"(src));
+}
+__device__ __forceinline__ void mov29_ip_s(uint32_t& dst, uint32_t src) {  // wave-uniform source
+  asm("v_mov_b32 %0, %1" : "+v"(dst) : "s"(src));
+}
+
+// No instruction: from here on p is a new value in the same registers.  Placed
+// behind a block that only some lanes ran, it makes the code below read p as
+// merged there; reading the value from before the block instead keeps that
+// one and the merged one live side by side, in two sets of registers.
+__device__ __forceinline__ void x29_pin(X29& p) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    asm("" : "+v"(p.X.l[i]));
+    asm("" : "+v"(p.Y.l[i]));
+    asm("" : "+v"(p.ZZ.l[i]));
+    asm("" : "+v"(p.ZZZ.l[i]));
+  }
+}
+
+// a run of a bucket starts: p = (x, y, 1, 1), written by the starting lanes only
+__device__ __forceinline__ void x29_acc_start_ip(X29& p, const Q29& ax, const Q29& ay) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    mov29_ip(p.X.l[i], ax.l[i]);
+    mov29_ip(p.Y.l[i], ay.l[i]);
+    mov29_ip_s(p.ZZ.l[i], F29P<FqP>::ONE.v[i]);
+    mov29_ip_s(p.ZZZ.l[i], F29P<FqP>::ONE.v[i]);
+  }
+}
+
+// p = infinity (x29_inf) in p's own registers, for the lanes whose run ended
+// cancelled: the flush then stores p as it stands, with no select per limb
+__device__ __forceinline__ void x29_acc_inf_ip(X29& p) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    mov29_ip_s(p.X.l[i], 0u);
+    mov29_ip_s(p.Y.l[i], F29P<FqP>::ONE.v[i]);
+    mov29_ip_s(p.ZZ.l[i], 0u);
+    mov29_ip_s(p.ZZZ.l[i], 0u);
+  }
+}
+
+// x29_acc_madd_tp with its exceptional cases, the sum landing in p's own
+// registers.  The exceptional lanes (P == 0 mod p) go FIRST: they read the old
+// Y against S2 (R == 0: p = 2a, else *inf) and leave the addition, so past
+// the zero test no path reads the old accumulator but the addition itself;
+// with the exceptional block behind the addition the old limbs stayed live
+// across it for those lanes, and the sum was built elsewhere and copied in.
+// Same values as x29_acc_madd_tp + x29_acc_madd_exc limb for limb (normfull29
+// of norm29(v) is normfull29(v): the normalized form of an integer is unique).
+__device__ __forceinline__ void x29_acc_madd_ip(X29& p, const Q29& ax, const Q29& ay, bool& inf) {
+  Q29 U2, S2;
+  mul29t2(ax, p.ZZ, ay, p.ZZZ, U2, S2);
+  const Q29 P = normfull29(subk29(U2, p.X, F29P<FqP>::K17));
+  const Q29 R = norm29(subk29(S2, p.Y, F29P<FqP>::K9));
+  bool add = true;
+  if (is_zero_mod29_fast<FqP, 20>(P)) {
+    add = false;
+    if (is_zero_mod29_fast<FqP, 20>(normfull29(R))) {
+      A29 a;
+      a.x = ax;
+      a.y = ay;  // canonical
+      const X29 d = x29_dbl_affine(a);
+#pragma unroll
+      for (int i = 0; i < 9; i++) {
+        mov29_ip(p.X.l[i], d.X.l[i]);
+        mov29_ip(p.Y.l[i], d.Y.l[i]);
+        mov29_ip(p.ZZ.l[i], d.ZZ.l[i]);
+        mov29_ip(p.ZZZ.l[i], d.ZZZ.l[i]);
+      }
+    } else {
+      inf = true;
+    }
+  }
+  x29_pin(p);
+  if (add) {
+    Q29 PP, RR, PPP, Q;
+    sqr29t2(P, R, PP, RR);
+    mul29t2(P, PP, p.X, PP, PPP, Q);
+    p.X = norm29(sub29(sub29(sub29(RR, PPP), Q), Q));
+    p.Y = mulsub29t(R, norm29(subk29(Q, p.X, F29P<FqP>::K17)), p.Y, PPP);
+    mul29t2(p.ZZ, PP, p.ZZZ, PPP, p.ZZ, p.ZZZ);
+  }
+}
+#endif
+
 // ---- MSM table rows (curve.h MsmPt) ----------------------------------------
 // pack a canonical point (x, y < p, 29-bit limbs, R = 2^261) or infinity
 QG_HD MsmPt msm_pt_pack(const Q29& x, const Q29& y, bool inf) {

@@ -381,7 +381,9 @@ __device__ __forceinline__ F29<C> sqr29t(const F29<C>& a) {
 // no v_mad_u64_u32 result is read by the next instruction, so the hazard
 // s_nop gfx950 places after every dependent mad of a single chain goes away
 // (micro/pair_bench.hip: +2.5 % multiplies/s at full occupancy).  Same
-// arithmetic and operand conditions as mul29t / sqr29t.
+// arithmetic and operand conditions as mul29t / sqr29t.  r1 may be a and r2
+// may be c (curve29.h x29_acc_madd_ip): limb i of a result is written in
+// column i + 9, after the last read of the operands' limb i in column i + 8.
 template <class C>
 __device__ __forceinline__ void mul29t2(const F29<C>& a, const F29<C>& b, const F29<C>& c,
                                         const F29<C>& d, F29<C>& r1, F29<C>& r2) {

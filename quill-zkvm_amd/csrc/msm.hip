@@ -802,9 +802,15 @@ __device__ __forceinline__ void msm_coop_issue(uint4* wbuf, const MsmPt* __restr
   uint32_t r[8];
 #pragma unroll
   for (int k = 0; k < 8; k++) r[k] = (uint32_t)__shfl((int)(ent & 0x7fffffffu), 8 * k + (int)(lane >> 3), 64);
+  // row address = the lane's word column + 128 * row in ONE 64-bit mad (the
+  // multiplier opaque, or it becomes a 64-bit shift, an add and a zeroed
+  // high half per row)
+  uint32_t rowb = (uint32_t)sizeof(MsmPt);
+  asm("" : "+s"(rowb));
+  const uint64_t col = (uint64_t)(reinterpret_cast<const uint4*>(table) + word);
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    const uint4* g = reinterpret_cast<const uint4*>(table + r[k]) + word;
+    const uint64_t g = (uint64_t)r[k] * rowb + col;
     __builtin_amdgcn_global_load_lds((msm_glb_ptr)g, (msm_lds_ptr)(wbuf + 64 * k), 16, 0, 0);
   }
 }
@@ -839,7 +845,9 @@ __global__ void __launch_bounds__(MSM_BLOCK) __attribute__((amdgpu_waves_per_eu(
   __shared__ uint4 img[MSM_BLOCK / 64][64 * 8];
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
-  uint4* wbuf = img[threadIdx.x >> 6];
+  // the wave's image by a scalar index: the DMA's LDS base (M0) is then set
+  // from an SGPR, not read out of a VGPR before every instruction
+  uint4* wbuf = img[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
   const uint32_t total = bstart[nb];
   const uint64_t e0w = (uint64_t)t * L;
   // whole waves stay or leave together (the DMA steps are wave-wide); lanes
@@ -858,7 +866,7 @@ __global__ void __launch_bounds__(MSM_BLOCK) __attribute__((amdgpu_waves_per_eu(
     b = lo;
     next = bstart[b + 1];
   }
-  X29 acc;
+  X29 acc = x29_inf();
   bool inf = true;
   uint4 g0 = msm_entries4(entries, e0, e1);
   uint4 g1 = e0 + 4 < e1 ? msm_entries4(entries, e0 + 4, e1) : g0;
@@ -866,8 +874,9 @@ __global__ void __launch_bounds__(MSM_BLOCK) __attribute__((amdgpu_waves_per_eu(
   for (uint32_t i = 0; i < L; i++) {  // wave-uniform trip count
     const uint32_t e = e0 + i;
     const uint32_t k = i & 3u;
-    const uint32_t ent = k == 0 ? g0.x : k == 1 ? g0.y : k == 2 ? g0.z : g0.w;
-    const uint32_t en = k == 0 ? g0.y : k == 1 ? g0.z : k == 2 ? g0.w : g1.x;
+    // the group's entries move up one place per step (g0.x: this step's entry,
+    // then the next step's); picking them by k cost six selects per step
+    const uint32_t ent = g0.x;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this step's rows have landed
     Q29 ax, ay;
     const bool pinf = msm_coop_read(wbuf, lane, (ent >> 31) != 0u, ax, ay);
@@ -875,11 +884,20 @@ __global__ void __launch_bounds__(MSM_BLOCK) __attribute__((amdgpu_waves_per_eu(
     if (k == 3) {
       g0 = g1;
       if (e + 5 < e1) g1 = msm_entries4(entries, e + 5, e1);
+    } else {
+      g0.x = g0.y;
+      g0.y = g0.z;
+      g0.z = g0.w;
     }
+    const uint32_t en = g0.x;
     if (i + 1 < L) msm_coop_issue(wbuf, table, lane, e + 1 < e1 ? en : 0u);
     if (e >= e1) continue;
     if (e == next) {
-      msm_flush(partial, owner, msm_chunk_of(e1 - 1, Lm) + b, b, acc, inf);
+      // a run that ended at infinity (cancelled, or infinity bases only) is
+      // rare: those lanes write x29_inf() into acc, dead after the flush
+      if (inf) x29_acc_inf_ip(acc);
+      x29_pin(acc);
+      msm_flush(partial, owner, msm_chunk_of(e1 - 1, Lm) + b, b, acc, false);
       inf = true;
       do {
         b++;
@@ -887,15 +905,19 @@ __global__ void __launch_bounds__(MSM_BLOCK) __attribute__((amdgpu_waves_per_eu(
       } while (next <= e);
     }
     if (pinf) continue;
+    // the accumulator stays in its loop-carried registers on every path
+    // (curve29.h x29_acc_start_ip / x29_acc_madd_ip): no limb is copied.
+    // The run start comes first and is no else-branch of the addition: a
+    // block laid out behind the addition that reads the old accumulator keeps
+    // every old limb live across it.
+    uint32_t add = inf ? 0u : 1u;
+    asm("" : "+v"(add));  // opaque: or the two branches are threaded back into if / else
     if (inf) {
-      acc.X = ax;
-      acc.Y = ay;
-      acc.ZZ = Q29::from_l9(F29P<FqP>::ONE);
-      acc.ZZZ = acc.ZZ;
+      x29_acc_start_ip(acc, ax, ay);
       inf = false;
-      continue;
     }
-    if (!x29_acc_madd_tp(acc, ax, ay)) x29_acc_madd_exc(acc, ax, ay, &inf);
+    x29_pin(acc);
+    if (add) x29_acc_madd_ip(acc, ax, ay, inf);
   }
   if (e0 < e1) msm_flush(partial, owner, msm_chunk_of(e1 - 1, Lm) + b, b, acc, inf);
 #endif
