@@ -108,15 +108,16 @@ QG_DEV uint32_t xcd_tile(uint32_t b, uint32_t G) {
 // ---- bucketing: two-pass LDS-histogram radix sort ------------------------
 // Bucket id b (BB = c-1 bits) = (g << LO) | l.  Pass A partitions digits by the
 // high part g with per-block LDS histograms (no per-digit global atomics);
-// pass B sorts every group by l in chunks of SORT_CHUNK entries, so a heavy
+// pass B sorts every group by l in chunks of CHUNK entries, so a heavy
 // group (skewed scalars, the short top window) spreads over many blocks.
-static constexpr int SORT_BLOCK = 256;
+// The block width of the pass-A scatter / rows kernels (BLK) and the block
+// width and chunk of the pass-B kernels (BLK, CHUNK) are template parameters;
+// msm_accumulate_phase picks an instantiation (sort_geometry below).
+static constexpr int SORT_BLOCK = 256;                      // k_sortA_hist, and the narrowest BLK
 static constexpr int SORT_TILE_MAX = 1024;                  // scalars per block (pass A)
 static constexpr size_t SORT_LDS_A = 72 * 1024;             // LDS budget for staged entries (2 blocks/CU)
-#ifndef QG_SORT_CHUNK
-#define QG_SORT_CHUNK 8192
-#endif
-static constexpr int SORT_CHUNK = QG_SORT_CHUNK;            // entries per block (pass B)
+static constexpr int SORT_CHUNK = 8192;                     // entries per block (pass B), 256-thread blocks
+static constexpr int SORT_H_MAX = 1024, SORT_NL_MAX = 4096; // most groups / buckets per group
 
 // ---- cross-stream hand-over guard (msm_device_batch) ----------------------
 // A batch on the side streams hands data over by events only: the scalars
@@ -163,7 +164,6 @@ __global__ void __launch_bounds__(SORT_BLOCK)
   const uint32_t tb = xcd_tile(blockIdx.x, nblk);
   const size_t base = (size_t)tb * tile;
   const size_t end = base + tile < n ? base + tile : n;
-  static_assert(SORT_TILE_MAX % SORT_BLOCK == 0, "pass-A tile must split evenly over the block");
   for (size_t i = base + threadIdx.x; i < end; i += blockDim.x) {
     Fr s;
     if (canon_ready) {
@@ -195,12 +195,13 @@ __global__ void __launch_bounds__(256)
     if (c0 + k < cols && r0 + tx < rows) out[(size_t)(c0 + k) * rows + r0 + tx] = tile[tx][k];
 }
 
-// Block-local exclusive scan of n <= 4 * SORT_BLOCK counts in LDS (in place).
-// Each thread owns `per` consecutive counts; the thread totals are scanned
-// within the wave by shuffles, the 4 wave totals through LDS: two barriers
-// (a Hillis-Steele scan over the block took 2 x 8).
-__device__ void lds_exscan(uint32_t* a, int n, uint32_t* tmp /* >= SORT_BLOCK / 64 words */) {
-  const int per = (n + SORT_BLOCK - 1) / SORT_BLOCK;
+// Block-local exclusive scan of n counts in LDS (in place) by a block of BLK
+// threads.  Each thread owns `per` consecutive counts; the thread totals are
+// scanned within the wave by shuffles, the BLK / 64 wave totals through LDS:
+// two barriers (a Hillis-Steele scan over the block took 2 x 8).
+template <int BLK>
+__device__ void lds_exscan(uint32_t* a, int n, uint32_t* tmp /* >= BLK / 64 words */) {
+  const int per = (n + BLK - 1) / BLK;
   const int b = threadIdx.x * per;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   uint32_t tot = 0;
@@ -244,7 +245,8 @@ __device__ __forceinline__ int lds_upper(const uint32_t* off, int n, uint32_t p)
 // Output per digit: the table entry (u32) and the bucket's low LO bits (u16).
 // wsel >= 0: only window wsel's digits, entry = the base's row in the one
 // table of one-shot bases (no window offset)
-__global__ void __launch_bounds__(SORT_BLOCK)
+template <int BLK>
+__global__ void __launch_bounds__(BLK)
     k_sortA_scatter(const Fr* __restrict__ canon, size_t n, size_t N, size_t off, int c, int W, int LO,
                     int H,
                     uint32_t nblk, uint32_t tile, const uint32_t* __restrict__ hrow,
@@ -263,11 +265,12 @@ __global__ void __launch_bounds__(SORT_BLOCK)
   const size_t end = base + tile < n ? base + tile : n;
   // the thread's scalars (tile <= SORT_TILE_MAX) are loaded first: their round
   // trip overlaps the row loads below
-  constexpr int PER = SORT_TILE_MAX / SORT_BLOCK;
+  static_assert(SORT_TILE_MAX % BLK == 0, "pass-A tile must split evenly over the block");
+  constexpr int PER = SORT_TILE_MAX / BLK;
   Fr sv[PER];
 #pragma unroll
   for (int j = 0; j < PER; j++) {
-    const size_t i = base + threadIdx.x + (size_t)j * SORT_BLOCK;
+    const size_t i = base + threadIdx.x + (size_t)j * BLK;
     if (i < end) sv[j] = canon[i];
   }
   // rows prepared by k_sortA_rows: the tile's local run starts and global bases
@@ -279,7 +282,7 @@ __global__ void __launch_bounds__(SORT_BLOCK)
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < PER; j++) {
-    const size_t i = base + threadIdx.x + (size_t)j * SORT_BLOCK;
+    const size_t i = base + threadIdx.x + (size_t)j * BLK;
     if (i >= end) break;
     for_each_digit(sv[j], c, W, [&](int w, uint32_t b, bool neg) {
       if (wsel >= 0 && w != wsel) return;
@@ -304,13 +307,14 @@ __global__ void __launch_bounds__(SORT_BLOCK)
 // per tile row (one block each): hrow <- exclusive scan of the tile's group
 // counts (its local run starts), orow <- global offset - local start (the base
 // that the scatter adds to an LDS position)
-__global__ void __launch_bounds__(SORT_BLOCK)
+template <int BLK>
+__global__ void __launch_bounds__(BLK)
     k_sortA_rows(uint32_t* __restrict__ hrow, uint32_t* __restrict__ orow, int H) {
-  __shared__ uint32_t a[4 * SORT_BLOCK], scr[SORT_BLOCK];
+  __shared__ uint32_t a[SORT_H_MAX], scr[BLK / 64];
   const size_t r = (size_t)blockIdx.x * H;
   for (int g = threadIdx.x; g < H; g += blockDim.x) a[g] = hrow[r + g];
   __syncthreads();
-  lds_exscan(a, H, scr);
+  lds_exscan<BLK>(a, H, scr);
   for (int g = threadIdx.x; g < H; g += blockDim.x) {
     hrow[r + g] = a[g];
     orow[r + g] -= a[g];
@@ -322,7 +326,7 @@ __global__ void __launch_bounds__(SORT_BLOCK)
 // here (no fill launches): [1] max threads per bucket = 0, [2..3] skewed slot
 // range = empty
 __global__ void __launch_bounds__(1024)
-    k_sort_chunks(const uint32_t* __restrict__ goff, uint32_t nblk, int H,
+    k_sort_chunks(const uint32_t* __restrict__ goff, uint32_t nblk, int H, uint32_t chunk,
                   uint32_t* __restrict__ gstart, uint32_t* __restrict__ cbase,
                   uint32_t* __restrict__ chunk_group, uint32_t* __restrict__ misc) {
   __shared__ uint32_t sh[1024];
@@ -333,7 +337,7 @@ __global__ void __launch_bounds__(1024)
   if (g < H) {
     gs = goff[(size_t)g * nblk];
     ge = (g + 1 < H) ? goff[(size_t)(g + 1) * nblk] : total;
-    nch = (ge - gs + SORT_CHUNK - 1) / SORT_CHUNK;
+    nch = (ge - gs + chunk - 1) / chunk;
     gstart[g] = gs;
   }
   sh[threadIdx.x] = nch;
@@ -356,7 +360,8 @@ __global__ void __launch_bounds__(1024)
   }
 }
 
-__global__ void __launch_bounds__(SORT_BLOCK)
+template <int BLK, int CHUNK>
+__global__ void __launch_bounds__(BLK)
     k_sortB_hist(const uint16_t* __restrict__ tmp_l, const uint32_t* __restrict__ gstart,
                  const uint32_t* __restrict__ cbase, const uint32_t* __restrict__ chunk_group,
                  const uint32_t* __restrict__ nchunks, int NL, uint32_t* __restrict__ chist) {
@@ -365,15 +370,15 @@ __global__ void __launch_bounds__(SORT_BLOCK)
   if (blockIdx.x >= nch) return;
   const uint32_t k = xcd_tile(blockIdx.x, nch);
   const uint32_t g = chunk_group[k];
-  const uint32_t s = gstart[g] + (k - cbase[g]) * SORT_CHUNK;
-  const uint32_t e = min(s + SORT_CHUNK, gstart[g + 1]);
+  const uint32_t s = gstart[g] + (k - cbase[g]) * CHUNK;
+  const uint32_t e = min(s + CHUNK, gstart[g + 1]);
   for (int l = threadIdx.x; l < NL; l += blockDim.x) hist[l] = 0;
   __syncthreads();
-  constexpr int PER = SORT_CHUNK / SORT_BLOCK;
+  constexpr int PER = CHUNK / BLK;
   uint32_t lv[PER];
 #pragma unroll
   for (int j = 0; j < PER; j++) {
-    const uint32_t p = s + threadIdx.x + j * SORT_BLOCK;
+    const uint32_t p = s + threadIdx.x + j * BLK;
     lv[j] = p < e ? (uint32_t)tmp_l[p] : 0xffffffffu;
   }
 #pragma unroll
@@ -413,8 +418,8 @@ __global__ void k_sort_chunk_offsets(const uint32_t* __restrict__ cbase,
 
 // Pass B scatter: the chunk is counting-sorted by the low bucket bits in LDS,
 // then each bucket run is written contiguously at its chunk offset.
-static_assert(SORT_CHUNK % SORT_BLOCK == 0, "pass-B chunk must split evenly over the block");
-__global__ void __launch_bounds__(SORT_BLOCK)
+template <int BLK, int CHUNK>
+__global__ void __launch_bounds__(BLK)
     k_sortB_scatter(const uint32_t* __restrict__ tmp_e, const uint16_t* __restrict__ tmp_l,
                     const uint32_t* __restrict__ gstart,
                     const uint32_t* __restrict__ cbase, const uint32_t* __restrict__ chunk_group,
@@ -422,8 +427,9 @@ __global__ void __launch_bounds__(SORT_BLOCK)
                     const uint32_t* __restrict__ coff, uint32_t* __restrict__ entries) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* e32 = reinterpret_cast<uint32_t*>(smem);
-  uint16_t* bins = reinterpret_cast<uint16_t*>(e32 + SORT_CHUNK);
-  uint32_t* loff = reinterpret_cast<uint32_t*>(bins + SORT_CHUNK);
+  static_assert(CHUNK % BLK == 0, "pass-B chunk must split evenly over the block");
+  uint16_t* bins = reinterpret_cast<uint16_t*>(e32 + CHUNK);
+  uint32_t* loff = reinterpret_cast<uint32_t*>(bins + CHUNK);
   uint32_t* cur = loff + NL;
   uint32_t* cb = cur + NL;
   uint32_t* scr = cb + NL;
@@ -431,15 +437,15 @@ __global__ void __launch_bounds__(SORT_BLOCK)
   if (blockIdx.x >= nch) return;
   const uint32_t k = xcd_tile(blockIdx.x, nch);
   const uint32_t g = chunk_group[k];
-  const uint32_t s = gstart[g] + (k - cbase[g]) * SORT_CHUNK;
-  const uint32_t e = min(s + SORT_CHUNK, gstart[g + 1]);
+  const uint32_t s = gstart[g] + (k - cbase[g]) * CHUNK;
+  const uint32_t e = min(s + CHUNK, gstart[g + 1]);
   // all of the thread's entries are loaded first: their round trip overlaps
   // the histogram row, its scan and the offset row instead of following them
-  constexpr int PER = SORT_CHUNK / SORT_BLOCK;
+  constexpr int PER = CHUNK / BLK;
   uint32_t ev[PER], lv[PER];
 #pragma unroll
   for (int j = 0; j < PER; j++) {
-    const uint32_t p = s + threadIdx.x + j * SORT_BLOCK;
+    const uint32_t p = s + threadIdx.x + j * BLK;
     lv[j] = p < e ? (uint32_t)tmp_l[p] : 0xffffffffu;
     ev[j] = p < e ? tmp_e[p] : 0u;
   }
@@ -449,7 +455,7 @@ __global__ void __launch_bounds__(SORT_BLOCK)
     cur[l] = 0;
   }
   __syncthreads();
-  lds_exscan(loff, NL, scr);
+  lds_exscan<BLK>(loff, NL, scr);
   for (int l = threadIdx.x; l < NL; l += blockDim.x) cb[l] = coff[(size_t)k * NL + l] - loff[l];
 #pragma unroll
   for (int j = 0; j < PER; j++) {
@@ -1408,6 +1414,88 @@ struct MsmRun {
 };
 static constexpr int MSM_MAX_BATCH = 1024;
 
+// Launch geometry of the sort kernels: pass A's scatter / rows kernels run
+// blkA threads over a tile of `tile` scalars, pass B's kernels blkB threads
+// over a chunk of `chunk` entries.  Only the instantiated pairs are valid:
+//   pass A: 256 threads with any tile, 512 with tile 512 / 1024, 1024 with 1024
+//   pass B: (256, 8192), (512, 8192), (512, 16384), (1024, 16384)
+struct SortGeom {
+  uint32_t blkA, tile, blkB, chunk;
+};
+
+// The default by the MSM's entries (profiles/r08_sort_block_ab.txt; bucketing
+// ms with 256- / 512- / 1024-thread blocks, the last over tile 1024 and chunk
+// 16384): 2^26 entries and more take 1024 threads (13 x 2^24: 2.41 / 2.20 /
+// 2.02, 13 x 2^23: 1.26 / 1.13 / 1.06), 2^20 and more 512 threads over the same
+// tile and chunk as before (13 x 2^22: 0.674 / 0.576 / 0.587, 15 x 2^20 at
+// c = 17: 0.200 / 0.174 / 0.192, 17 x 2^16: 0.088 / 0.079 / 0.087), fewer keep
+// 256 (24 x 2^12: 0.076 / 0.078).  QG_SORT_BLOCK_A / QG_SORT_TILE /
+// QG_SORT_BLOCK_B / QG_SORT_CHUNK override (A/B runs); a combination without
+// an instantiation is QG_ERR_INVALID.
+// side: an MSM of a batch on the side streams, whose bucketing runs beside the
+// other stream's accumulation, keeps 256 threads: with the wider blocks
+// HyperPlonk's side bucketing gained 1-4 ms per proof and the accumulation
+// beside it lost 24-34 ms (proof 848-854 -> 870-872 ms).  The windows of
+// one-shot bases (wsel >= 0) keep it too: 2^20 bases measured 1.93 -> 1.85 ms of
+// bucketing with 512 threads, but the 2^24 bench leg 27.3 -> 27.4-27.6 ms.
+static constexpr size_t SORT_WIDE_MIN = (size_t)1 << 26;
+static constexpr size_t SORT_MID_MIN = (size_t)1 << 20;
+static SortGeom sort_geometry(size_t max_entries, int WE, bool narrow) {
+  SortGeom g;
+  const bool wide = !narrow && max_entries >= SORT_WIDE_MIN;
+  const bool mid = !narrow && max_entries >= SORT_MID_MIN;
+  g.blkA = wide ? 1024 : mid ? 512 : SORT_BLOCK;
+  g.blkB = wide ? 1024 : mid ? 512 : SORT_BLOCK;
+  g.chunk = wide ? 16384 : SORT_CHUNK;
+  // a block stages at least one scalar per thread: with many windows (small c)
+  // the wide tile does not fit the CU's LDS, and the default steps down
+  while (g.blkA > (uint32_t)SORT_BLOCK &&
+         (size_t)g.blkA * WE * 8 + (3 * (size_t)SORT_H_MAX + 16) * 4 > 160 * 1024)
+    g.blkA >>= 1;
+  if (const char* ov = getenv("QG_SORT_BLOCK_A")) g.blkA = (uint32_t)atoi(ov);
+  if (const char* ov = getenv("QG_SORT_BLOCK_B")) g.blkB = (uint32_t)atoi(ov);
+  if (const char* ov = getenv("QG_SORT_CHUNK")) g.chunk = (uint32_t)atoi(ov);
+  // pass-A tile: as many scalars as fit their WE digits (8 B each) in the LDS
+  // budget of 256-thread blocks; a wider block takes at least its own width
+  g.tile = SORT_TILE_MAX;
+  while (g.tile > 64 && (size_t)g.tile * WE * 8 > SORT_LDS_A) g.tile >>= 1;
+  if (g.blkA > SORT_BLOCK && g.blkA <= (uint32_t)SORT_TILE_MAX) g.tile = std::max(g.tile, g.blkA);
+  if (const char* ov = getenv("QG_SORT_TILE")) g.tile = (uint32_t)atoi(ov);
+  QG_CHECK(g.tile >= 64 && g.tile <= (uint32_t)SORT_TILE_MAX && (g.tile & (g.tile - 1)) == 0,
+           QG_ERR_INVALID, "QG_SORT_TILE must be a power of two in [64, 1024]");
+  QG_CHECK(g.blkA == 256 || ((g.blkA == 512 || g.blkA == 1024) && g.tile >= g.blkA),
+           QG_ERR_INVALID, "no pass-A sort kernel for this QG_SORT_BLOCK_A / QG_SORT_TILE");
+  QG_CHECK((g.blkB == 256 && g.chunk == 8192) || (g.blkB == 512 && g.chunk == 8192) ||
+               (g.blkB == 512 && g.chunk == 16384) || (g.blkB == 1024 && g.chunk == 16384),
+           QG_ERR_INVALID, "no pass-B sort kernel for this QG_SORT_BLOCK_B / QG_SORT_CHUNK");
+  return g;
+}
+
+// the > 64 KiB dynamic-LDS attribute of one kernel instantiation, once per
+// context (= per device and per calling thread: a context is used by one
+// thread at a time); every instantiation has its own memo key
+static void sort_lds_attr(qg_ctx* ctx, const void* fn, const std::string& key) {
+  if (ctx->memo.count(key)) return;
+  QG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  ctx->memo[key] = "1";
+}
+
+// QG_SORT_DISPATCH_A(blk, F): F(BLK) for the instantiated pass-A block width;
+// QG_SORT_DISPATCH_B(blk, chunk, F): F(BLK, CHUNK) for the pass-B pair
+#define QG_SORT_DISPATCH_A(blk, F) \
+  do {                             \
+    if ((blk) == 256) { F(256); }  \
+    else if ((blk) == 512) { F(512); } \
+    else { F(1024); }              \
+  } while (0)
+#define QG_SORT_DISPATCH_B(blk, chunk, F)                   \
+  do {                                                      \
+    if ((blk) == 256) { F(256, 8192); }                     \
+    else if ((blk) == 512 && (chunk) == 8192) { F(512, 8192); } \
+    else if ((blk) == 512) { F(512, 16384); }               \
+    else { F(1024, 16384); }                                \
+  } while (0)
+
 // bucketing (two-pass radix sort) + bucket accumulation of MSM `slot` of a
 // batch: sum_i d_scalars[i] * base[srs_off + i]
 //
@@ -1449,15 +1537,11 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
     // bucket id b = (g << LO) | l
     const int BB = c - 1, LO = (BB + 1) / 2, HI = BB - LO;
     const int H = 1 << HI, NL = 1 << LO;
-    // pass-A tile: as many scalars as fit their W digits (8 B each) in LDS
-    uint32_t tile = SORT_TILE_MAX;
-    while (tile > 64 && (size_t)tile * WE * 8 > SORT_LDS_A) tile >>= 1;
-    if (const char* ov = getenv("QG_SORT_TILE")) tile = (uint32_t)atoi(ov);  // tuning experiments
-    QG_CHECK(tile >= 64 && tile <= SORT_TILE_MAX && (tile & (tile - 1)) == 0, QG_ERR_INVALID,
-             "QG_SORT_TILE must be a power of two in [64, 1024]");
+    const SortGeom geo = sort_geometry(max_entries, WE, side || wsel >= 0);
+    const uint32_t tile = geo.tile, chunk = geo.chunk;
     const uint32_t nblk = div_up(n, tile);
     const size_t nghist = (size_t)H * nblk;
-    const size_t max_chunks = max_entries / SORT_CHUNK + H + 1;
+    const size_t max_chunks = max_entries / chunk + H + 1;
     uint32_t* ghist = ctx->scratch_as<uint32_t>("msm_ghist" + tg, nghist + 1);
     uint32_t* goff = ctx->scratch_as<uint32_t>("msm_goff" + tg, nghist + 1);
     uint32_t* gtiles = ctx->scratch_as<uint32_t>("msm_gtiles" + tg, div_up(nghist, 2048) + 1);
@@ -1552,8 +1636,14 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
     const size_t nslots = max_threads + nb + 1;  // partial slot of (thread t, bucket b): t + b
     X29Raw* partial = ctx->scratch_as<X29Raw>("msm_partial" + sfx, nslots);
     uint32_t* owner = ctx->scratch_as<uint32_t>("msm_owner" + sfx, nslots);
-    QG_CHECK(ntiles <= 1024 * 64 && H <= 1024 && NL <= 4096, QG_ERR_UNSUPPORTED,
+    QG_CHECK(ntiles <= 1024 * 64 && H <= SORT_H_MAX && NL <= SORT_NL_MAX, QG_ERR_UNSUPPORTED,
              "bucket count too large");
+    // dynamic LDS of the two scatters: staged entries, three count / offset
+    // rows, the scan's wave totals
+    const size_t smemA = (size_t)tile * WE * 8 + (3 * (size_t)H + geo.blkA / 64) * 4;
+    const size_t smemB = (size_t)chunk * 6 + (3 * (size_t)NL + geo.blkB / 64) * 4;
+    QG_CHECK(smemA <= 160 * 1024 && smemB <= 160 * 1024, QG_ERR_UNSUPPORTED,
+             "sort tile / chunk exceeds LDS");
     QG_CHECK(nslots < 0xffffffffull && max_chunks < 0xffffffffull, QG_ERR_UNSUPPORTED,
              "MSM too large");
 
@@ -1583,31 +1673,26 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
       hipLaunchKernelGGL(k_transpose32, dim3(div_up(nblk, 32), div_up(H, 32)), dim3(256), 0,
                          bst, goff, (uint32_t)H, nblk, orow);
       QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_sortA_rows, dim3(nblk), dim3(SORT_BLOCK), 0, bst, hrow, orow, H);
-      QG_LAUNCH_CHECK();
-      const size_t smemA = (size_t)tile * WE * 8 + (3 * (size_t)H + SORT_BLOCK) * 4;
-      QG_CHECK(smemA <= 160 * 1024, QG_ERR_UNSUPPORTED, "pass-A tile exceeds LDS");
-      // the >64 KiB dynamic-LDS attribute, once per context (= per device and
-      // per calling thread: a context is used by one thread at a time)
-      if (ctx->memo.count("msm_lds_attr") == 0) {
-        QG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sortA_scatter),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        QG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sortB_scatter),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->memo["msm_lds_attr"] = "1";
-      }
-      hipLaunchKernelGGL(k_sortA_scatter, dim3(nblk), dim3(SORT_BLOCK), smemA, bst,
-                         canon, n, srs->n, srs_off, c, W, LO, H, nblk, tile, hrow, orow, tmp_e, tmp_l,
-                         wsel);
-      QG_LAUNCH_CHECK();
+#define QG_SORT_A_LAUNCH(BLK)                                                                    \
+  hipLaunchKernelGGL(k_sortA_rows<BLK>, dim3(nblk), dim3(BLK), 0, bst, hrow, orow, H);           \
+  QG_LAUNCH_CHECK();                                                                             \
+  sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortA_scatter<BLK>), "msm_lds_attrA" #BLK); \
+  hipLaunchKernelGGL(k_sortA_scatter<BLK>, dim3(nblk), dim3(BLK), smemA, bst, canon, n, srs->n,  \
+                     srs_off, c, W, LO, H, nblk, tile, hrow, orow, tmp_e, tmp_l, wsel);          \
+  QG_LAUNCH_CHECK()
+      QG_SORT_DISPATCH_A(geo.blkA, QG_SORT_A_LAUNCH);
+#undef QG_SORT_A_LAUNCH
       // pass B: sort every group by the low bits, in chunks
-      hipLaunchKernelGGL(k_sort_chunks, dim3(1), dim3(1024), 0, bst, goff, nblk, H,
+      hipLaunchKernelGGL(k_sort_chunks, dim3(1), dim3(1024), 0, bst, goff, nblk, H, chunk,
                          gstart, cbase, cgroup, misc);
       QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_sortB_hist, dim3((unsigned)max_chunks), dim3(SORT_BLOCK),
-                         NL * sizeof(uint32_t), bst, tmp_l, gstart, cbase, cgroup, misc, NL,
-                         chist);
-      QG_LAUNCH_CHECK();
+#define QG_SORT_B_HIST(BLK, CHUNK)                                                              \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_hist<BLK, CHUNK>), dim3((unsigned)max_chunks),     \
+                     dim3(BLK), NL * sizeof(uint32_t), bst, tmp_l, gstart, cbase, cgroup, misc, \
+                     NL, chist);                                                                \
+  QG_LAUNCH_CHECK()
+      QG_SORT_DISPATCH_B(geo.blkB, chunk, QG_SORT_B_HIST);
+#undef QG_SORT_B_HIST
       hipLaunchKernelGGL(k_sort_bucket_count, dim3(div_up(nb, 256)), dim3(256), 0, bst,
                          cbase, chist, LO, nb, counts);
       QG_LAUNCH_CHECK();
@@ -1634,11 +1719,15 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
       hipLaunchKernelGGL(k_sort_chunk_offsets, dim3(div_up(nb, 256)), dim3(256), 0, bst,
                          cbase, chist, LO, nb, bstart, coff);
       QG_LAUNCH_CHECK();
-      const size_t smemB = (size_t)SORT_CHUNK * 6 + (3 * (size_t)NL + SORT_BLOCK) * 4;
-      hipLaunchKernelGGL(k_sortB_scatter, dim3((unsigned)max_chunks), dim3(SORT_BLOCK), smemB,
-                         bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL, chist, coff,
-                         entries);
-      QG_LAUNCH_CHECK();
+#define QG_SORT_B_SCATTER(BLK, CHUNK)                                                          \
+  sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortB_scatter<BLK, CHUNK>),              \
+                "msm_lds_attrB" #BLK "_" #CHUNK);                                              \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<BLK, CHUNK>), dim3((unsigned)max_chunks), \
+                     dim3(BLK), smemB, bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL,     \
+                     chist, coff, entries);                                                    \
+  QG_LAUNCH_CHECK()
+      QG_SORT_DISPATCH_B(geo.blkB, chunk, QG_SORT_B_SCATTER);
+#undef QG_SORT_B_SCATTER
     }
     const hipStream_t ast = bst;  // the accumulation follows on the same stream
     {
