@@ -94,6 +94,27 @@ QG_DEV void for_each_digit(const Fr& canon, int c, int W, Emit&& emit) {
   }
 }
 
+// One step of for_each_digit without a branch on the digit's sign: window w's
+// digit of the scalar in v (shifted down by c), as bucket b, sign and any (the
+// digit is not 0).  The scatter takes its digits through this: with a branch
+// the lanes of a wave split by sign and every window runs both sides, each
+// with its own LDS round trip.
+struct DigitStep {
+  uint32_t b;
+  bool neg, any;
+};
+QG_DEV DigitStep digit_step(uint32_t (&v)[8], uint32_t& carry, int c) {
+  const uint32_t full = 1u << c;
+  const uint32_t d = (v[0] & (full - 1u)) + carry;
+  const bool neg = d > (full >> 1);
+  const uint32_t mag = neg ? full - d : d;  // digit = d - 2^c < 0, or d
+  carry = neg ? 1u : 0u;
+#pragma unroll
+  for (int i = 0; i < 7; i++) v[i] = __builtin_amdgcn_alignbit(v[i + 1], v[i], (uint32_t)c);
+  v[7] >>= c;
+  return DigitStep{mag - 1u, neg, mag != 0u};
+}
+
 // XCD-aware tile order: workgroup b runs on XCD b % 8 (placement is a speed
 // hint only, never assumed for correctness), so tile t = start(b % 8) + b / 8
 // gives every XCD one contiguous range of tiles.  The runs that neighbouring
@@ -118,6 +139,7 @@ static constexpr int SORT_TILE_MAX = 1024;                  // scalars per block
 static constexpr size_t SORT_LDS_A = 72 * 1024;             // LDS budget for staged entries (2 blocks/CU)
 static constexpr int SORT_CHUNK = 8192;                     // entries per block (pass B), 256-thread blocks
 static constexpr int SORT_H_MAX = 1024, SORT_NL_MAX = 4096; // most groups / buckets per group
+static constexpr int SORT_ILP = 4;                          // LDS counter atomics in flight per thread (scatters)
 
 // ---- cross-stream hand-over guard (msm_device_batch) ----------------------
 // A batch on the side streams hands data over by events only: the scalars
@@ -238,6 +260,10 @@ __device__ __forceinline__ int lds_upper(const uint32_t* off, int n, uint32_t p)
   return lo;
 }
 
+// vmcnt(0) of gfx9's s_waitcnt, the other counters left open: the prefetched
+// loads of a scatter block are waited for where only they are in flight
+static constexpr int QG_WAIT_VM0 = 0x0F70;
+
 // Pass A scatter: digits of the block's tile are bucketed by group in LDS
 // (entry + its bucket), then written out as contiguous per-group runs
 // (coalesced stores) through a per-block base table, no per-element search.
@@ -245,62 +271,163 @@ __device__ __forceinline__ int lds_upper(const uint32_t* off, int n, uint32_t p)
 // Output per digit: the table entry (u32) and the bucket's low LO bits (u16).
 // wsel >= 0: only window wsel's digits, entry = the base's row in the one
 // table of one-shot bases (no window offset)
-template <int BLK>
+//
+// A block walks the tiles k = blockIdx.x, + gridDim.x, ... < nblk (a pure
+// function of the launch, no work counter), each taken through xcd_tile: with
+// a grid that is a multiple of 8 every block stays in its XCD's range.  A
+// grid of nblk blocks is one tile per block.  PF (a grid below nblk): the next
+// tile's scalars and rows are loaded into registers before the current
+// tile's LDS scatter and its rows are put into the second row buffer (rstride
+// words after the first) before the write-out, so their round trip runs under
+// the scatter, and the write-out's global stores under the next tile's; only
+// its LDS reads are waited for (one barrier) before the staging area is
+// reused.  Without PF every tile is loaded when its turn comes.
+template <int BLK, bool PF>
 __global__ void __launch_bounds__(BLK)
     k_sortA_scatter(const Fr* __restrict__ canon, size_t n, size_t N, size_t off, int c, int W, int LO,
                     int H,
                     uint32_t nblk, uint32_t tile, const uint32_t* __restrict__ hrow,
                     const uint32_t* __restrict__ orow, uint32_t* __restrict__ tmp_e,
-                    uint16_t* __restrict__ tmp_l, int wsel) {
+                    uint16_t* __restrict__ tmp_l, int wsel, uint32_t rstride) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* ent = reinterpret_cast<uint32_t*>(smem);
   uint32_t* bkt = ent + (size_t)tile * (wsel < 0 ? W : 1);
-  uint32_t* loff = bkt + (size_t)tile * (wsel < 0 ? W : 1);
-  uint32_t* cur = loff + H;
-  uint32_t* gb = cur + H;
-  uint32_t* scr = gb + H;
-  (void)scr;
-  const uint32_t tb = xcd_tile(blockIdx.x, nblk);
-  const size_t base = (size_t)tb * tile;
-  const size_t end = base + tile < n ? base + tile : n;
-  // the thread's scalars (tile <= SORT_TILE_MAX) are loaded first: their round
-  // trip overlaps the row loads below
+  uint32_t* rows = bkt + (size_t)tile * (wsel < 0 ? W : 1);
+  uint32_t k = blockIdx.x;
+  if (k >= nblk) return;  // no tile: before the first barrier
   static_assert(SORT_TILE_MAX % BLK == 0, "pass-A tile must split evenly over the block");
-  constexpr int PER = SORT_TILE_MAX / BLK;
+  static_assert(SORT_H_MAX % BLK == 0, "pass-A rows must split evenly over the block");
+  constexpr int PER = SORT_TILE_MAX / BLK, RPT = SORT_H_MAX / BLK, ILP = SORT_ILP;
+  // the thread's scalars (tile <= SORT_TILE_MAX) are loaded first: their round
+  // trip overlaps the row loads; rows prepared by k_sortA_rows: the tile's
+  // local run starts and global bases
+  auto load_scalars = [&](uint32_t tb, Fr* s) {
+    const size_t base = (size_t)tb * tile;
+    const size_t end = base + tile < n ? base + tile : n;
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+      const size_t i = base + threadIdx.x + (size_t)j * BLK;
+      if (i < end) s[j] = canon[i];
+    }
+  };
+  auto load = [&](uint32_t kk, Fr* s, uint32_t* h, uint32_t* o) {
+    const uint32_t tb = xcd_tile(kk, nblk);
+    load_scalars(tb, s);
+#pragma unroll
+    for (int r = 0; r < RPT; r++) {
+      const int g = threadIdx.x + r * BLK;
+      if (g < H) {
+        h[r] = hrow[(size_t)tb * H + g];
+        o[r] = orow[(size_t)tb * H + g];
+      }
+    }
+  };
+  // a row buffer: loff[H] | cur[H] | gb[H]
+  auto put_rows = [&](uint32_t* loff, const uint32_t* h, const uint32_t* o) {
+#pragma unroll
+    for (int r = 0; r < RPT; r++) {
+      const int g = threadIdx.x + r * BLK;
+      if (g < H) {
+        loff[g] = h[r];
+        loff[H + g] = 0;
+        loff[2 * H + g] = o[r];
+      }
+    }
+  };
   Fr sv[PER];
+  uint32_t hr[RPT], gr[RPT];
+  uint32_t* loff = rows;
+  if (PF) {
+    load(k, sv, hr, gr);
+    put_rows(loff, hr, gr);
+    // the first tile is waited for here, once: inside the loop a wait for it
+    // would also wait for the next tile's loads, which are issued after it
+    __builtin_amdgcn_s_waitcnt(QG_WAIT_VM0);
+    __syncthreads();
+  }
+  for (;;) {
+    const uint32_t kn = k + gridDim.x;
+    const bool more = kn < nblk;
+    Fr nsv[PER];
+    uint32_t nhr[RPT], ngr[RPT];
+    if (PF) {
+      if (more) load(kn, nsv, nhr, ngr);
+    } else {
+      const uint32_t tb = xcd_tile(k, nblk);
+      load_scalars(tb, sv);
+      for (int g = threadIdx.x; g < H; g += blockDim.x) {
+        loff[g] = hrow[(size_t)tb * H + g];
+        loff[2 * H + g] = orow[(size_t)tb * H + g];
+        loff[H + g] = 0;
+      }
+      __syncthreads();
+    }
+    uint32_t* cur = loff + H;
+    const uint32_t* gb = cur + H;
+    const size_t base = (size_t)xcd_tile(k, nblk) * tile;
+    const size_t end = base + tile < n ? base + tile : n;
 #pragma unroll
-  for (int j = 0; j < PER; j++) {
-    const size_t i = base + threadIdx.x + (size_t)j * BLK;
-    if (i < end) sv[j] = canon[i];
-  }
-  // rows prepared by k_sortA_rows: the tile's local run starts and global bases
-  for (int g = threadIdx.x; g < H; g += blockDim.x) {
-    loff[g] = hrow[(size_t)tb * H + g];
-    gb[g] = orow[(size_t)tb * H + g];
-    cur[g] = 0;
-  }
-  __syncthreads();
+    for (int j = 0; j < PER; j++) {
+      const size_t i = base + threadIdx.x + (size_t)j * BLK;
+      if (i >= end) break;
+      // ILP windows at a time: their counter atomics are issued back to
+      // back (LDS returns in order), then the slots are filled
+      uint32_t v[8], carry = 0;
 #pragma unroll
-  for (int j = 0; j < PER; j++) {
-    const size_t i = base + threadIdx.x + (size_t)j * BLK;
-    if (i >= end) break;
-    for_each_digit(sv[j], c, W, [&](int w, uint32_t b, bool neg) {
-      if (wsel >= 0 && w != wsel) return;
-      const uint32_t g = b >> LO;
-      const uint32_t slot = loff[g] + atomicAdd(&cur[g], 1u);
-      const size_t row = (wsel < 0 ? (size_t)w * N : 0) + off + i;
-      ent[slot] = (uint32_t)row | (neg ? 0x80000000u : 0u);
-      bkt[slot] = b;
-    });
-  }
-  __syncthreads();
-  const uint32_t total = loff[H - 1] + cur[H - 1];
-  const uint32_t lmask = (1u << LO) - 1u;
-  for (uint32_t p = threadIdx.x; p < total; p += blockDim.x) {
-    const uint32_t b = bkt[p];
-    const uint32_t dst = gb[b >> LO] + p;
-    tmp_e[dst] = ent[p];
-    tmp_l[dst] = (uint16_t)(b & lmask);
+      for (int q = 0; q < 8; q++) v[q] = sv[j].v[q];
+      for (int w0 = 0; w0 < W; w0 += ILP) {
+        uint32_t r[ILP], lo[ILP], g[ILP], en[ILP], bb[ILP];
+        bool ok[ILP];
+#pragma unroll
+        for (int q = 0; q < ILP; q++) {
+          const int w = w0 + q;
+          const DigitStep t = digit_step(v, carry, c);
+          ok[q] = w < W && t.any && (wsel < 0 || w == wsel);
+          const size_t row = (wsel < 0 ? (size_t)w * N : 0) + off + i;
+          en[q] = (uint32_t)row | (t.neg ? 0x80000000u : 0u);
+          bb[q] = t.b;
+          g[q] = t.b >> LO;
+          r[q] = lo[q] = 0;
+          if (ok[q]) {
+            lo[q] = loff[g[q]];
+            r[q] = atomicAdd(&cur[g[q]], 1u);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < ILP; q++) {
+          if (!ok[q]) continue;
+          const uint32_t slot = lo[q] + r[q];
+          ent[slot] = en[q];
+          bkt[slot] = bb[q];
+        }
+      }
+    }
+    uint32_t* nloff = loff == rows ? rows + rstride : rows;
+    if (PF) {
+      // After this wait no load is in flight, so nothing below waits for the
+      // write-out's stores.  On every path (not under `more`): the compiler
+      // places its own waits by block, not by condition.  The other row
+      // buffer was last read by the write-out before the last barrier.
+      __builtin_amdgcn_s_waitcnt(QG_WAIT_VM0);
+      if (more) put_rows(nloff, nhr, ngr);
+    }
+    __syncthreads();
+    const uint32_t total = loff[H - 1] + cur[H - 1];
+    const uint32_t lmask = (1u << LO) - 1u;
+    for (uint32_t p = threadIdx.x; p < total; p += blockDim.x) {
+      const uint32_t b = bkt[p];
+      const uint32_t dst = gb[b >> LO] + p;
+      tmp_e[dst] = ent[p];
+      tmp_l[dst] = (uint16_t)(b & lmask);
+    }
+    if (!more) break;
+    __syncthreads();  // the write-out's LDS reads, before the next scatter's writes
+    k = kn;
+    if (PF) {
+#pragma unroll
+      for (int j = 0; j < PER; j++) sv[j] = nsv[j];
+      loff = nloff;
+    }
   }
 }
 
@@ -418,55 +545,158 @@ __global__ void k_sort_chunk_offsets(const uint32_t* __restrict__ cbase,
 
 // Pass B scatter: the chunk is counting-sorted by the low bucket bits in LDS,
 // then each bucket run is written contiguously at its chunk offset.
-template <int BLK, int CHUNK>
+// A block walks the chunks k = blockIdx.x, + gridDim.x, ... < *nchunks like
+// pass A's tiles.  PF: the next chunk's entries, its histogram row and its
+// offset row are loaded into registers before the current chunk's scan and
+// scatter (its start and end one chunk earlier still: two dependent scalar
+// loads), and the histogram row goes to the second row buffer (rstride words
+// after the first) before the write-out.
+template <int BLK, int CHUNK, bool PF>
 __global__ void __launch_bounds__(BLK)
     k_sortB_scatter(const uint32_t* __restrict__ tmp_e, const uint16_t* __restrict__ tmp_l,
                     const uint32_t* __restrict__ gstart,
                     const uint32_t* __restrict__ cbase, const uint32_t* __restrict__ chunk_group,
                     const uint32_t* __restrict__ nchunks, int NL, const uint32_t* __restrict__ chist,
-                    const uint32_t* __restrict__ coff, uint32_t* __restrict__ entries) {
+                    const uint32_t* __restrict__ coff, uint32_t* __restrict__ entries,
+                    uint32_t rstride) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint32_t* e32 = reinterpret_cast<uint32_t*>(smem);
   static_assert(CHUNK % BLK == 0, "pass-B chunk must split evenly over the block");
+  static_assert(SORT_NL_MAX % BLK == 0, "pass-B rows must split evenly over the block");
   uint16_t* bins = reinterpret_cast<uint16_t*>(e32 + CHUNK);
-  uint32_t* loff = reinterpret_cast<uint32_t*>(bins + CHUNK);
-  uint32_t* cur = loff + NL;
-  uint32_t* cb = cur + NL;
-  uint32_t* scr = cb + NL;
+  uint32_t* scr = reinterpret_cast<uint32_t*>(bins + CHUNK);
+  uint32_t* rows = scr + BLK / 64;  // a row buffer: loff[NL] | cur[NL] | cb[NL]
   const uint32_t nch = *nchunks;
-  if (blockIdx.x >= nch) return;
-  const uint32_t k = xcd_tile(blockIdx.x, nch);
-  const uint32_t g = chunk_group[k];
-  const uint32_t s = gstart[g] + (k - cbase[g]) * CHUNK;
-  const uint32_t e = min(s + CHUNK, gstart[g + 1]);
+  uint32_t k = blockIdx.x;
+  if (k >= nch) return;  // no chunk: before the first barrier
+  constexpr int PER = CHUNK / BLK, RPT = SORT_NL_MAX / BLK, ILP = SORT_ILP;
+  // chunk kk = xcd_tile's image: its entries [s, e) of tmp_e / tmp_l
+  auto span = [&](uint32_t kk, uint32_t& ck, uint32_t& s, uint32_t& e) {
+    ck = xcd_tile(kk, nch);
+    const uint32_t g = chunk_group[ck];
+    s = gstart[g] + (ck - cbase[g]) * CHUNK;
+    e = min(s + CHUNK, gstart[g + 1]);
+  };
   // all of the thread's entries are loaded first: their round trip overlaps
-  // the histogram row, its scan and the offset row instead of following them
-  constexpr int PER = CHUNK / BLK;
-  uint32_t ev[PER], lv[PER];
+  // the histogram row (computed by k_sortB_hist), its scan and the offset row
+  auto load_entries = [&](uint32_t s, uint32_t e, uint32_t* ev, uint32_t* lv) {
 #pragma unroll
-  for (int j = 0; j < PER; j++) {
-    const uint32_t p = s + threadIdx.x + j * BLK;
-    lv[j] = p < e ? (uint32_t)tmp_l[p] : 0xffffffffu;
-    ev[j] = p < e ? tmp_e[p] : 0u;
-  }
-  // the chunk's histogram was computed by k_sortB_hist (chist)
-  for (int l = threadIdx.x; l < NL; l += blockDim.x) {
-    loff[l] = chist[(size_t)k * NL + l];
-    cur[l] = 0;
-  }
-  __syncthreads();
-  lds_exscan<BLK>(loff, NL, scr);
-  for (int l = threadIdx.x; l < NL; l += blockDim.x) cb[l] = coff[(size_t)k * NL + l] - loff[l];
+    for (int j = 0; j < PER; j++) {
+      const uint32_t p = s + threadIdx.x + j * BLK;
+      lv[j] = p < e ? (uint32_t)tmp_l[p] : 0xffffffffu;
+      ev[j] = p < e ? tmp_e[p] : 0u;
+    }
+  };
+  auto load = [&](uint32_t ck, uint32_t s, uint32_t e, uint32_t* ev, uint32_t* lv, uint32_t* h,
+                  uint32_t* o) {
+    load_entries(s, e, ev, lv);
 #pragma unroll
-  for (int j = 0; j < PER; j++) {
-    if (lv[j] == 0xffffffffu) continue;
-    const uint32_t l = lv[j];
-    const uint32_t slot = loff[l] + atomicAdd(&cur[l], 1u);
-    e32[slot] = ev[j];
-    bins[slot] = (uint16_t)l;
+    for (int r = 0; r < RPT; r++) {
+      const int l = threadIdx.x + r * BLK;
+      if (l < NL) {
+        h[r] = chist[(size_t)ck * NL + l];
+        o[r] = coff[(size_t)ck * NL + l];
+      }
+    }
+  };
+  auto put_rows = [&](uint32_t* loff, const uint32_t* h) {
+#pragma unroll
+    for (int r = 0; r < RPT; r++) {
+      const int l = threadIdx.x + r * BLK;
+      if (l < NL) {
+        loff[l] = h[r];
+        loff[NL + l] = 0;
+      }
+    }
+  };
+  uint32_t ck = 0, s = 0, e = 0, nck = 0, ns = 0, ne = 0;
+  uint32_t ev[PER], lv[PER], hr[RPT], co[RPT];
+  uint32_t* loff = rows;
+  if (PF) {
+    span(k, ck, s, e);
+    if (k + gridDim.x < nch) span(k + gridDim.x, nck, ns, ne);
+    load(ck, s, e, ev, lv, hr, co);
+    put_rows(loff, hr);
+    __builtin_amdgcn_s_waitcnt(QG_WAIT_VM0);  // as in pass A: the first chunk, once
+    __syncthreads();
   }
-  __syncthreads();
-  for (uint32_t q = threadIdx.x; q < e - s; q += blockDim.x) entries[cb[bins[q]] + q] = e32[q];
+  for (;;) {
+    const uint32_t kn = k + gridDim.x;
+    const bool more = kn < nch;
+    uint32_t nev[PER], nlv[PER], nhr[RPT], nco[RPT];
+    uint32_t fck = 0, fs = 0, fe = 0;  // the chunk after the next
+    if (PF) {
+      if (more) {
+        load(nck, ns, ne, nev, nlv, nhr, nco);
+        if (kn + gridDim.x < nch) span(kn + gridDim.x, fck, fs, fe);
+      }
+    } else {
+      span(k, ck, s, e);
+      load_entries(s, e, ev, lv);
+      for (int l = threadIdx.x; l < NL; l += blockDim.x) {
+        loff[l] = chist[(size_t)ck * NL + l];
+        loff[NL + l] = 0;
+      }
+      __syncthreads();
+    }
+    uint32_t* cur = loff + NL;
+    uint32_t* cb = cur + NL;
+    lds_exscan<BLK>(loff, NL, scr);
+    if (PF) {
+#pragma unroll
+      for (int r = 0; r < RPT; r++) {
+        const int l = threadIdx.x + r * BLK;
+        if (l < NL) cb[l] = co[r] - loff[l];
+      }
+    } else {
+      for (int l = threadIdx.x; l < NL; l += blockDim.x) cb[l] = coff[(size_t)ck * NL + l] - loff[l];
+    }
+    // ILP entries at a time, as in pass A
+    static_assert(PER % ILP == 0, "pass-B entries per thread must split into ILP groups");
+#pragma unroll
+    for (int j0 = 0; j0 < PER; j0 += ILP) {
+      uint32_t r[ILP], lo[ILP];
+#pragma unroll
+      for (int q = 0; q < ILP; q++) {
+        r[q] = lo[q] = 0;
+        if (lv[j0 + q] != 0xffffffffu) {
+          lo[q] = loff[lv[j0 + q]];
+          r[q] = atomicAdd(&cur[lv[j0 + q]], 1u);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < ILP; q++) {
+        if (lv[j0 + q] == 0xffffffffu) continue;
+        const uint32_t l = lv[j0 + q];
+        const uint32_t slot = lo[q] + r[q];
+        e32[slot] = ev[j0 + q];
+        bins[slot] = (uint16_t)l;
+      }
+    }
+    uint32_t* nloff = loff == rows ? rows + rstride : rows;
+    if (PF) {
+      // as in pass A: no load stays in flight past this wait
+      __builtin_amdgcn_s_waitcnt(QG_WAIT_VM0);
+      if (more) put_rows(nloff, nhr);
+    }
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < e - s; q += blockDim.x) entries[cb[bins[q]] + q] = e32[q];
+    if (!more) break;
+    __syncthreads();  // the write-out's LDS reads, before the next scatter's writes
+    k = kn;
+    if (PF) {
+#pragma unroll
+      for (int j = 0; j < PER; j++) {
+        ev[j] = nev[j];
+        lv[j] = nlv[j];
+      }
+#pragma unroll
+      for (int r = 0; r < RPT; r++) co[r] = nco[r];
+      loff = nloff;
+      s = ns, e = ne;
+      nck = fck, ns = fs, ne = fe;
+    }
+  }
 }
 
 // ---- generic exclusive scan of uint32 (out[n] = total) -------------------
@@ -1419,8 +1649,13 @@ static constexpr int MSM_MAX_BATCH = 1024;
 // over a chunk of `chunk` entries.  Only the instantiated pairs are valid:
 //   pass A: 256 threads with any tile, 512 with tile 512 / 1024, 1024 with 1024
 //   pass B: (256, 8192), (512, 8192), (512, 16384), (1024, 16384)
+// gridA / gridB: blocks of the two scatter kernels.  0: one per tile / chunk;
+// -1: the default, which is that too except for the wide class, whose blocks
+// walk several tiles each (sort_scatter_grid)
 struct SortGeom {
   uint32_t blkA, tile, blkB, chunk;
+  int gridA, gridB;
+  bool wide;
 };
 
 // The default by the MSM's entries (profiles/r08_sort_block_ab.txt; bucketing
@@ -1431,7 +1666,10 @@ struct SortGeom {
 // c = 17: 0.200 / 0.174 / 0.192, 17 x 2^16: 0.088 / 0.079 / 0.087), fewer keep
 // 256 (24 x 2^12: 0.076 / 0.078).  QG_SORT_BLOCK_A / QG_SORT_TILE /
 // QG_SORT_BLOCK_B / QG_SORT_CHUNK override (A/B runs); a combination without
-// an instantiation is QG_ERR_INVALID.
+// an instantiation is QG_ERR_INVALID.  QG_SORT_GRID_A / QG_SORT_GRID_B force
+// the scatters' block counts (0 = one block per tile / chunk; any count up to
+// SORT_GRID_MAX runs, a multiple of 8 keeps a block's tiles on one XCD; blocks
+// beyond the tile count exit at once); out of range is QG_ERR_INVALID.
 // side: an MSM of a batch on the side streams, whose bucketing runs beside the
 // other stream's accumulation, keeps 256 threads: with the wider blocks
 // HyperPlonk's side bucketing gained 1-4 ms per proof and the accumulation
@@ -1440,6 +1678,14 @@ struct SortGeom {
 // bucketing with 512 threads, but the 2^24 bench leg 27.3 -> 27.4-27.6 ms.
 static constexpr size_t SORT_WIDE_MIN = (size_t)1 << 26;
 static constexpr size_t SORT_MID_MIN = (size_t)1 << 20;
+static constexpr int SORT_GRID_MAX = 1 << 20;
+static int sort_grid_override(const char* ov) {
+  char* end = nullptr;
+  const long v = strtol(ov, &end, 10);
+  QG_CHECK(end != ov && *end == 0 && v >= 0 && v <= SORT_GRID_MAX, QG_ERR_INVALID,
+           "QG_SORT_GRID_A / QG_SORT_GRID_B must be a block count in [0, 2^20]");
+  return (int)v;
+}
 static SortGeom sort_geometry(size_t max_entries, int WE, bool narrow) {
   SortGeom g;
   const bool wide = !narrow && max_entries >= SORT_WIDE_MIN;
@@ -1447,6 +1693,8 @@ static SortGeom sort_geometry(size_t max_entries, int WE, bool narrow) {
   g.blkA = wide ? 1024 : mid ? 512 : SORT_BLOCK;
   g.blkB = wide ? 1024 : mid ? 512 : SORT_BLOCK;
   g.chunk = wide ? 16384 : SORT_CHUNK;
+  g.wide = wide;
+  g.gridA = g.gridB = -1;
   // a block stages at least one scalar per thread: with many windows (small c)
   // the wide tile does not fit the CU's LDS, and the default steps down
   while (g.blkA > (uint32_t)SORT_BLOCK &&
@@ -1455,6 +1703,8 @@ static SortGeom sort_geometry(size_t max_entries, int WE, bool narrow) {
   if (const char* ov = getenv("QG_SORT_BLOCK_A")) g.blkA = (uint32_t)atoi(ov);
   if (const char* ov = getenv("QG_SORT_BLOCK_B")) g.blkB = (uint32_t)atoi(ov);
   if (const char* ov = getenv("QG_SORT_CHUNK")) g.chunk = (uint32_t)atoi(ov);
+  if (const char* ov = getenv("QG_SORT_GRID_A")) g.gridA = sort_grid_override(ov);
+  if (const char* ov = getenv("QG_SORT_GRID_B")) g.gridB = sort_grid_override(ov);
   // pass-A tile: as many scalars as fit their WE digits (8 B each) in the LDS
   // budget of 256-thread blocks; a wider block takes at least its own width
   g.tile = SORT_TILE_MAX;
@@ -1478,6 +1728,34 @@ static void sort_lds_attr(qg_ctx* ctx, const void* fn, const std::string& key) {
   if (ctx->memo.count(key)) return;
   QG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   ctx->memo[key] = "1";
+}
+
+// Blocks of a scatter kernel.  forced > 0: that many; 0: one per tile.  The
+// default (-1) is one per tile too, except where `multi` (the wide class with
+// the prefetching instantiation): SORT_GRID_ROUNDS times the blocks the device
+// holds at once (the kernel's occupancy at this LDS size x CUs), a multiple
+// of 8 so that a block's tiles stay in one XCD's range, at most one per tile.
+// Exactly the resident count measured no better than one block per tile
+// (2^24 bucketing 2.02 ms both; the slowest CU sets the time), 4 and 8 rounds
+// of blocks, which the dispatcher hands to whichever CU is free, 1.93 / 1.90
+// (profiles/r09_sort_pipeline_ab.txt).
+static constexpr size_t SORT_GRID_ROUNDS = 8;
+static uint32_t sort_scatter_grid(qg_ctx* ctx, const void* fn, const std::string& key, int blk,
+                                  size_t smem, int forced, bool multi, size_t count) {
+  if (forced > 0) return (uint32_t)forced;
+  if (forced == 0 || !multi) return (uint32_t)count;
+  const std::string mk = key + "_occ" + std::to_string(smem);
+  auto it = ctx->memo.find(mk);
+  int occ = 0;
+  if (it == ctx->memo.end()) {
+    QG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, blk, smem));
+    ctx->memo[mk] = std::to_string(occ);
+  } else {
+    occ = std::stoi(it->second);
+  }
+  QG_CHECK(occ >= 1, QG_ERR_DEVICE, "sort scatter kernel cannot be resident");
+  const size_t blocks = (((size_t)occ * ctx->num_cus()) & ~(size_t)7) * SORT_GRID_ROUNDS;
+  return (uint32_t)(blocks >= 8 && blocks < count ? blocks : count);
 }
 
 // QG_SORT_DISPATCH_A(blk, F): F(BLK) for the instantiated pass-A block width;
@@ -1640,10 +1918,28 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
              "bucket count too large");
     // dynamic LDS of the two scatters: staged entries, three count / offset
     // rows, the scan's wave totals
-    const size_t smemA = (size_t)tile * WE * 8 + (3 * (size_t)H + geo.blkA / 64) * 4;
-    const size_t smemB = (size_t)chunk * 6 + (3 * (size_t)NL + geo.blkB / 64) * 4;
+    size_t smemA = (size_t)tile * WE * 8 + (3 * (size_t)H + geo.blkA / 64) * 4;
+    size_t smemB = (size_t)chunk * 6 + (3 * (size_t)NL + geo.blkB / 64) * 4;
     QG_CHECK(smemA <= 160 * 1024 && smemB <= 160 * 1024, QG_ERR_UNSUPPORTED,
              "sort tile / chunk exceeds LDS");
+    // The scatters' grids.  Fewer blocks than tiles / chunks: the 1024-thread
+    // kernels prefetch the next tile (a second row buffer in LDS, where it
+    // fits); the narrower ones walk their tiles without (no measured case for
+    // them).
+    const void* fnA = reinterpret_cast<const void*>(&k_sortA_scatter<1024, true>);
+    const void* fnB = reinterpret_cast<const void*>(&k_sortB_scatter<1024, 16384, true>);
+    const size_t smemA2 = smemA + 3 * (size_t)H * 4, smemB2 = smemB + 3 * (size_t)NL * 4;
+    const bool canA = geo.blkA == 1024 && smemA2 <= 160 * 1024;
+    const bool canB = geo.blkB == 1024 && smemB2 <= 160 * 1024;
+    if (canA) sort_lds_attr(ctx, fnA, "msm_lds_attrA1024pf");
+    if (canB) sort_lds_attr(ctx, fnB, "msm_lds_attrB1024_16384pf");
+    const uint32_t gridA = sort_scatter_grid(ctx, fnA, "msm_sortA1024pf", 1024, smemA2, geo.gridA,
+                                             geo.wide && canA, nblk);
+    const uint32_t gridB = sort_scatter_grid(ctx, fnB, "msm_sortB1024pf", 1024, smemB2, geo.gridB,
+                                             geo.wide && canB, max_chunks);
+    const bool pfA = canA && gridA < nblk, pfB = canB && gridB < max_chunks;
+    if (pfA) smemA = smemA2;
+    if (pfB) smemB = smemB2;
     QG_CHECK(nslots < 0xffffffffull && max_chunks < 0xffffffffull, QG_ERR_UNSUPPORTED,
              "MSM too large");
 
@@ -1676,9 +1972,17 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
 #define QG_SORT_A_LAUNCH(BLK)                                                                    \
   hipLaunchKernelGGL(k_sortA_rows<BLK>, dim3(nblk), dim3(BLK), 0, bst, hrow, orow, H);           \
   QG_LAUNCH_CHECK();                                                                             \
-  sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortA_scatter<BLK>), "msm_lds_attrA" #BLK); \
-  hipLaunchKernelGGL(k_sortA_scatter<BLK>, dim3(nblk), dim3(BLK), smemA, bst, canon, n, srs->n,  \
-                     srs_off, c, W, LO, H, nblk, tile, hrow, orow, tmp_e, tmp_l, wsel);          \
+  if (pfA) {                                                                                     \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortA_scatter<1024, true>), dim3(gridA), dim3(1024),    \
+                       smemA, bst, canon, n, srs->n, srs_off, c, W, LO, H, nblk, tile, hrow,     \
+                       orow, tmp_e, tmp_l, wsel, 3u * (uint32_t)H);                              \
+  } else {                                                                                       \
+    sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortA_scatter<BLK, false>),              \
+                  "msm_lds_attrA" #BLK);                                                         \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortA_scatter<BLK, false>), dim3(gridA), dim3(BLK),     \
+                       smemA, bst, canon, n, srs->n, srs_off, c, W, LO, H, nblk, tile, hrow,     \
+                       orow, tmp_e, tmp_l, wsel, 0u);                                            \
+  }                                                                                              \
   QG_LAUNCH_CHECK()
       QG_SORT_DISPATCH_A(geo.blkA, QG_SORT_A_LAUNCH);
 #undef QG_SORT_A_LAUNCH
@@ -1720,11 +2024,17 @@ static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_s
                          cbase, chist, LO, nb, bstart, coff);
       QG_LAUNCH_CHECK();
 #define QG_SORT_B_SCATTER(BLK, CHUNK)                                                          \
-  sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortB_scatter<BLK, CHUNK>),              \
-                "msm_lds_attrB" #BLK "_" #CHUNK);                                              \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<BLK, CHUNK>), dim3((unsigned)max_chunks), \
-                     dim3(BLK), smemB, bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL,     \
-                     chist, coff, entries);                                                    \
+  if (pfB) {                                                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<1024, 16384, true>), dim3(gridB),       \
+                       dim3(1024), smemB, bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL,  \
+                       chist, coff, entries, 3u * (uint32_t)NL);                               \
+  } else {                                                                                     \
+    sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortB_scatter<BLK, CHUNK, false>),     \
+                  "msm_lds_attrB" #BLK "_" #CHUNK);                                            \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<BLK, CHUNK, false>), dim3(gridB),       \
+                       dim3(BLK), smemB, bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL,   \
+                       chist, coff, entries, 0u);                                              \
+  }                                                                                            \
   QG_LAUNCH_CHECK()
       QG_SORT_DISPATCH_B(geo.blkB, chunk, QG_SORT_B_SCATTER);
 #undef QG_SORT_B_SCATTER
