@@ -564,7 +564,12 @@ int qg_trace_marker(qg_ctx* ctx, uint32_t tag);
  * (each was recomputed in stream order; 0 while the event ordering holds).
  * "open_checks": KZG quotients checked against p(sigma) - y == q(sigma)(sigma - x)
  * (kzg.rs:85); "open_check_failures": those that failed (each failing call
- * returned QG_ERR_ASSERT, "Polynomial division failed"). */
+ * returned QG_ERR_ASSERT, "Polynomial division failed").
+ * "events_created": HIP events the context created because its pool of
+ * returned events was empty (constant once a repeated workload is warm).
+ * "events_pooled": events resting in that pool now; created - pooled is the
+ * number in use, which a call leaves as it found it (an event that a failed
+ * call did not hand back shows here, long before the pool runs dry). */
 int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value);
 /* DensePolynomial::evaluate (pcs/src/kzg.rs:78) on a device vector:
  * out = sum_{i < n} poly[i] * x^(shift + i) (Montgomery in and out), by the

@@ -287,6 +287,8 @@ int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value) {
            : n == "msm_handover_violation" ? ctx->msm_handover_violation
            : n == "open_checks"            ? ctx->open_checks
            : n == "open_check_failures"    ? ctx->open_check_failures
+           : n == "events_created"         ? ctx->events_created
+           : n == "events_pooled"          ? ctx->event_pool.size()
                                            : 0;
   return QG_OK;
 }

@@ -12,14 +12,10 @@
 #include "../../include/quill_gpu.h"
 #include "arena.h"
 #include "curve.h"
+#include "error.h"
 #include "field.h"
 
 namespace qg {
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define QG_HIP(call)                                                                  \
   do {                                                                                \
@@ -27,11 +23,6 @@ struct Error : std::runtime_error {
     if (_e != hipSuccess)                                                             \
       throw ::qg::Error(_e == hipErrorOutOfMemory ? QG_ERR_OOM : QG_ERR_DEVICE,       \
                         std::string(#call) + ": " + hipGetErrorString(_e));           \
-  } while (0)
-
-#define QG_CHECK(cond, code, msg)                  \
-  do {                                             \
-    if (!(cond)) throw ::qg::Error((code), (msg)); \
   } while (0)
 
 // Launch-and-check helper: kernel errors surface at the call.
@@ -130,10 +121,16 @@ struct qg_ctx {
   uint64_t open_fault_value = 0;
 
   // every stream of this context, synchronized (scratch release, destroy)
-  static void drain_streams(void* self) {
-    qg_ctx* c = static_cast<qg_ctx*>(self);
-    for (hipStream_t s : {c->stream, c->copy_stream, c->side_stream, c->side_stream2})
-      if (s) QG_HIP(hipStreamSynchronize(s));
+  static void drain_streams(void* self) { QG_HIP(static_cast<qg_ctx*>(self)->drain_streams_quiet()); }
+  // the same without throwing (unwinding): every stream is synchronized, the
+  // first error is returned
+  hipError_t drain_streams_quiet() noexcept {
+    hipError_t first = hipSuccess;
+    for (hipStream_t s : {stream, copy_stream, side_stream, side_stream2}) {
+      const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+      if (first == hipSuccess) first = e;
+    }
+    return first;
   }
 
   int cus = 0;  // compute units of `device` (cached)
@@ -172,8 +169,10 @@ struct qg_ctx {
     }
     hipEvent_t e;
     QG_HIP(hipEventCreate(&e));
+    events_created++;
     return e;
   }
+  uint64_t events_created = 0;  // events ev_get had to create (the pool was empty)
   // begin/end a timed region on the context stream (or on stream s)
   int tbegin(const char* name, hipStream_t s = nullptr) {
     if (!timing) return -1;
@@ -238,6 +237,41 @@ struct qg_srs {
   // one-shot MSMs (qg_bases_upload), whose windows are summed by Horner steps
   int tables = 0;
   qg::MsmPt* d_table = nullptr;
+};
+
+// The cross-stream hand-over events one batch of work takes from the pool.
+// The caller releases them after the synchronization that ends the batch.
+// Destroyed unreleased (an error unwinds the batch), it first drains the
+// context's streams, ignoring their errors, so that no event returns to the
+// pool - and is recorded again - while a queued wait still refers to it.
+struct QgEvents {
+  qg_ctx* c;
+  std::vector<hipEvent_t> held;
+  explicit QgEvents(qg_ctx* ctx) : c(ctx) {}
+  QgEvents(const QgEvents&) = delete;
+  QgEvents& operator=(const QgEvents&) = delete;
+  hipEvent_t get() {
+    const hipEvent_t e = c->ev_get();
+    try {
+      held.push_back(e);
+    } catch (...) {  // not recorded yet: straight back to the pool
+      c->event_pool.push_back(e);
+      throw;
+    }
+    return e;
+  }
+  void release() {
+    c->event_pool.insert(c->event_pool.end(), held.begin(), held.end());
+    held.clear();
+  }
+  ~QgEvents() {
+    if (held.empty()) return;
+    (void)c->drain_streams_quiet();
+    try {
+      release();
+    } catch (...) {  // no memory for the pool's vector: the events are lost
+    }
+  }
 };
 
 // scoped timer

@@ -376,6 +376,85 @@ QG_HD X29 x29_add(const X29& p, const X29& q) {
   return {X3, Y3, mul29(mul29(p.ZZ, q.ZZ), PP), mul29(mul29(p.ZZZ, q.ZZZ), PPP)};
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// ---- quad-cooperative point arithmetic (latency-bound levels) -------------
+// Every lane of a quad (4 lanes) holds both operands; the field products of
+// one XYZZ addition / doubling are spread over the quad in dependent stages
+// and the stage results broadcast back with DPP quad permutes, so every lane
+// returns the full result.  Same formulas and operand bounds as x29_add /
+// x29_dbl (above): 4 product stages per addition instead of 14 products
+// in a row, 3 per doubling instead of 9.  micro/add_bench.hip: 4.1 us per
+// addition and 2.6 us per doubling on one wave (7.9 / 4.3 us single-lane),
+// for the short chains at the top of the reduction where lanes are idle.
+template <int S>
+__device__ __forceinline__ Q29 q29_quad(const Q29& a) {
+  Q29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+    r.l[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.l[i], S * 0x55, 0xf, 0xf, false);
+  return r;
+}
+
+__device__ __forceinline__ Q29 q29_sel(bool c, const Q29& a, const Q29& b) {
+  Q29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = c ? a.l[i] : b.l[i];
+  return r;
+}
+
+__device__ __forceinline__ X29 x29_sel(bool c, const X29& a, const X29& b) {
+  return {q29_sel(c, a.X, b.X), q29_sel(c, a.Y, b.Y), q29_sel(c, a.ZZ, b.ZZ), q29_sel(c, a.ZZZ, b.ZZZ)};
+}
+
+__device__ __forceinline__ X29 x29_add_q4(const X29& p, const X29& q) {
+  if (x29_is_inf(p)) return q;
+  if (x29_is_inf(q)) return p;
+  const uint32_t r = threadIdx.x & 3u;
+  const bool r0 = r == 0, r1 = r == 1, r2 = r == 2, odd = (r & 1u) != 0u;
+  // U1 = X1 ZZ2 | U2 = X2 ZZ1 | S1 = Y1 ZZZ2 | S2 = Y2 ZZZ1;  ZZ1 ZZ2 | ZZZ1 ZZZ2
+  const Q29 m0 = mul29(q29_sel(r0, p.X, q29_sel(r1, q.X, q29_sel(r2, p.Y, q.Y))),
+                       q29_sel(r0, q.ZZ, q29_sel(r1, p.ZZ, q29_sel(r2, q.ZZZ, p.ZZZ))));
+  const Q29 m1 = mul29(q29_sel(odd, p.ZZZ, p.ZZ), q29_sel(odd, q.ZZZ, q.ZZ));
+  const Q29 U1 = q29_quad<0>(m0), U2 = q29_quad<1>(m0), S1 = q29_quad<2>(m0), S2 = q29_quad<3>(m0);
+  const Q29 ZZ12 = q29_quad<0>(m1), ZZZ12 = q29_quad<1>(m1);
+  const Q29 P = normfull29(sub29(U2, U1));
+  const Q29 R = normfull29(sub29(S2, S1));
+  if (is_zero_mod29_fast<FqP, 8>(P)) return x29_add(p, q);  // doubling / cancellation (quad-uniform)
+  // PP = P^2 | RR = R^2
+  const Q29 sq = sqr29(q29_sel(odd, R, P));
+  const Q29 PP = q29_quad<0>(sq), RR = q29_quad<1>(sq);
+  // PPP = P PP | Q = U1 PP | ZZ3 = ZZ1 ZZ2 PP
+  const Q29 m3 = mul29(q29_sel(r0, P, q29_sel(r1, U1, ZZ12)), PP);
+  const Q29 PPP = q29_quad<0>(m3), Q = q29_quad<1>(m3), ZZ3 = q29_quad<2>(m3);
+  const Q29 X3 = red16p29(sub29(sub29(sub29(RR, PPP), Q), Q));
+  // Y3 = R (Q - X3) - S1 PPP | ZZZ3 = ZZZ1 ZZZ2 PPP (- 0 0)
+  const Q29 z = Q29::zero();
+  const Q29 m4 = red6p29(mulsub29(q29_sel(r0, R, ZZZ12), q29_sel(r0, norm29(sub29(Q, X3)), PPP),
+                                  q29_sel(r0, S1, z), q29_sel(r0, PPP, z)));
+  return {X3, q29_quad<0>(m4), ZZ3, q29_quad<1>(m4)};
+}
+
+__device__ __forceinline__ X29 x29_dbl_q4(const X29& p) {
+  if (x29_is_inf(p)) return p;
+  const uint32_t r = threadIdx.x & 3u;
+  const bool r0 = r == 0, r1 = r == 1, r2 = r == 2;
+  const Q29 U = normfull29(add29(p.Y, p.Y));
+  // V = U^2 | X2 = X^2
+  const Q29 s1 = sqr29(q29_sel((r & 1u) != 0u, p.X, U));
+  const Q29 V = q29_quad<0>(s1), X2 = q29_quad<1>(s1);
+  const Q29 M = normfull29(add29(add29(X2, X2), X2));
+  // W = U V | S = X V | ZZ3 = ZZ V | M^2
+  const Q29 m2 = mul29(q29_sel(r0, U, q29_sel(r1, p.X, q29_sel(r2, p.ZZ, M))), q29_sel(r < 3, V, M));
+  const Q29 W = q29_quad<0>(m2), S = q29_quad<1>(m2), ZZ3 = q29_quad<2>(m2), MM = q29_quad<3>(m2);
+  const Q29 X3 = red16p29(sub29(sub29(MM, S), S));
+  // Y3 = M (S - X3) - W Y | ZZZ3 = W ZZZ (- 0 0)
+  const Q29 z = Q29::zero();
+  const Q29 m3 = red6p29(mulsub29(q29_sel(r0, M, W), q29_sel(r0, norm29(sub29(S, X3)), p.ZZZ),
+                                  q29_sel(r0, W, z), q29_sel(r0, p.Y, z)));
+  return {X3, q29_quad<0>(m3), ZZ3, q29_quad<1>(m3)};
+}
+#endif
+
 QG_HD X29 x29_neg(const X29& p) {
   return {p.X, red6p29(sub29(Q29::zero(), p.Y)), p.ZZ, p.ZZZ};
 }

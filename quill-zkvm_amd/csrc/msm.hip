@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "curve29.h"
+#include "msm_plan.h"
 
 using namespace qg;
 
@@ -133,13 +134,9 @@ QG_DEV uint32_t xcd_tile(uint32_t b, uint32_t G) {
 // group (skewed scalars, the short top window) spreads over many blocks.
 // The block width of the pass-A scatter / rows kernels (BLK) and the block
 // width and chunk of the pass-B kernels (BLK, CHUNK) are template parameters;
-// msm_accumulate_phase picks an instantiation (sort_geometry below).
-static constexpr int SORT_BLOCK = 256;                      // k_sortA_hist, and the narrowest BLK
-static constexpr int SORT_TILE_MAX = 1024;                  // scalars per block (pass A)
-static constexpr size_t SORT_LDS_A = 72 * 1024;             // LDS budget for staged entries (2 blocks/CU)
-static constexpr int SORT_CHUNK = 8192;                     // entries per block (pass B), 256-thread blocks
-static constexpr int SORT_H_MAX = 1024, SORT_NL_MAX = 4096; // most groups / buckets per group
-static constexpr int SORT_ILP = 4;                          // LDS counter atomics in flight per thread (scatters)
+// msm_bucketing_launch picks an instantiation by the plan's geometry
+// (sort_geometry, msm_plan.h, which also has SORT_BLOCK and the other limits).
+static constexpr int SORT_ILP = 4;                         // LDS counter atomics in flight per thread (scatters)
 
 // ---- cross-stream hand-over guard (msm_device_batch) ----------------------
 // A batch on the side streams hands data over by events only: the scalars
@@ -758,11 +755,7 @@ __global__ void k_scan32_add(const uint32_t* __restrict__ tile_off, size_t n, ui
 }
 
 // ---- exclusive scan of (count, ceil(count/E)) over nb buckets -------------
-static constexpr int SCAN_PER_THREAD = 8;
-static constexpr int SCAN_BLOCK = 256;
-static constexpr int SCAN_TILE = SCAN_PER_THREAD * SCAN_BLOCK;
-
-// entries per accumulation thread = L (chosen per call, msm_accumulate_phase)
+// entries per accumulation thread = L (chosen per call, msm_plan)
 __device__ __forceinline__ uint2 scan_val(const uint32_t* counts, size_t i, size_t nb, uint32_t L) {
   uint32_t c = i < nb ? counts[i] : 0u;
   return make_uint2(c, (c + L - 1) / L);
@@ -1070,9 +1063,6 @@ __device__ __forceinline__ bool msm_coop_read(const uint4* wbuf, uint32_t lane, 
 }
 #endif
 
-#ifndef QG_COOP_WPE
-#define QG_COOP_WPE 3
-#endif
 __global__ void __launch_bounds__(MSM_BLOCK) __attribute__((amdgpu_waves_per_eu(QG_COOP_WPE)))
     k_msm_accumulate_coop(const MsmPt* __restrict__ table, const uint32_t* __restrict__ entries,
                           const uint32_t* __restrict__ bstart, uint32_t nb, uint32_t L, uint64_t Lm,
@@ -1244,83 +1234,7 @@ __device__ __forceinline__ X29 x29_shfl_down(const X29& p, uint32_t d, int width
           q29_shfl_down(p.ZZ, d, width), q29_shfl_down(p.ZZZ, d, width)};
 }
 
-// ---- quad-cooperative point arithmetic (latency-bound levels) -------------
-// Every lane of a quad (4 lanes) holds both operands; the field products of
-// one XYZZ addition / doubling are spread over the quad in dependent stages
-// and the stage results broadcast back with DPP quad permutes, so every lane
-// returns the full result.  Same formulas and operand bounds as x29_add /
-// x29_dbl (curve29.h): 4 product stages per addition instead of 14 products
-// in a row, 3 per doubling instead of 9.  micro/add_bench.hip: 4.1 us per
-// addition and 2.6 us per doubling on one wave (7.9 / 4.3 us single-lane),
-// for the short chains at the top of the reduction where lanes are idle.
-template <int S>
-__device__ __forceinline__ Q29 q29_quad(const Q29& a) {
-  Q29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-    r.l[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.l[i], S * 0x55, 0xf, 0xf, false);
-  return r;
-}
-
-__device__ __forceinline__ Q29 q29_sel(bool c, const Q29& a, const Q29& b) {
-  Q29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = c ? a.l[i] : b.l[i];
-  return r;
-}
-
-__device__ __forceinline__ X29 x29_sel(bool c, const X29& a, const X29& b) {
-  return {q29_sel(c, a.X, b.X), q29_sel(c, a.Y, b.Y), q29_sel(c, a.ZZ, b.ZZ), q29_sel(c, a.ZZZ, b.ZZZ)};
-}
-
-__device__ __forceinline__ X29 x29_add_q4(const X29& p, const X29& q) {
-  if (x29_is_inf(p)) return q;
-  if (x29_is_inf(q)) return p;
-  const uint32_t r = threadIdx.x & 3u;
-  const bool r0 = r == 0, r1 = r == 1, r2 = r == 2, odd = (r & 1u) != 0u;
-  // U1 = X1 ZZ2 | U2 = X2 ZZ1 | S1 = Y1 ZZZ2 | S2 = Y2 ZZZ1;  ZZ1 ZZ2 | ZZZ1 ZZZ2
-  const Q29 m0 = mul29(q29_sel(r0, p.X, q29_sel(r1, q.X, q29_sel(r2, p.Y, q.Y))),
-                       q29_sel(r0, q.ZZ, q29_sel(r1, p.ZZ, q29_sel(r2, q.ZZZ, p.ZZZ))));
-  const Q29 m1 = mul29(q29_sel(odd, p.ZZZ, p.ZZ), q29_sel(odd, q.ZZZ, q.ZZ));
-  const Q29 U1 = q29_quad<0>(m0), U2 = q29_quad<1>(m0), S1 = q29_quad<2>(m0), S2 = q29_quad<3>(m0);
-  const Q29 ZZ12 = q29_quad<0>(m1), ZZZ12 = q29_quad<1>(m1);
-  const Q29 P = normfull29(sub29(U2, U1));
-  const Q29 R = normfull29(sub29(S2, S1));
-  if (is_zero_mod29_fast<FqP, 8>(P)) return x29_add(p, q);  // doubling / cancellation (quad-uniform)
-  // PP = P^2 | RR = R^2
-  const Q29 sq = sqr29(q29_sel(odd, R, P));
-  const Q29 PP = q29_quad<0>(sq), RR = q29_quad<1>(sq);
-  // PPP = P PP | Q = U1 PP | ZZ3 = ZZ1 ZZ2 PP
-  const Q29 m3 = mul29(q29_sel(r0, P, q29_sel(r1, U1, ZZ12)), PP);
-  const Q29 PPP = q29_quad<0>(m3), Q = q29_quad<1>(m3), ZZ3 = q29_quad<2>(m3);
-  const Q29 X3 = red16p29(sub29(sub29(sub29(RR, PPP), Q), Q));
-  // Y3 = R (Q - X3) - S1 PPP | ZZZ3 = ZZZ1 ZZZ2 PPP (- 0 0)
-  const Q29 z = Q29::zero();
-  const Q29 m4 = red6p29(mulsub29(q29_sel(r0, R, ZZZ12), q29_sel(r0, norm29(sub29(Q, X3)), PPP),
-                                  q29_sel(r0, S1, z), q29_sel(r0, PPP, z)));
-  return {X3, q29_quad<0>(m4), ZZ3, q29_quad<1>(m4)};
-}
-
-__device__ __forceinline__ X29 x29_dbl_q4(const X29& p) {
-  if (x29_is_inf(p)) return p;
-  const uint32_t r = threadIdx.x & 3u;
-  const bool r0 = r == 0, r1 = r == 1, r2 = r == 2;
-  const Q29 U = normfull29(add29(p.Y, p.Y));
-  // V = U^2 | X2 = X^2
-  const Q29 s1 = sqr29(q29_sel((r & 1u) != 0u, p.X, U));
-  const Q29 V = q29_quad<0>(s1), X2 = q29_quad<1>(s1);
-  const Q29 M = normfull29(add29(add29(X2, X2), X2));
-  // W = U V | S = X V | ZZ3 = ZZ V | M^2
-  const Q29 m2 = mul29(q29_sel(r0, U, q29_sel(r1, p.X, q29_sel(r2, p.ZZ, M))), q29_sel(r < 3, V, M));
-  const Q29 W = q29_quad<0>(m2), S = q29_quad<1>(m2), ZZ3 = q29_quad<2>(m2), MM = q29_quad<3>(m2);
-  const Q29 X3 = red16p29(sub29(sub29(MM, S), S));
-  // Y3 = M (S - X3) - W Y | ZZZ3 = W ZZZ (- 0 0)
-  const Q29 z = Q29::zero();
-  const Q29 m3 = red6p29(mulsub29(q29_sel(r0, M, W), q29_sel(r0, norm29(sub29(S, X3)), p.ZZZ),
-                                  q29_sel(r0, W, z), q29_sel(r0, p.Y, z)));
-  return {X3, q29_quad<0>(m3), ZZ3, q29_quad<1>(m3)};
-}
-
+// (x29_add_q4 / x29_dbl_q4, the quad-cooperative point arithmetic: curve29.h)
 template <bool Q4>
 __device__ __forceinline__ X29 red_add(const X29& a, const X29& b) {
   if constexpr (Q4) return x29_add_q4(a, b);
@@ -1638,453 +1552,381 @@ struct MsmRun {
   // misc[1..3] copied to pinned host memory right after the bucket scan, and
   // its event: the reduction's launch plan waits for the bucketing only, so
   // its kernels are queued while the accumulation still runs
-  const uint32_t* h_mx = nullptr;
+  // (the event belongs to the QgEvents guard of the batch that made the run)
+  uint32_t* h_mx = nullptr;
   hipEvent_t ev_mx = nullptr;
   uint32_t gen = 0;  // misc[4] of this run: h_mx[3] must equal it
 };
 static constexpr int MSM_MAX_BATCH = 1024;
 
-// Launch geometry of the sort kernels: pass A's scatter / rows kernels run
-// blkA threads over a tile of `tile` scalars, pass B's kernels blkB threads
-// over a chunk of `chunk` entries.  Only the instantiated pairs are valid:
-//   pass A: 256 threads with any tile, 512 with tile 512 / 1024, 1024 with 1024
-//   pass B: (256, 8192), (512, 8192), (512, 16384), (1024, 16384)
-// gridA / gridB: blocks of the two scatter kernels.  0: one per tile / chunk;
-// -1: the default, which is that too except for the wide class, whose blocks
-// walk several tiles each (sort_scatter_grid)
-struct SortGeom {
-  uint32_t blkA, tile, blkB, chunk;
-  int gridA, gridB;
-  bool wide;
+// One MSM for msm_accumulate_phase: sum_i d_scalars[i] * base[srs_off + i],
+// MSM `slot` of its batch.
+//
+// stream: the stream this MSM runs on.  Null or ctx->stream: everything in
+// stream order.  A side stream (msm_device_batch, QG_MSM_PIPE=1): the caller
+// has made it wait for the scalars; bucketing and accumulation both queue on
+// it, with their own copies of the shared bucketing scratch and entry list,
+// so the next MSM's bucketing - memory-bound radix passes - runs on the other
+// side stream beside this accumulation (VALU-bound, leaving a wave slot and
+// LDS per CU free), and every MSM's data flows within one queue.
+// hv / hgen: the hand-over guard words of such a batch (k_sortA_hist).
+// wsel >= 0: the digits of window wsel only, over the one table of one-shot
+// bases (msm_oneshot_local); -1: every window over the window-shifted tables.
+// canon_ready: an earlier window of the same scalars left the canonical
+// scalars in the (per-stream) canon scratch.
+struct MsmJob {
+  const Fr* d_scalars = nullptr;
+  size_t n = 0;
+  int slot = 0;
+  size_t srs_off = 0;
+  hipStream_t stream = nullptr;
+  uint32_t* hv = nullptr;
+  uint32_t hgen = 0;
+  int wsel = -1;
+  bool canon_ready = false;
 };
 
-// The default by the MSM's entries (profiles/r08_sort_block_ab.txt; bucketing
-// ms with 256- / 512- / 1024-thread blocks, the last over tile 1024 and chunk
-// 16384): 2^26 entries and more take 1024 threads (13 x 2^24: 2.41 / 2.20 /
-// 2.02, 13 x 2^23: 1.26 / 1.13 / 1.06), 2^20 and more 512 threads over the same
-// tile and chunk as before (13 x 2^22: 0.674 / 0.576 / 0.587, 15 x 2^20 at
-// c = 17: 0.200 / 0.174 / 0.192, 17 x 2^16: 0.088 / 0.079 / 0.087), fewer keep
-// 256 (24 x 2^12: 0.076 / 0.078).  QG_SORT_BLOCK_A / QG_SORT_TILE /
-// QG_SORT_BLOCK_B / QG_SORT_CHUNK override (A/B runs); a combination without
-// an instantiation is QG_ERR_INVALID.  QG_SORT_GRID_A / QG_SORT_GRID_B force
-// the scatters' block counts (0 = one block per tile / chunk; any count up to
-// SORT_GRID_MAX runs, a multiple of 8 keeps a block's tiles on one XCD; blocks
-// beyond the tile count exit at once); out of range is QG_ERR_INVALID.
-// side: an MSM of a batch on the side streams, whose bucketing runs beside the
-// other stream's accumulation, keeps 256 threads: with the wider blocks
-// HyperPlonk's side bucketing gained 1-4 ms per proof and the accumulation
-// beside it lost 24-34 ms (proof 848-854 -> 870-872 ms).  The windows of
-// one-shot bases (wsel >= 0) keep it too: 2^20 bases measured 1.93 -> 1.85 ms of
-// bucketing with 512 threads, but the 2^24 bench leg 27.3 -> 27.4-27.6 ms.
-static constexpr size_t SORT_WIDE_MIN = (size_t)1 << 26;
-static constexpr size_t SORT_MID_MIN = (size_t)1 << 20;
-static constexpr int SORT_GRID_MAX = 1 << 20;
-static int sort_grid_override(const char* ov) {
-  char* end = nullptr;
-  const long v = strtol(ov, &end, 10);
-  QG_CHECK(end != ov && *end == 0 && v >= 0 && v <= SORT_GRID_MAX, QG_ERR_INVALID,
-           "QG_SORT_GRID_A / QG_SORT_GRID_B must be a block count in [0, 2^20]");
-  return (int)v;
+static bool msm_on_side_stream(const qg_ctx* ctx, const MsmJob& job) {
+  return job.stream != nullptr && job.stream != ctx->stream;
 }
-static SortGeom sort_geometry(size_t max_entries, int WE, bool narrow) {
-  SortGeom g;
-  const bool wide = !narrow && max_entries >= SORT_WIDE_MIN;
-  const bool mid = !narrow && max_entries >= SORT_MID_MIN;
-  g.blkA = wide ? 1024 : mid ? 512 : SORT_BLOCK;
-  g.blkB = wide ? 1024 : mid ? 512 : SORT_BLOCK;
-  g.chunk = wide ? 16384 : SORT_CHUNK;
-  g.wide = wide;
-  g.gridA = g.gridB = -1;
-  // a block stages at least one scalar per thread: with many windows (small c)
-  // the wide tile does not fit the CU's LDS, and the default steps down
-  while (g.blkA > (uint32_t)SORT_BLOCK &&
-         (size_t)g.blkA * WE * 8 + (3 * (size_t)SORT_H_MAX + 16) * 4 > 160 * 1024)
-    g.blkA >>= 1;
-  if (const char* ov = getenv("QG_SORT_BLOCK_A")) g.blkA = (uint32_t)atoi(ov);
-  if (const char* ov = getenv("QG_SORT_BLOCK_B")) g.blkB = (uint32_t)atoi(ov);
-  if (const char* ov = getenv("QG_SORT_CHUNK")) g.chunk = (uint32_t)atoi(ov);
-  if (const char* ov = getenv("QG_SORT_GRID_A")) g.gridA = sort_grid_override(ov);
-  if (const char* ov = getenv("QG_SORT_GRID_B")) g.gridB = sort_grid_override(ov);
-  // pass-A tile: as many scalars as fit their WE digits (8 B each) in the LDS
-  // budget of 256-thread blocks; a wider block takes at least its own width
-  g.tile = SORT_TILE_MAX;
-  while (g.tile > 64 && (size_t)g.tile * WE * 8 > SORT_LDS_A) g.tile >>= 1;
-  if (g.blkA > SORT_BLOCK && g.blkA <= (uint32_t)SORT_TILE_MAX) g.tile = std::max(g.tile, g.blkA);
-  if (const char* ov = getenv("QG_SORT_TILE")) g.tile = (uint32_t)atoi(ov);
-  QG_CHECK(g.tile >= 64 && g.tile <= (uint32_t)SORT_TILE_MAX && (g.tile & (g.tile - 1)) == 0,
-           QG_ERR_INVALID, "QG_SORT_TILE must be a power of two in [64, 1024]");
-  QG_CHECK(g.blkA == 256 || ((g.blkA == 512 || g.blkA == 1024) && g.tile >= g.blkA),
-           QG_ERR_INVALID, "no pass-A sort kernel for this QG_SORT_BLOCK_A / QG_SORT_TILE");
-  QG_CHECK((g.blkB == 256 && g.chunk == 8192) || (g.blkB == 512 && g.chunk == 8192) ||
-               (g.blkB == 512 && g.chunk == 16384) || (g.blkB == 1024 && g.chunk == 16384),
-           QG_ERR_INVALID, "no pass-B sort kernel for this QG_SORT_BLOCK_B / QG_SORT_CHUNK");
-  return g;
+
+// One scatter instantiation: the kernel and the stem of its memo keys
+struct SortFn {
+  const void* fn;
+  std::string key;
+};
+template <int BLK, bool PF>
+static SortFn sortA_fn() {
+  return {reinterpret_cast<const void*>(&k_sortA_scatter<BLK, PF>),
+          "msm_sortA" + std::to_string(BLK) + (PF ? "pf" : "")};
+}
+template <int BLK, int CHUNK, bool PF>
+static SortFn sortB_fn() {
+  return {reinterpret_cast<const void*>(&k_sortB_scatter<BLK, CHUNK, PF>),
+          "msm_sortB" + std::to_string(BLK) + "_" + std::to_string(CHUNK) + (PF ? "pf" : "")};
 }
 
 // the > 64 KiB dynamic-LDS attribute of one kernel instantiation, once per
 // context (= per device and per calling thread: a context is used by one
 // thread at a time); every instantiation has its own memo key
-static void sort_lds_attr(qg_ctx* ctx, const void* fn, const std::string& key) {
+static void sort_lds_attr(qg_ctx* ctx, const SortFn& f) {
+  const std::string key = f.key + "_lds";
   if (ctx->memo.count(key)) return;
-  QG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  QG_HIP(hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   ctx->memo[key] = "1";
 }
 
-// Blocks of a scatter kernel.  forced > 0: that many; 0: one per tile.  The
-// default (-1) is one per tile too, except where `multi` (the wide class with
-// the prefetching instantiation): SORT_GRID_ROUNDS times the blocks the device
-// holds at once (the kernel's occupancy at this LDS size x CUs), a multiple
-// of 8 so that a block's tiles stay in one XCD's range, at most one per tile.
-// Exactly the resident count measured no better than one block per tile
-// (2^24 bucketing 2.02 ms both; the slowest CU sets the time), 4 and 8 rounds
-// of blocks, which the dispatcher hands to whichever CU is free, 1.93 / 1.90
-// (profiles/r09_sort_pipeline_ab.txt).
-static constexpr size_t SORT_GRID_ROUNDS = 8;
-static uint32_t sort_scatter_grid(qg_ctx* ctx, const void* fn, const std::string& key, int blk,
-                                  size_t smem, int forced, bool multi, size_t count) {
-  if (forced > 0) return (uint32_t)forced;
-  if (forced == 0 || !multi) return (uint32_t)count;
-  const std::string mk = key + "_occ" + std::to_string(smem);
+// msm_plan's question to the device: resident blocks per CU of the
+// prefetching scatter of pass 'A' / 'B' at this LDS size (memoized)
+static int sort_pf_occupancy(qg_ctx* ctx, char pass, int blk, size_t smem) {
+  QG_CHECK(blk == 1024, QG_ERR_ASSERT, "the prefetching scatters have 1024 threads");
+  const SortFn f = pass == 'A' ? sortA_fn<1024, true>() : sortB_fn<1024, 16384, true>();
+  sort_lds_attr(ctx, f);
+  const std::string mk = f.key + "_occ" + std::to_string(smem);
   auto it = ctx->memo.find(mk);
+  if (it != ctx->memo.end()) return std::stoi(it->second);
   int occ = 0;
-  if (it == ctx->memo.end()) {
-    QG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, blk, smem));
-    ctx->memo[mk] = std::to_string(occ);
-  } else {
-    occ = std::stoi(it->second);
-  }
-  QG_CHECK(occ >= 1, QG_ERR_DEVICE, "sort scatter kernel cannot be resident");
-  const size_t blocks = (((size_t)occ * ctx->num_cus()) & ~(size_t)7) * SORT_GRID_ROUNDS;
-  return (uint32_t)(blocks >= 8 && blocks < count ? blocks : count);
+  QG_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, f.fn, blk, smem));
+  ctx->memo[mk] = std::to_string(occ);
+  return occ;
 }
 
-// QG_SORT_DISPATCH_A(blk, F): F(BLK) for the instantiated pass-A block width;
-// QG_SORT_DISPATCH_B(blk, chunk, F): F(BLK, CHUNK) for the pass-B pair
-#define QG_SORT_DISPATCH_A(blk, F) \
-  do {                             \
-    if ((blk) == 256) { F(256); }  \
-    else if ((blk) == 512) { F(512); } \
-    else { F(1024); }              \
-  } while (0)
-#define QG_SORT_DISPATCH_B(blk, chunk, F)                   \
-  do {                                                      \
-    if ((blk) == 256) { F(256, 8192); }                     \
-    else if ((blk) == 512 && (chunk) == 8192) { F(512, 8192); } \
-    else if ((blk) == 512) { F(512, 16384); }               \
-    else { F(1024, 16384); }                                \
-  } while (0)
+// The plan of `job` over `srs`, after the checks of the job against the SRS.
+// The overrides are read here, once per MSM.
+static MsmPlan msm_job_plan(qg_ctx* ctx, const qg_srs* srs, const MsmJob& job) {
+  const int W = srs->W, wsel = job.wsel;
+  QG_CHECK((wsel < 0) == (srs->tables == W) && wsel < W, QG_ERR_INVALID,
+           "MSM window selection does not match the SRS tables");
+  QG_CHECK((size_t)W * srs->n < 0x80000000ull, QG_ERR_UNSUPPORTED, "SRS table index overflow");
+  QG_CHECK(job.slot >= 0 && job.slot < MSM_MAX_BATCH, QG_ERR_UNSUPPORTED, "MSM batch too large");
+  MsmShape sh;
+  sh.n = job.n;
+  sh.c = srs->c;
+  sh.W = W;
+  sh.wsel = wsel;
+  sh.side = msm_on_side_stream(ctx, job);
+  sh.cus = ctx->num_cus();
+  return msm_plan(sh, msm_tuning_from_env(), [ctx](char pass, int blk, size_t smem) {
+    return sort_pf_occupancy(ctx, pass, blk, smem);
+  });
+}
 
-// bucketing (two-pass radix sort) + bucket accumulation of MSM `slot` of a
-// batch: sum_i d_scalars[i] * base[srs_off + i]
-//
-// bst: the stream this MSM runs on.  ctx->stream (default): everything in
-// stream order.  A side stream (msm_device_batch, QG_MSM_PIPE=1): the caller
-// has made bst wait for the scalars; bucketing and accumulation both queue on
-// bst, with their own copies of the shared bucketing scratch and entry list,
-// so the next MSM's bucketing - memory-bound radix passes - runs on the other
-// side stream beside this accumulation (VALU-bound, leaving a wave slot and
-// LDS per CU free), and every MSM's data flows within one queue.
-// reserve: only size the shared bucketing scratch and the entry list (of the
-// stream `slot` selects) for an MSM of length n, launching nothing.  A batch
-// reserves for its longest MSM first: a slot that grew in the middle of a
-// batch would be freed while an earlier MSM's kernels still read it.
-// wsel >= 0: the digits of window wsel only, over the one table of one-shot
-// bases (msm_oneshot_local); -1: every window over the window-shifted tables
-static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const Fr* d_scalars, size_t n,
-                                   int slot, size_t srs_off = 0, hipStream_t bst = nullptr,
-                                   bool reserve = false, uint32_t* hv = nullptr, uint32_t hgen = 0,
-                                   int wsel = -1, bool canon_ready = false) {
-  QG_CHECK(srs_off <= srs->n && n <= srs->n - srs_off, QG_ERR_INVALID, "MSM length exceeds the SRS");
-  MsmRun run;
+// The device scratch of one MSM run.
+struct MsmScratch {
+  uint32_t *ghist, *goff, *gtiles, *gstart, *cbase, *cgroup;
+  uint32_t* misc;  // [0] nchunks, [1] max tpb
+  uint32_t *chist, *coff, *tmp_e;
+  uint16_t* tmp_l;
+  uint32_t *hrow, *orow;
+  Fr* canon;
+  uint32_t *counts, *bstart, *entries;
+  uint2* tile_tot;
+  X29Raw* partial;
+  uint32_t* owner;
+};
+
+// The slot list: "@p" slots are the shared bucketing scratch and the entry
+// list, one copy per stream (side mode: this MSM's bucketing AND accumulation
+// run on one of two side streams by MSM parity, so each MSM's data flows
+// within one queue); "#slot" slots belong to one MSM of the batch.
+// RESERVED slots are the ones msm_reserve sizes before a batch (run = false
+// touches only those); RUN_ONLY slots are sized by each run alone.
+static MsmScratch msm_scratch(qg_ctx* ctx, const MsmPlan& p, size_t n, int slot, bool side,
+                              bool run) {
   const std::string sfx = "#" + std::to_string(slot);
-  const bool side = bst != nullptr && bst != ctx->stream;
-  if (!bst) bst = ctx->stream;
-  // side mode: this MSM's bucketing AND accumulation run on bst, one of two
-  // side streams by MSM parity, so each MSM's data flows within one queue;
-  // the shared bucketing scratch and the entry list are per stream
   const std::string tg = side ? "@" + std::to_string(slot & 1) : std::string();
-  if (n > 0) {
-    const int c = srs->c, W = srs->W;
-    QG_CHECK((wsel < 0) == (srs->tables == W) && wsel < W, QG_ERR_INVALID,
-             "MSM window selection does not match the SRS tables");
-    const int WE = wsel < 0 ? W : 1;  // digits per scalar this run bins
-    const uint32_t nb = 1u << (c - 1);
-    const size_t max_entries = n * (size_t)WE;
-    QG_CHECK((size_t)W * srs->n < 0x80000000ull, QG_ERR_UNSUPPORTED, "SRS table index overflow");
-    QG_CHECK(max_entries < 0xffffffffull, QG_ERR_UNSUPPORTED, "too many MSM entries");
-    // bucket id b = (g << LO) | l
-    const int BB = c - 1, LO = (BB + 1) / 2, HI = BB - LO;
-    const int H = 1 << HI, NL = 1 << LO;
-    const SortGeom geo = sort_geometry(max_entries, WE, side || wsel >= 0);
-    const uint32_t tile = geo.tile, chunk = geo.chunk;
-    const uint32_t nblk = div_up(n, tile);
-    const size_t nghist = (size_t)H * nblk;
-    const size_t max_chunks = max_entries / chunk + H + 1;
-    uint32_t* ghist = ctx->scratch_as<uint32_t>("msm_ghist" + tg, nghist + 1);
-    uint32_t* goff = ctx->scratch_as<uint32_t>("msm_goff" + tg, nghist + 1);
-    uint32_t* gtiles = ctx->scratch_as<uint32_t>("msm_gtiles" + tg, div_up(nghist, 2048) + 1);
-    uint32_t* gstart = ctx->scratch_as<uint32_t>("msm_gstart" + tg, H + 1);
-    uint32_t* cbase = ctx->scratch_as<uint32_t>("msm_cbase" + tg, H + 1);
-    uint32_t* cgroup = ctx->scratch_as<uint32_t>("msm_cgroup" + tg, max_chunks);
-    uint32_t* misc = ctx->scratch_as<uint32_t>("msm_misc" + sfx, 5);  // [0] nchunks, [1] max tpb
-    uint32_t* chist = ctx->scratch_as<uint32_t>("msm_chist" + tg, max_chunks * NL);
-    uint32_t* coff = ctx->scratch_as<uint32_t>("msm_coff" + tg, max_chunks * NL);
-    uint32_t* tmp_e = ctx->scratch_as<uint32_t>("msm_tmp_e" + tg, max_entries + 1);
-    uint16_t* tmp_l = ctx->scratch_as<uint16_t>("msm_tmp_l" + tg, max_entries + 1);
-    uint32_t* hrow = ctx->scratch_as<uint32_t>("msm_hrow" + tg, nghist + 1);
-    uint32_t* orow = ctx->scratch_as<uint32_t>("msm_orow" + tg, nghist + 1);
-    Fr* canon = ctx->scratch_as<Fr>("msm_canon" + tg, n);
-    uint32_t* counts = ctx->scratch_as<uint32_t>("msm_counts" + tg, nb);
-    uint32_t* bstart = ctx->scratch_as<uint32_t>("msm_bstart" + sfx, nb + 1);
-    uint32_t* entries = ctx->scratch_as<uint32_t>("msm_entries" + tg, max_entries + 1);
-    if (reserve) return run;
-    const int ntiles = (int)div_up(nb, SCAN_TILE);
-    uint2* tile_tot = ctx->scratch_as<uint2>("msm_tiles" + tg, ntiles);
-    // entries per accumulation thread (flat chunks, k_msm_accumulate): 64, or
-    // 128 for the largest MSMs, fewer while that would leave < 3 waves of
-    // threads per resident slot (256 CUs x 16 waves).  Measured against equal
-    // splits into 1 / 2 / 3 whole waves of the chip (QG_MSM_ROUNDS, which also
-    // leave fewer partials for the reduction): the accumulate loses 0.3-0.5 ms
-    // at 2^24 with 1-2 waves, and 3 waves is no faster than 128 entries.
-    uint32_t L;
-    if (const char* ov = getenv("QG_MSM_ROUNDS")) {  // tuning experiments
-      const int rounds = atoi(ov);
-      QG_CHECK(rounds >= 1 && rounds <= 64, QG_ERR_INVALID, "QG_MSM_ROUNDS out of range");
-      const size_t resident = (size_t)ctx->num_cus() * 16 * 64;
-      L = 4;  // a power of two (k_msm_accumulate takes log2 L), rounded up
-      while ((size_t)L * resident * rounds < max_entries) L <<= 1;
-    } else {
-      int elog = max_entries >= ((size_t)1 << 27) ? 7 : 6;
-      while (elog > 2 && (max_entries >> elog) < (size_t)ctx->num_cus() * 16 * 64 * 3) elog--;
-      // but at most ~4 chunks per bucket: below that the reduction's slot
-      // merges cost more than the accumulation gains from the extra threads
-      // (own-SRS MSMs, profiles/r04_msm_small_elog.txt: 2^20 / 2^18 / 2^16 at
-      // c = 17 / 16 / 15 take 1.73 / 1.09 / 0.73 ms with the thread rule alone,
-      // 1.69 / 0.87 / 0.69 ms with 64 / 32 / 32 entries per chunk)
-      // In a batch on the side streams (HyperPlonk's openings: 2^20-2^23-scalar
-      // MSMs on the c = 20 tables, many buckets per MSM) at most ~2 chunks per
-      // bucket: fewer partial slots to merge, HyperPlonk reduce 73.5 / 73.9 ->
-      // 63.5 / 63.3 ms per proof, proof 879.7 / 878.3 -> 872.0 / 871.7 ms
-      // (profiles/r06e_msm_cpb_ab.txt); a lone MSM keeps 4 (the 2^24 headline
-      // measured no better with 2).  QG_MSM_CPB overrides (A/B runs).
-      int emin = 0;
-      size_t cpb = side ? 2 : 4;
-      if (const char* ov = getenv("QG_MSM_CPB")) cpb = (size_t)std::max(1, atoi(ov));
-      while (emin < 7 && ((size_t)1 << emin) * cpb * nb < max_entries) emin++;
-      elog = std::max(elog, emin);
-      L = 1u << elog;
-    }
-    if (const char* ov = getenv("QG_MSM_ELOG")) L = 1u << atoi(ov);  // tuning experiments
-    // the accumulate form (below) and its resident waves per SIMD
-    bool pf = max_entries >= ((size_t)1 << 27);
-    if (const char* ov = getenv("QG_MSM_PF")) pf = atoi(ov) != 0;
-    bool coop = max_entries >= ((size_t)1 << 25);
-    if (const char* ov = getenv("QG_MSM_COOP")) coop = atoi(ov) != 0;
-    // Equal chunks (any multiple of 4 entries) filling exactly k rounds of the
-    // chip's resident waves: no partly-filled last round, and fewer, longer
-    // chunks leave fewer partial slots per bucket for the reduction.  The MSMs
-    // of a side-stream batch take k = 1: HyperPlonk 866.9 / 870.6 -> 847.1 /
-    // 850.5 ms per proof, its reduce 63.3 -> 52.1 ms (the accumulate itself
-    // slower, the other stream's bucketing beside it faster), 2^24 headline
-    // unchanged (profiles/r06g_msm_eqsplit_ab.txt).  A lone MSM keeps the
-    // power-of-two rule: with k = 1 / 2 / 3 the 2^24 accumulate is 1.4 / 0.7 /
-    // 0.5 ms slower for a reduction 0.20 / 0.10 / 0.18 ms faster (the waves of
-    // one round do not finish together; many rounds even them out).
-    // QG_MSM_EQSPLIT=k overrides (0: the power-of-two rule; A/B runs).
-    int eqk = side ? 1 : 0;
-    if (const char* ov = getenv("QG_MSM_EQSPLIT")) eqk = atoi(ov);
-    {
-      const int k = eqk;
-      if (k > 0) {
-        const size_t wpe = coop ? QG_COOP_WPE : (pf ? 3 : 4);
-        const size_t resident = (size_t)ctx->num_cus() * 4 * wpe * 64;
-        const size_t lq = (div_up(max_entries, resident * (size_t)k) + 3) & ~(size_t)3;
-        L = (uint32_t)std::max<size_t>(4, lq);
-      }
-    }
-    // partial slots a bucket's sum adds in a row in the reduction: the typical
-    // count + 1 (a bucket of c entries spans ceil(c / L) or one more slots);
-    // skewed buckets beyond it are pre-summed by tree steps
-    const uint32_t T = std::max<uint32_t>(4, (uint32_t)div_up(div_up(max_entries, nb), L) + 2);
-    // k_msm_accumulate takes the group phase of entry e as e & 3: chunks start
-    // at multiples of 4
-    QG_CHECK(L >= 4 && L <= 65536 && (L & 3u) == 0, QG_ERR_INVALID, "MSM chunk length out of range");
-    const uint64_t Lm = ~0ull / L + 1;  // msm_chunk_of's multiplier
-    const size_t max_threads = div_up(max_entries, L);
-    const size_t nslots = max_threads + nb + 1;  // partial slot of (thread t, bucket b): t + b
-    X29Raw* partial = ctx->scratch_as<X29Raw>("msm_partial" + sfx, nslots);
-    uint32_t* owner = ctx->scratch_as<uint32_t>("msm_owner" + sfx, nslots);
-    QG_CHECK(ntiles <= 1024 * 64 && H <= SORT_H_MAX && NL <= SORT_NL_MAX, QG_ERR_UNSUPPORTED,
-             "bucket count too large");
-    // dynamic LDS of the two scatters: staged entries, three count / offset
-    // rows, the scan's wave totals
-    size_t smemA = (size_t)tile * WE * 8 + (3 * (size_t)H + geo.blkA / 64) * 4;
-    size_t smemB = (size_t)chunk * 6 + (3 * (size_t)NL + geo.blkB / 64) * 4;
-    QG_CHECK(smemA <= 160 * 1024 && smemB <= 160 * 1024, QG_ERR_UNSUPPORTED,
-             "sort tile / chunk exceeds LDS");
-    // The scatters' grids.  Fewer blocks than tiles / chunks: the 1024-thread
-    // kernels prefetch the next tile (a second row buffer in LDS, where it
-    // fits); the narrower ones walk their tiles without (no measured case for
-    // them).
-    const void* fnA = reinterpret_cast<const void*>(&k_sortA_scatter<1024, true>);
-    const void* fnB = reinterpret_cast<const void*>(&k_sortB_scatter<1024, 16384, true>);
-    const size_t smemA2 = smemA + 3 * (size_t)H * 4, smemB2 = smemB + 3 * (size_t)NL * 4;
-    const bool canA = geo.blkA == 1024 && smemA2 <= 160 * 1024;
-    const bool canB = geo.blkB == 1024 && smemB2 <= 160 * 1024;
-    if (canA) sort_lds_attr(ctx, fnA, "msm_lds_attrA1024pf");
-    if (canB) sort_lds_attr(ctx, fnB, "msm_lds_attrB1024_16384pf");
-    const uint32_t gridA = sort_scatter_grid(ctx, fnA, "msm_sortA1024pf", 1024, smemA2, geo.gridA,
-                                             geo.wide && canA, nblk);
-    const uint32_t gridB = sort_scatter_grid(ctx, fnB, "msm_sortB1024pf", 1024, smemB2, geo.gridB,
-                                             geo.wide && canB, max_chunks);
-    const bool pfA = canA && gridA < nblk, pfB = canB && gridB < max_chunks;
-    if (pfA) smemA = smemA2;
-    if (pfB) smemB = smemB2;
-    QG_CHECK(nslots < 0xffffffffull && max_chunks < 0xffffffffull, QG_ERR_UNSUPPORTED,
-             "MSM too large");
+  constexpr bool RESERVED = true, RUN_ONLY = false;
+  auto get = [&](auto*& ptr, const std::string& name, size_t count, bool reserved) {
+    using T = std::remove_reference_t<decltype(*ptr)>;
+    if (run || reserved) ptr = ctx->scratch_as<T>(name, count);
+  };
+  MsmScratch s{};
+  get(s.ghist, "msm_ghist" + tg, p.nghist + 1, RESERVED);
+  get(s.goff, "msm_goff" + tg, p.nghist + 1, RESERVED);
+  get(s.gtiles, "msm_gtiles" + tg, div_up(p.nghist, 2048) + 1, RESERVED);
+  get(s.gstart, "msm_gstart" + tg, p.H + 1, RESERVED);
+  get(s.cbase, "msm_cbase" + tg, p.H + 1, RESERVED);
+  get(s.cgroup, "msm_cgroup" + tg, p.max_chunks, RESERVED);
+  get(s.misc, "msm_misc" + sfx, 5, RESERVED);
+  get(s.chist, "msm_chist" + tg, p.max_chunks * p.NL, RESERVED);
+  get(s.coff, "msm_coff" + tg, p.max_chunks * p.NL, RESERVED);
+  get(s.tmp_e, "msm_tmp_e" + tg, p.max_entries + 1, RESERVED);
+  get(s.tmp_l, "msm_tmp_l" + tg, p.max_entries + 1, RESERVED);
+  get(s.hrow, "msm_hrow" + tg, p.nghist + 1, RESERVED);
+  get(s.orow, "msm_orow" + tg, p.nghist + 1, RESERVED);
+  get(s.canon, "msm_canon" + tg, n, RESERVED);
+  get(s.counts, "msm_counts" + tg, p.nb, RESERVED);
+  get(s.bstart, "msm_bstart" + sfx, p.nb + 1, RESERVED);
+  get(s.entries, "msm_entries" + tg, p.max_entries + 1, RESERVED);
+  get(s.tile_tot, "msm_tiles" + tg, p.ntiles, RUN_ONLY);
+  get(s.partial, "msm_partial" + sfx, p.nslots, RUN_ONLY);  // slot of (thread t, bucket b): t + b
+  get(s.owner, "msm_owner" + sfx, p.nslots, RUN_ONLY);
+  return s;
+}
 
-    {
-      // on the side stream the region is the bucketing's span there, overlapped
-      // with the previous MSM's accumulation: its own name
-      QgTimed tm(ctx, side ? "msm_bucketing_side" : "msm_bucketing", bst);
-      // pass A: partition digits by the high bucket bits
-      hipLaunchKernelGGL(k_sortA_hist, dim3(nblk), dim3(SORT_BLOCK), H * sizeof(uint32_t),
-                         bst, d_scalars, n, c, W, LO, H, nblk, tile, hrow, canon, hv, hgen, wsel,
-                         canon_ready ? 1 : 0);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_transpose32, dim3(div_up(H, 32), div_up(nblk, 32)), dim3(256), 0,
-                         bst, hrow, nblk, (uint32_t)H, ghist);
-      QG_LAUNCH_CHECK();
-      const unsigned gt = div_up(nghist, 2048);
-      QG_CHECK(gt <= 1024u * 1024u, QG_ERR_UNSUPPORTED, "histogram too large");
-      hipLaunchKernelGGL(k_scan32_tiles, dim3(gt), dim3(256), 0, bst, ghist, nghist, goff,
-                         gtiles);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_scan32_top, dim3(1), dim3(1024), 0, bst, gtiles, (int)gt,
-                         goff + nghist);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_scan32_add, dim3(div_up(nghist, 256)), dim3(256), 0, bst, gtiles,
-                         nghist, goff);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_transpose32, dim3(div_up(nblk, 32), div_up(H, 32)), dim3(256), 0,
-                         bst, goff, (uint32_t)H, nblk, orow);
-      QG_LAUNCH_CHECK();
-#define QG_SORT_A_LAUNCH(BLK)                                                                    \
-  hipLaunchKernelGGL(k_sortA_rows<BLK>, dim3(nblk), dim3(BLK), 0, bst, hrow, orow, H);           \
-  QG_LAUNCH_CHECK();                                                                             \
-  if (pfA) {                                                                                     \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortA_scatter<1024, true>), dim3(gridA), dim3(1024),    \
-                       smemA, bst, canon, n, srs->n, srs_off, c, W, LO, H, nblk, tile, hrow,     \
-                       orow, tmp_e, tmp_l, wsel, 3u * (uint32_t)H);                              \
-  } else {                                                                                       \
-    sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortA_scatter<BLK, false>),              \
-                  "msm_lds_attrA" #BLK);                                                         \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortA_scatter<BLK, false>), dim3(gridA), dim3(BLK),     \
-                       smemA, bst, canon, n, srs->n, srs_off, c, W, LO, H, nblk, tile, hrow,     \
-                       orow, tmp_e, tmp_l, wsel, 0u);                                            \
-  }                                                                                              \
-  QG_LAUNCH_CHECK()
-      QG_SORT_DISPATCH_A(geo.blkA, QG_SORT_A_LAUNCH);
-#undef QG_SORT_A_LAUNCH
-      // pass B: sort every group by the low bits, in chunks
-      hipLaunchKernelGGL(k_sort_chunks, dim3(1), dim3(1024), 0, bst, goff, nblk, H, chunk,
-                         gstart, cbase, cgroup, misc);
-      QG_LAUNCH_CHECK();
-#define QG_SORT_B_HIST(BLK, CHUNK)                                                              \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_hist<BLK, CHUNK>), dim3((unsigned)max_chunks),     \
-                     dim3(BLK), NL * sizeof(uint32_t), bst, tmp_l, gstart, cbase, cgroup, misc, \
-                     NL, chist);                                                                \
-  QG_LAUNCH_CHECK()
-      QG_SORT_DISPATCH_B(geo.blkB, chunk, QG_SORT_B_HIST);
-#undef QG_SORT_B_HIST
-      hipLaunchKernelGGL(k_sort_bucket_count, dim3(div_up(nb, 256)), dim3(256), 0, bst,
-                         cbase, chist, LO, nb, counts);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(SCAN_BLOCK), 0, bst, counts,
-                         (size_t)nb, L, bstart, tile_tot, misc + 1);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, bst, tile_tot, ntiles,
-                         bstart, (size_t)nb);
-      QG_LAUNCH_CHECK();
-      run.gen = ++ctx->msm_gen;
-      hipLaunchKernelGGL(k_scan_add, dim3(div_up(nb, 256)), dim3(256), 0, bst, tile_tot,
-                         (size_t)nb, bstart, counts, L, T, misc, run.gen, owner, nslots);
-      QG_LAUNCH_CHECK();
-      {
-        QG_CHECK(slot >= 0 && slot < MSM_MAX_BATCH, QG_ERR_UNSUPPORTED, "MSM batch too large");
-        uint32_t* hmx =
-            reinterpret_cast<uint32_t*>(ctx->pinned_get("msm_mx", MSM_MAX_BATCH * 4 * sizeof(uint32_t)));
-        QG_HIP(hipMemcpyAsync(hmx + 4 * slot, misc + 1, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              bst));
-        run.ev_mx = ctx->ev_get();
-        QG_HIP(hipEventRecord(run.ev_mx, bst));
-        run.h_mx = hmx + 4 * slot;
-      }
-      hipLaunchKernelGGL(k_sort_chunk_offsets, dim3(div_up(nb, 256)), dim3(256), 0, bst,
-                         cbase, chist, LO, nb, bstart, coff);
-      QG_LAUNCH_CHECK();
-#define QG_SORT_B_SCATTER(BLK, CHUNK)                                                          \
-  if (pfB) {                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<1024, 16384, true>), dim3(gridB),       \
-                       dim3(1024), smemB, bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL,  \
-                       chist, coff, entries, 3u * (uint32_t)NL);                               \
-  } else {                                                                                     \
-    sort_lds_attr(ctx, reinterpret_cast<const void*>(&k_sortB_scatter<BLK, CHUNK, false>),     \
-                  "msm_lds_attrB" #BLK "_" #CHUNK);                                            \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<BLK, CHUNK, false>), dim3(gridB),       \
-                       dim3(BLK), smemB, bst, tmp_e, tmp_l, gstart, cbase, cgroup, misc, NL,   \
-                       chist, coff, entries, 0u);                                              \
-  }                                                                                            \
-  QG_LAUNCH_CHECK()
-      QG_SORT_DISPATCH_B(geo.blkB, chunk, QG_SORT_B_SCATTER);
-#undef QG_SORT_B_SCATTER
-    }
-    const hipStream_t ast = bst;  // the accumulation follows on the same stream
-    {
-      QgTimed tm(ctx, "msm_accumulate", ast);
-      // the prefetching per-lane-gather form (QG_MSM_PF=1 with QG_MSM_COOP=0;
-      // the default for 2^27+ entries before the cooperative gathers)
-      // (pf / coop chosen above) cooperative row gathers from 2^25 entries
-      // (2^22 scalars x 13 windows): 2^24 accumulate 16.4-16.6 -> 15.3 ms, 2^22
-      // -4 %, 2^20 neutral (profiles/r05_msm_coop_ab.txt); QG_MSM_COOP=0/1
-      // forces it (A/B runs)
-      if (coop)
-        hipLaunchKernelGGL(k_msm_accumulate_coop, dim3(div_up(max_threads, MSM_BLOCK)),
-                           dim3(MSM_BLOCK), 0, ast, srs->d_table, entries, bstart, nb, L, Lm,
-                           partial, owner);
-      else if (pf)
-        hipLaunchKernelGGL(k_msm_accumulate<true>, dim3(div_up(max_threads, MSM_BLOCK)),
-                           dim3(MSM_BLOCK), 0, ast, srs->d_table, entries, bstart, nb, L, Lm,
-                           partial, owner);
-      else
-        hipLaunchKernelGGL(k_msm_accumulate<false>, dim3(div_up(max_threads, MSM_BLOCK)),
-                           dim3(MSM_BLOCK), 0, ast, srs->d_table, entries, bstart, nb, L, Lm,
-                           partial, owner);
-      QG_LAUNCH_CHECK();
-    }
-    run.empty = n == 0;
-    run.L = L;
-    run.T = T;
-    run.nslots = nslots;
-    run.partial = partial;
-    run.owner = owner;
-    run.bstart = bstart;
-    run.misc = misc;
+// Size the shared bucketing scratch and the entry list (of the stream `slot`
+// selects) for an MSM of length n, launching nothing.  A batch reserves for
+// its longest MSM first: a slot that grew in the middle of a batch would be
+// freed while an earlier MSM's kernels still read it.
+static void msm_reserve(qg_ctx* ctx, const qg_srs* srs, size_t n, int slot, hipStream_t stream) {
+  QG_CHECK(n <= srs->n, QG_ERR_INVALID, "MSM length exceeds the SRS");
+  if (n == 0) return;
+  MsmJob job;
+  job.n = n;
+  job.slot = slot;
+  job.stream = stream;
+  msm_scratch(ctx, msm_job_plan(ctx, srs, job), n, slot, msm_on_side_stream(ctx, job), false);
+}
+
+// pass A's per-tile offsets and scatter with BLK threads; the prefetching
+// instantiation where the plan's grid has fewer blocks than tiles
+template <int BLK, bool PF>
+static void launch_sortA_scatter(qg_ctx* ctx, const qg_srs* srs, const MsmJob& job,
+                                 const MsmPlan& p, const MsmScratch& s) {
+  sort_lds_attr(ctx, sortA_fn<BLK, PF>());
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortA_scatter<BLK, PF>), dim3(p.gridA), dim3(BLK), p.smemA,
+                     job.stream, s.canon, job.n, srs->n, job.srs_off, srs->c, srs->W, p.LO, p.H,
+                     p.nblk, p.geo.tile, s.hrow, s.orow, s.tmp_e, s.tmp_l, job.wsel,
+                     PF ? 3u * (uint32_t)p.H : 0u);
+  QG_LAUNCH_CHECK();
+}
+template <int BLK>
+static void launch_sortA(qg_ctx* ctx, const qg_srs* srs, const MsmJob& job, const MsmPlan& p,
+                         const MsmScratch& s) {
+  hipLaunchKernelGGL(k_sortA_rows<BLK>, dim3(p.nblk), dim3(BLK), 0, job.stream, s.hrow, s.orow, p.H);
+  QG_LAUNCH_CHECK();
+  if (p.pfA)
+    launch_sortA_scatter<1024, true>(ctx, srs, job, p, s);
+  else
+    launch_sortA_scatter<BLK, false>(ctx, srs, job, p, s);
+}
+
+template <int BLK, int CHUNK>
+static void launch_sortB_hist(const MsmJob& job, const MsmPlan& p, const MsmScratch& s) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_hist<BLK, CHUNK>), dim3((unsigned)p.max_chunks),
+                     dim3(BLK), p.NL * sizeof(uint32_t), job.stream, s.tmp_l, s.gstart, s.cbase,
+                     s.cgroup, s.misc, p.NL, s.chist);
+  QG_LAUNCH_CHECK();
+}
+template <int BLK, int CHUNK, bool PF>
+static void launch_sortB_scatter_as(qg_ctx* ctx, const MsmJob& job, const MsmPlan& p,
+                                    const MsmScratch& s) {
+  sort_lds_attr(ctx, sortB_fn<BLK, CHUNK, PF>());
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sortB_scatter<BLK, CHUNK, PF>), dim3(p.gridB), dim3(BLK),
+                     p.smemB, job.stream, s.tmp_e, s.tmp_l, s.gstart, s.cbase, s.cgroup, s.misc, p.NL,
+                     s.chist, s.coff, s.entries, PF ? 3u * (uint32_t)p.NL : 0u);
+  QG_LAUNCH_CHECK();
+}
+template <int BLK, int CHUNK>
+static void launch_sortB_scatter(qg_ctx* ctx, const MsmJob& job, const MsmPlan& p,
+                                 const MsmScratch& s) {
+  if (p.pfB)
+    launch_sortB_scatter_as<1024, 16384, true>(ctx, job, p, s);
+  else
+    launch_sortB_scatter_as<BLK, CHUNK, false>(ctx, job, p, s);
+}
+
+// the two pass-B kernels of the plan's (blkB, chunk) pair (sort_geometry
+// admits only the instantiated ones)
+static void sortB_hist_launch(const MsmJob& job, const MsmPlan& p, const MsmScratch& s) {
+  const bool small = p.geo.chunk == 8192;
+  switch (p.geo.blkB) {
+    case 256: launch_sortB_hist<256, 8192>(job, p, s); break;
+    case 512:
+      if (small) launch_sortB_hist<512, 8192>(job, p, s);
+      else launch_sortB_hist<512, 16384>(job, p, s);
+      break;
+    default: launch_sortB_hist<1024, 16384>(job, p, s); break;
   }
+}
+static void sortB_scatter_launch(qg_ctx* ctx, const MsmJob& job, const MsmPlan& p,
+                                 const MsmScratch& s) {
+  const bool small = p.geo.chunk == 8192;
+  switch (p.geo.blkB) {
+    case 256: launch_sortB_scatter<256, 8192>(ctx, job, p, s); break;
+    case 512:
+      if (small) launch_sortB_scatter<512, 8192>(ctx, job, p, s);
+      else launch_sortB_scatter<512, 16384>(ctx, job, p, s);
+      break;
+    default: launch_sortB_scatter<1024, 16384>(ctx, job, p, s); break;
+  }
+}
+
+// pass A: partition digits by the high bucket bits
+static void msm_passA_launch(qg_ctx* ctx, const qg_srs* srs, const MsmJob& job, const MsmPlan& p,
+                             const MsmScratch& s) {
+  const hipStream_t st = job.stream;
+  const uint32_t nblk = p.nblk, H = (uint32_t)p.H;
+  hipLaunchKernelGGL(k_sortA_hist, dim3(nblk), dim3(SORT_BLOCK), H * sizeof(uint32_t), st,
+                     job.d_scalars, job.n, srs->c, srs->W, p.LO, p.H, nblk, p.geo.tile, s.hrow,
+                     s.canon, job.hv, job.hgen, job.wsel, job.canon_ready ? 1 : 0);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_transpose32, dim3(div_up(H, 32), div_up(nblk, 32)), dim3(256), 0, st, s.hrow,
+                     nblk, H, s.ghist);
+  QG_LAUNCH_CHECK();
+  const unsigned gt = div_up(p.nghist, 2048);
+  hipLaunchKernelGGL(k_scan32_tiles, dim3(gt), dim3(256), 0, st, s.ghist, p.nghist, s.goff, s.gtiles);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_scan32_top, dim3(1), dim3(1024), 0, st, s.gtiles, (int)gt, s.goff + p.nghist);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_scan32_add, dim3(div_up(p.nghist, 256)), dim3(256), 0, st, s.gtiles, p.nghist,
+                     s.goff);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_transpose32, dim3(div_up(nblk, 32), div_up(H, 32)), dim3(256), 0, st, s.goff,
+                     H, nblk, s.orow);
+  QG_LAUNCH_CHECK();
+  switch (p.geo.blkA) {
+    case 256: launch_sortA<256>(ctx, srs, job, p, s); break;
+    case 512: launch_sortA<512>(ctx, srs, job, p, s); break;
+    default: launch_sortA<1024>(ctx, srs, job, p, s); break;
+  }
+}
+
+// pass B: sort every group by the low bits, in chunks; between its histogram
+// and its scatter the bucket scan, whose plan words (misc[1..4]) go to the
+// pinned copy of `run` behind run.ev_mx
+static void msm_passB_launch(qg_ctx* ctx, const MsmJob& job, const MsmPlan& p, const MsmScratch& s,
+                             const MsmRun& run) {
+  const hipStream_t st = job.stream;
+  const uint32_t nb = p.nb;
+  hipLaunchKernelGGL(k_sort_chunks, dim3(1), dim3(1024), 0, st, s.goff, p.nblk, p.H, p.geo.chunk,
+                     s.gstart, s.cbase, s.cgroup, s.misc);
+  QG_LAUNCH_CHECK();
+  sortB_hist_launch(job, p, s);
+  hipLaunchKernelGGL(k_sort_bucket_count, dim3(div_up(nb, 256)), dim3(256), 0, st, s.cbase, s.chist,
+                     p.LO, nb, s.counts);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_scan_tiles, dim3(p.ntiles), dim3(SCAN_BLOCK), 0, st, s.counts, (size_t)nb,
+                     p.L, s.bstart, s.tile_tot, s.misc + 1);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, s.tile_tot, p.ntiles, s.bstart,
+                     (size_t)nb);
+  QG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_scan_add, dim3(div_up(nb, 256)), dim3(256), 0, st, s.tile_tot, (size_t)nb,
+                     s.bstart, s.counts, p.L, p.T, s.misc, run.gen, s.owner, p.nslots);
+  QG_LAUNCH_CHECK();
+  QG_HIP(hipMemcpyAsync(run.h_mx, s.misc + 1, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  QG_HIP(hipEventRecord(run.ev_mx, st));
+  hipLaunchKernelGGL(k_sort_chunk_offsets, dim3(div_up(nb, 256)), dim3(256), 0, st, s.cbase, s.chist,
+                     p.LO, nb, s.bstart, s.coff);
+  QG_LAUNCH_CHECK();
+  sortB_scatter_launch(ctx, job, p, s);
+}
+
+// bucketing: the two-pass radix sort of the digits into the entry list
+static void msm_bucketing_launch(qg_ctx* ctx, const qg_srs* srs, const MsmJob& job,
+                                 const MsmPlan& p, const MsmScratch& s, const MsmRun& run) {
+  // on the side stream the region is the bucketing's span there, overlapped
+  // with the previous MSM's accumulation: its own name
+  QgTimed tm(ctx, msm_on_side_stream(ctx, job) ? "msm_bucketing_side" : "msm_bucketing", job.stream);
+  msm_passA_launch(ctx, srs, job, p, s);
+  msm_passB_launch(ctx, job, p, s, run);
+}
+
+// the accumulation follows on the same stream
+static void msm_accumulate_launch(qg_ctx* ctx, const qg_srs* srs, const MsmJob& job,
+                                  const MsmPlan& p, const MsmScratch& s) {
+  QgTimed tm(ctx, "msm_accumulate", job.stream);
+  // the prefetching per-lane-gather form (QG_MSM_PF=1 with QG_MSM_COOP=0;
+  // the default for 2^27+ entries before the cooperative gathers)
+  // (pf / coop chosen by msm_plan) cooperative row gathers from 2^25 entries
+  // (2^22 scalars x 13 windows): 2^24 accumulate 16.4-16.6 -> 15.3 ms, 2^22
+  // -4 %, 2^20 neutral (profiles/r05_msm_coop_ab.txt); QG_MSM_COOP=0/1
+  // forces it (A/B runs)
+  auto kernel = p.coop ? k_msm_accumulate_coop : p.pf ? k_msm_accumulate<true> : k_msm_accumulate<false>;
+  hipLaunchKernelGGL(kernel, dim3(div_up(p.max_threads, MSM_BLOCK)), dim3(MSM_BLOCK), 0, job.stream,
+                     srs->d_table, s.entries, s.bstart, p.nb, p.L, p.Lm, s.partial, s.owner);
+  QG_LAUNCH_CHECK();
+}
+
+// bucketing (two-pass radix sort) + bucket accumulation of one MSM of a batch.
+// evs: the event guard of the caller's batch, which owns the run's ev_mx
+static MsmRun msm_accumulate_phase(qg_ctx* ctx, const qg_srs* srs, const MsmJob& j, QgEvents& evs) {
+  QG_CHECK(j.srs_off <= srs->n && j.n <= srs->n - j.srs_off, QG_ERR_INVALID,
+           "MSM length exceeds the SRS");
+  MsmRun run;
+  if (j.n == 0) return run;
+  MsmJob job = j;
+  if (!job.stream) job.stream = ctx->stream;
+  const MsmPlan p = msm_job_plan(ctx, srs, job);
+  const MsmScratch s = msm_scratch(ctx, p, job.n, job.slot, msm_on_side_stream(ctx, job), true);
+  uint32_t* hmx =
+      reinterpret_cast<uint32_t*>(ctx->pinned_get("msm_mx", MSM_MAX_BATCH * 4 * sizeof(uint32_t)));
+  run.empty = false;
+  run.L = p.L;
+  run.T = p.T;
+  run.nslots = p.nslots;
+  run.partial = s.partial;
+  run.owner = s.owner;
+  run.bstart = s.bstart;
+  run.misc = s.misc;
+  run.h_mx = hmx + 4 * job.slot;
+  run.ev_mx = evs.get();
+  run.gen = ++ctx->msm_gen;
+  msm_bucketing_launch(ctx, srs, job, p, s, run);
+  msm_accumulate_launch(ctx, srs, job, p, s);
   return run;
 }
+
+// hv / hgen: the hand-over guard words of a batch whose partials come from
+// the side streams (msm_device_batch); its error word lands in *h_err (pinned)
+// with the results
+struct MsmHandover {
+  uint32_t* hv = nullptr;
+  uint32_t hgen = 0;
+  uint32_t* h_err = nullptr;
+};
 
 // Bucket reduction of a batch of accumulated MSMs (same SRS): tree steps for
 // skewed buckets (per MSM, rare), then ONE launch each of the bucket combine,
 // the two weighted-sum levels and the export for the whole batch — the
 // latency-bound tail of the MSM is paid once per batch.  out: XYZZ (R = 2^256)
 // per MSM, not yet summed over ranks.
-// hv / hgen: the hand-over guard words of a batch whose partials come from
-// the side streams (msm_device_batch); its error word lands in *h_err (pinned)
-// with the results
 static void msm_reduce_phase(qg_ctx* ctx, const qg_srs* srs, const std::vector<MsmRun>& runs,
-                             std::vector<G1Xyzz>& out, uint32_t* hv = nullptr, uint32_t hgen = 0,
-                             uint32_t* h_err = nullptr) {
+                             std::vector<G1Xyzz>& out, const MsmHandover& ho = {}) {
+  uint32_t* const hv = ho.hv;
+  uint32_t* const h_err = ho.h_err;
+  const uint32_t hgen = ho.hgen;
   const uint32_t k = (uint32_t)runs.size();
   out.assign(k, G1Xyzz::infinity());
   std::vector<uint32_t> live;
@@ -2123,8 +1965,6 @@ static void msm_reduce_phase(qg_ctx* ctx, const qg_srs* srs, const std::vector<M
       ctx->msm_plan_refetch++;
     }
   }
-  for (const MsmRun& r : runs)
-    if (r.ev_mx) ctx->event_pool.push_back(r.ev_mx);
   // level 1: S = 2^slog1 buckets per thread, as many threads as the chip has
   // SIMD lanes (one wave per SIMD) over the whole batch; folds of 2^gl1 lanes
   const size_t lanes = (size_t)ctx->num_cus() * 4 * 64;
@@ -2295,14 +2135,23 @@ static std::vector<G1Affine> msm_finish_ranks_batch(qg_ctx* ctx, const std::vect
 static G1Xyzz msm_oneshot_local(qg_ctx* ctx, const qg_srs* srs, const Fr* d, size_t n,
                                 size_t srs_off = 0) {
   if (n == 0) return G1Xyzz::infinity();
+  QgEvents evs(ctx);
   std::vector<MsmRun> runs;
   // all on ctx->stream: window w > 0 reads the canonical scalars window 0's
   // pass A left in the (per-stream) canon scratch
-  for (int w = 0; w < srs->W; w++)
-    runs.push_back(
-        msm_accumulate_phase(ctx, srs, d, n, w, srs_off, nullptr, false, nullptr, 0, w, w > 0));
+  for (int w = 0; w < srs->W; w++) {
+    MsmJob job;
+    job.d_scalars = d;
+    job.n = n;
+    job.slot = w;
+    job.srs_off = srs_off;
+    job.wsel = w;
+    job.canon_ready = w > 0;
+    runs.push_back(msm_accumulate_phase(ctx, srs, job, evs));
+  }
   std::vector<G1Xyzz> part;
   msm_reduce_phase(ctx, srs, runs, part);  // ends with a synchronization
+  evs.release();
   G1Xyzz acc = part[srs->W - 1];
   for (int w = srs->W - 2; w >= 0; w--) {
     for (int k = 0; k < srs->c; k++) acc = xyzz_dbl(acc);
@@ -2325,7 +2174,7 @@ static std::vector<G1Xyzz> msm_batch_local(qg_ctx* ctx, const qg_srs* srs,
   hipStream_t side[2] = {nullptr, nullptr};
   bool host_sync = false;
   if (const char* ov = getenv("QG_MSM_PIPE_SYNC")) host_sync = atoi(ov) != 0;
-  std::vector<hipEvent_t> held;  // hand-over events of this batch
+  QgEvents evs(ctx);  // hand-over events of this batch, and its runs' ev_mx
   uint32_t* hv = nullptr;
   uint32_t hgen = 0;
   uint32_t* h_err = nullptr;
@@ -2342,8 +2191,7 @@ static std::vector<G1Xyzz> msm_batch_local(qg_ctx* ctx, const qg_srs* srs,
       hgen = ++ctx->msm_gen;
       hipLaunchKernelGGL(k_handover_tag, dim3(1), dim3(64), 0, ctx->stream, hv, 0u, hgen, 1u);
       QG_LAUNCH_CHECK();
-      hipEvent_t ev = ctx->ev_get();
-      held.push_back(ev);
+      hipEvent_t ev = evs.get();
       QG_HIP(hipEventRecord(ev, ctx->stream));
       for (hipStream_t st : side) QG_HIP(hipStreamWaitEvent(st, ev, 0));
     }
@@ -2352,21 +2200,26 @@ static std::vector<G1Xyzz> msm_batch_local(qg_ctx* ctx, const qg_srs* srs,
     size_t im = 0;
     for (size_t i = 1; i < ns.size(); i++)
       if (ns[i] > ns[im]) im = i;
-    for (int p = 0; p < (pipe ? 2 : 1); p++)
-      msm_accumulate_phase(ctx, srs, scalars[im], ns[im], p, 0, side[p], true);
+    for (int p = 0; p < (pipe ? 2 : 1); p++) msm_reserve(ctx, srs, ns[im], p, side[p]);
   }
   std::vector<MsmRun> runs;
-  for (size_t i = 0; i < scalars.size(); i++)
-    runs.push_back(
-        msm_accumulate_phase(ctx, srs, scalars[i], ns[i], (int)i, 0, side[i & 1], false, hv, hgen));
+  for (size_t i = 0; i < scalars.size(); i++) {
+    MsmJob job;
+    job.d_scalars = scalars[i];
+    job.n = ns[i];
+    job.slot = (int)i;
+    job.stream = side[i & 1];
+    job.hv = hv;
+    job.hgen = hgen;
+    runs.push_back(msm_accumulate_phase(ctx, srs, job, evs));
+  }
   if (pipe && host_sync) {
     for (hipStream_t st : side) QG_HIP(hipStreamSynchronize(st));
   } else if (pipe) {  // the reduction (ctx->stream) after both side streams
     for (int p = 0; p < 2; p++) {
       hipLaunchKernelGGL(k_handover_tag, dim3(1), dim3(64), 0, side[p], hv, 2u + (uint32_t)p, hgen, 0u);
       QG_LAUNCH_CHECK();
-      hipEvent_t ev = ctx->ev_get();
-      held.push_back(ev);
+      hipEvent_t ev = evs.get();
       QG_HIP(hipEventRecord(ev, side[p]));
       QG_HIP(hipStreamWaitEvent(ctx->stream, ev, 0));
     }
@@ -2375,8 +2228,12 @@ static std::vector<G1Xyzz> msm_batch_local(qg_ctx* ctx, const qg_srs* srs,
   // ends with a synchronization of ctx->stream, which waited for both side
   // streams: the side streams are idle when this returns (the grid-barrier
   // sumcheck kernels never share the chip with them)
-  msm_reduce_phase(ctx, srs, runs, local, hv, hgen, h_err);
-  for (hipEvent_t e : held) ctx->event_pool.push_back(e);
+  MsmHandover ho;
+  ho.hv = hv;
+  ho.hgen = hgen;
+  ho.h_err = h_err;
+  msm_reduce_phase(ctx, srs, runs, local, ho);
+  evs.release();
   if (hv && *h_err != 0) {
     ctx->msm_handover_violation++;
     *violated = true;
@@ -2428,11 +2285,10 @@ static G1Affine msm_host(qg_ctx* ctx, const qg_srs* srs, const uint64_t* h, size
   if (!ctx->copy_stream) QG_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
   // the hand-over events return to the pool only after the reduction's
   // synchronization (none is re-recorded while a queued wait refers to it)
-  std::vector<hipEvent_t> held;
+  QgEvents evs(ctx);
   {  // the uploads start after the work already queued on ctx->stream (stream
      // order in both directions: the scratch slot may still be read there)
-    hipEvent_t ev = ctx->ev_get();
-    held.push_back(ev);
+    hipEvent_t ev = evs.get();
     QG_HIP(hipEventRecord(ev, ctx->stream));
     QG_HIP(hipStreamWaitEvent(ctx->copy_stream, ev, 0));
   }
@@ -2443,15 +2299,19 @@ static G1Affine msm_host(qg_ctx* ctx, const qg_srs* srs, const uint64_t* h, size
     if (len == 0) break;
     QG_HIP(hipMemcpyAsync(d + off, h + 4 * off, len * sizeof(Fr), hipMemcpyHostToDevice,
                           ctx->copy_stream));
-    hipEvent_t ev = ctx->ev_get();
-    held.push_back(ev);
+    hipEvent_t ev = evs.get();
     QG_HIP(hipEventRecord(ev, ctx->copy_stream));
     QG_HIP(hipStreamWaitEvent(ctx->stream, ev, 0));
-    runs.push_back(msm_accumulate_phase(ctx, srs, d + off, len, k, off));
+    MsmJob job;
+    job.d_scalars = d + off;
+    job.n = len;
+    job.slot = k;
+    job.srs_off = off;
+    runs.push_back(msm_accumulate_phase(ctx, srs, job, evs));
   }
   std::vector<G1Xyzz> part;
   msm_reduce_phase(ctx, srs, runs, part);  // ends with a synchronization
-  for (hipEvent_t e : held) ctx->event_pool.push_back(e);
+  evs.release();
   G1Xyzz acc = G1Xyzz::infinity();
   for (const G1Xyzz& q : part) acc = xyzz_add(acc, q);
   return msm_finish_ranks(ctx, acc);
@@ -2462,16 +2322,22 @@ G1Affine msm_device(qg_ctx* ctx, const qg_srs* srs, const Fr* d_scalars, size_t 
 }
 
 // msm_unchecked over the base slice srs[off..] (qg_msm_g1_at / _dev_at): the
-// entries point at rows off + i of each table (msm_accumulate_phase srs_off)
+// entries point at rows off + i of each table (MsmJob srs_off)
 static G1Affine msm_device_at(qg_ctx* ctx, const qg_srs* srs, const Fr* d, size_t n, size_t off) {
   if (off == 0) return msm_device(ctx, srs, d, n);
   G1Xyzz acc = G1Xyzz::infinity();
   if (srs->tables != srs->W) {
     acc = msm_oneshot_local(ctx, srs, d, n, off);
   } else if (n > 0) {
-    std::vector<MsmRun> runs{msm_accumulate_phase(ctx, srs, d, n, 0, off)};
+    QgEvents evs(ctx);
+    MsmJob job;
+    job.d_scalars = d;
+    job.n = n;
+    job.srs_off = off;
+    std::vector<MsmRun> runs{msm_accumulate_phase(ctx, srs, job, evs)};
     std::vector<G1Xyzz> part;
     msm_reduce_phase(ctx, srs, runs, part);  // ends with a synchronization
+    evs.release();
     acc = part[0];
   }
   return msm_finish_ranks(ctx, acc);
@@ -2524,144 +2390,13 @@ __global__ void __launch_bounds__(256) k_fetch_stream(const uint4* __restrict__ 
   sink[t] = s;
 }
 
-// ---- qg_selftest_curve29 / qg_selftest_msm_fold -----------------------------
-// The XYZZ primitives one call at a time on raw limbs (quill_gpu.h).  Values
-// are computed and stored by thread index only.
+// ---- qg_selftest_msm_fold ---------------------------------------------------
+// (qg_selftest_curve29, the XYZZ primitives one call at a time: selftest29.hip)
 static constexpr size_t X29_MAX_CASES = 65536;
-
-QG_HD X29 x29_from_limbs(const uint32_t* w) {
-  X29 p;
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    p.X.l[i] = w[i];
-    p.Y.l[i] = w[9 + i];
-    p.ZZ.l[i] = w[18 + i];
-    p.ZZZ.l[i] = w[27 + i];
-  }
-  return p;
-}
-
-QG_HD void x29_to_limbs(const X29& p, uint32_t* w) {
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    w[i] = p.X.l[i];
-    w[9 + i] = p.Y.l[i];
-    w[18 + i] = p.ZZ.l[i];
-    w[27 + i] = p.ZZZ.l[i];
-  }
-}
-
-// the host-callable ops; false: not one of them
-QG_HD bool x29_op_hd(int op, const X29& p, const X29& q, X29& r) {
-  switch (op) {
-    case QG_X29_ADD: r = x29_add(p, q); return true;
-    case QG_X29_DBL: r = x29_dbl(p); return true;
-    case QG_X29_ADD_AFFINE: {
-      A29 a;
-      a.x = q.X;
-      a.y = q.Y;
-      r = x29_add_affine(p, a);
-      return true;
-    }
-    case QG_X29_ACC_FINISH: r = x29_acc_finish(p); return true;
-    case QG_X29_RAW: r = x29_unraw(x29_raw(p)); return true;
-    default: return false;
-  }
-}
-
-// OP < QG_X29_ADD_Q4: thread i runs case i; the quad ops: lanes 4 i .. 4 i + 3
-// run case i and every lane stores what it returned
-template <int OP>
-__global__ void __launch_bounds__(64)
-    k_x29_selftest(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out,
-                   uint32_t* __restrict__ flags) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr bool QUAD = OP == QG_X29_ADD_Q4 || OP == QG_X29_DBL_Q4;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = QUAD ? t >> 2 : t;
-  if (i >= n) return;  // whole quads leave together
-  const X29 p = x29_from_limbs(in + i * QG_SELFTEST_X29_IN);
-  const X29 q = x29_from_limbs(in + i * QG_SELFTEST_X29_IN + 36);
-  X29 r = p;
-  uint32_t fl = 0;
-  if constexpr (OP == QG_X29_ACC_MADD) {
-    bool inf = false;
-    if (x29_acc_madd_tp(r, q.X, q.Y)) {
-      fl = QG_X29_FLAG_MAIN;
-    } else {
-      x29_acc_madd_exc(r, q.X, q.Y, &inf);
-      fl = QG_X29_FLAG_EXC | (inf ? QG_X29_FLAG_INF : 0u);
-    }
-  } else if constexpr (OP == QG_X29_ADD_Q4) {
-    r = x29_add_q4(p, q);
-  } else if constexpr (OP == QG_X29_DBL_Q4) {
-    r = x29_dbl_q4(p);
-  } else {
-    x29_op_hd(OP, p, q, r);
-  }
-  x29_to_limbs(r, out + t * QG_SELFTEST_X29_OUT);
-  if (!QUAD || (t & 3u) == 0) flags[i] = fl;
-#endif
-}
-
-template <int OP>
-static void x29_selftest_launch(qg_ctx* ctx, const uint32_t* d_in, size_t n, uint32_t* d_out,
-                                uint32_t* d_flags) {
-  const size_t threads = (OP == QG_X29_ADD_Q4 || OP == QG_X29_DBL_Q4) ? 4 * n : n;
-  hipLaunchKernelGGL(k_x29_selftest<OP>, dim3(div_up(threads, 64)), dim3(64), 0, ctx->stream, d_in, n,
-                     d_out, d_flags);
-  QG_LAUNCH_CHECK();
-}
-
-static void x29_selftest(qg_ctx* ctx, int op, bool dev, const uint32_t* in, size_t n, uint32_t* out,
-                         uint32_t* flags) {
-  if (n == 0) return;
-  if (!dev) {
-    for (size_t i = 0; i < n; i++) {
-      const X29 p = x29_from_limbs(in + i * QG_SELFTEST_X29_IN);
-      const X29 q = x29_from_limbs(in + i * QG_SELFTEST_X29_IN + 36);
-      X29 r = p;
-      QG_CHECK(x29_op_hd(op, p, q, r), QG_ERR_UNSUPPORTED, "device-only form: no host path");
-      x29_to_limbs(r, out + i * QG_SELFTEST_X29_OUT);
-      flags[i] = 0;
-    }
-    return;
-  }
-  QG_CHECK(ctx, QG_ERR_INVALID, "device self-test needs a context");
-  QG_HIP(hipSetDevice(ctx->device));
-  const bool quad = op == QG_X29_ADD_Q4 || op == QG_X29_DBL_Q4;
-  const size_t ni = n * QG_SELFTEST_X29_IN;
-  const size_t no = n * (quad ? QG_SELFTEST_X29_OUT_Q4 : QG_SELFTEST_X29_OUT);
-  uint32_t* d = ctx->scratch_as<uint32_t>("x29_selftest", ni + no + n);
-  uint32_t *d_out = d + ni, *d_flags = d_out + no;
-  QG_HIP(hipMemcpyAsync(d, in, ni * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-  switch (op) {
-    case QG_X29_ADD: x29_selftest_launch<QG_X29_ADD>(ctx, d, n, d_out, d_flags); break;
-    case QG_X29_DBL: x29_selftest_launch<QG_X29_DBL>(ctx, d, n, d_out, d_flags); break;
-    case QG_X29_ADD_AFFINE: x29_selftest_launch<QG_X29_ADD_AFFINE>(ctx, d, n, d_out, d_flags); break;
-    case QG_X29_ACC_FINISH: x29_selftest_launch<QG_X29_ACC_FINISH>(ctx, d, n, d_out, d_flags); break;
-    case QG_X29_RAW: x29_selftest_launch<QG_X29_RAW>(ctx, d, n, d_out, d_flags); break;
-    case QG_X29_ACC_MADD: x29_selftest_launch<QG_X29_ACC_MADD>(ctx, d, n, d_out, d_flags); break;
-    case QG_X29_ADD_Q4: x29_selftest_launch<QG_X29_ADD_Q4>(ctx, d, n, d_out, d_flags); break;
-    default: x29_selftest_launch<QG_X29_DBL_Q4>(ctx, d, n, d_out, d_flags); break;
-  }
-  QG_HIP(hipMemcpyAsync(out, d_out, no * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  QG_HIP(hipMemcpyAsync(flags, d_flags, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  ctx->sync();
-}
 
 }  // namespace qg
 
 extern "C" {
-
-int qg_selftest_curve29(qg_ctx* ctx, int op, int on_device, const uint32_t* in, size_t n,
-                        uint32_t* out, uint32_t* flags) {
-  if (!in || !out || !flags) return QG_ERR_INVALID;
-  if (op < 0 || op >= QG_X29_OP_COUNT) return QG_ERR_INVALID;
-  if (n > X29_MAX_CASES) return QG_ERR_INVALID;
-  if (on_device && !ctx) return QG_ERR_INVALID;
-  return qg_guard(ctx, [&] { x29_selftest(ctx, op, on_device != 0, in, n, out, flags); });
-}
 
 int qg_selftest_msm_fold(qg_ctx* ctx, int q4, const uint32_t* A, const uint32_t* Y, uint32_t m,
                          uint32_t batch, size_t istride, int want_y, uint32_t* A_out,

@@ -5,8 +5,10 @@
 // only the residue.  on_device = 0 runs the QG_HD functions as compiled for
 // the host; on_device = 1 runs them as compiled for gfx950, plus the
 // device-only throughput forms (mul29t ...).  One thread per case, no
-// data-dependent addressing.
+// data-dependent addressing.  qg_selftest_curve29 (below) does the same for
+// the XYZZ primitives of curve29.h.
 #include "common.h"
+#include "curve29.h"
 #include "field29.h"
 
 using namespace qg;
@@ -124,6 +126,132 @@ static void f29_selftest(qg_ctx* ctx, int op, bool dev, const uint32_t* in, size
   }
 }
 
+// ---- qg_selftest_curve29 ----------------------------------------------------
+// The XYZZ primitives one call at a time on raw limbs (quill_gpu.h).  Values
+// are computed and stored by thread index only.
+static constexpr size_t X29_MAX_CASES = 65536;
+
+QG_HD X29 x29_from_limbs(const uint32_t* w) {
+  X29 p;
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    p.X.l[i] = w[i];
+    p.Y.l[i] = w[9 + i];
+    p.ZZ.l[i] = w[18 + i];
+    p.ZZZ.l[i] = w[27 + i];
+  }
+  return p;
+}
+
+QG_HD void x29_to_limbs(const X29& p, uint32_t* w) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    w[i] = p.X.l[i];
+    w[9 + i] = p.Y.l[i];
+    w[18 + i] = p.ZZ.l[i];
+    w[27 + i] = p.ZZZ.l[i];
+  }
+}
+
+// the host-callable ops; false: not one of them
+QG_HD bool x29_op_hd(int op, const X29& p, const X29& q, X29& r) {
+  switch (op) {
+    case QG_X29_ADD: r = x29_add(p, q); return true;
+    case QG_X29_DBL: r = x29_dbl(p); return true;
+    case QG_X29_ADD_AFFINE: {
+      A29 a;
+      a.x = q.X;
+      a.y = q.Y;
+      r = x29_add_affine(p, a);
+      return true;
+    }
+    case QG_X29_ACC_FINISH: r = x29_acc_finish(p); return true;
+    case QG_X29_RAW: r = x29_unraw(x29_raw(p)); return true;
+    default: return false;
+  }
+}
+
+// OP < QG_X29_ADD_Q4: thread i runs case i; the quad ops: lanes 4 i .. 4 i + 3
+// run case i and every lane stores what it returned
+template <int OP>
+__global__ void __launch_bounds__(64)
+    k_x29_selftest(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out,
+                   uint32_t* __restrict__ flags) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool QUAD = OP == QG_X29_ADD_Q4 || OP == QG_X29_DBL_Q4;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = QUAD ? t >> 2 : t;
+  if (i >= n) return;  // whole quads leave together
+  const X29 p = x29_from_limbs(in + i * QG_SELFTEST_X29_IN);
+  const X29 q = x29_from_limbs(in + i * QG_SELFTEST_X29_IN + 36);
+  X29 r = p;
+  uint32_t fl = 0;
+  if constexpr (OP == QG_X29_ACC_MADD) {
+    bool inf = false;
+    if (x29_acc_madd_tp(r, q.X, q.Y)) {
+      fl = QG_X29_FLAG_MAIN;
+    } else {
+      x29_acc_madd_exc(r, q.X, q.Y, &inf);
+      fl = QG_X29_FLAG_EXC | (inf ? QG_X29_FLAG_INF : 0u);
+    }
+  } else if constexpr (OP == QG_X29_ADD_Q4) {
+    r = x29_add_q4(p, q);
+  } else if constexpr (OP == QG_X29_DBL_Q4) {
+    r = x29_dbl_q4(p);
+  } else {
+    x29_op_hd(OP, p, q, r);
+  }
+  x29_to_limbs(r, out + t * QG_SELFTEST_X29_OUT);
+  if (!QUAD || (t & 3u) == 0) flags[i] = fl;
+#endif
+}
+
+template <int OP>
+static void x29_selftest_launch(qg_ctx* ctx, const uint32_t* d_in, size_t n, uint32_t* d_out,
+                                uint32_t* d_flags) {
+  const size_t threads = (OP == QG_X29_ADD_Q4 || OP == QG_X29_DBL_Q4) ? 4 * n : n;
+  hipLaunchKernelGGL(k_x29_selftest<OP>, dim3(div_up(threads, 64)), dim3(64), 0, ctx->stream, d_in, n,
+                     d_out, d_flags);
+  QG_LAUNCH_CHECK();
+}
+
+static void x29_selftest(qg_ctx* ctx, int op, bool dev, const uint32_t* in, size_t n, uint32_t* out,
+                         uint32_t* flags) {
+  if (n == 0) return;
+  if (!dev) {
+    for (size_t i = 0; i < n; i++) {
+      const X29 p = x29_from_limbs(in + i * QG_SELFTEST_X29_IN);
+      const X29 q = x29_from_limbs(in + i * QG_SELFTEST_X29_IN + 36);
+      X29 r = p;
+      QG_CHECK(x29_op_hd(op, p, q, r), QG_ERR_UNSUPPORTED, "device-only form: no host path");
+      x29_to_limbs(r, out + i * QG_SELFTEST_X29_OUT);
+      flags[i] = 0;
+    }
+    return;
+  }
+  QG_CHECK(ctx, QG_ERR_INVALID, "device self-test needs a context");
+  QG_HIP(hipSetDevice(ctx->device));
+  const bool quad = op == QG_X29_ADD_Q4 || op == QG_X29_DBL_Q4;
+  const size_t ni = n * QG_SELFTEST_X29_IN;
+  const size_t no = n * (quad ? QG_SELFTEST_X29_OUT_Q4 : QG_SELFTEST_X29_OUT);
+  uint32_t* d = ctx->scratch_as<uint32_t>("x29_selftest", ni + no + n);
+  uint32_t *d_out = d + ni, *d_flags = d_out + no;
+  QG_HIP(hipMemcpyAsync(d, in, ni * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  switch (op) {
+    case QG_X29_ADD: x29_selftest_launch<QG_X29_ADD>(ctx, d, n, d_out, d_flags); break;
+    case QG_X29_DBL: x29_selftest_launch<QG_X29_DBL>(ctx, d, n, d_out, d_flags); break;
+    case QG_X29_ADD_AFFINE: x29_selftest_launch<QG_X29_ADD_AFFINE>(ctx, d, n, d_out, d_flags); break;
+    case QG_X29_ACC_FINISH: x29_selftest_launch<QG_X29_ACC_FINISH>(ctx, d, n, d_out, d_flags); break;
+    case QG_X29_RAW: x29_selftest_launch<QG_X29_RAW>(ctx, d, n, d_out, d_flags); break;
+    case QG_X29_ACC_MADD: x29_selftest_launch<QG_X29_ACC_MADD>(ctx, d, n, d_out, d_flags); break;
+    case QG_X29_ADD_Q4: x29_selftest_launch<QG_X29_ADD_Q4>(ctx, d, n, d_out, d_flags); break;
+    default: x29_selftest_launch<QG_X29_DBL_Q4>(ctx, d, n, d_out, d_flags); break;
+  }
+  QG_HIP(hipMemcpyAsync(out, d_out, no * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  QG_HIP(hipMemcpyAsync(flags, d_flags, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+}
+
 }  // namespace qg
 
 extern "C" {
@@ -139,6 +267,15 @@ int qg_selftest_field29(qg_ctx* ctx, int field, int op, int on_device, const uin
     if (field == 0) f29_selftest<FrP>(ctx, op, on_device != 0, in, n, out);
     else f29_selftest<FqP>(ctx, op, on_device != 0, in, n, out);
   });
+}
+
+int qg_selftest_curve29(qg_ctx* ctx, int op, int on_device, const uint32_t* in, size_t n,
+                        uint32_t* out, uint32_t* flags) {
+  if (!in || !out || !flags) return QG_ERR_INVALID;
+  if (op < 0 || op >= QG_X29_OP_COUNT) return QG_ERR_INVALID;
+  if (n > X29_MAX_CASES) return QG_ERR_INVALID;
+  if (on_device && !ctx) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] { x29_selftest(ctx, op, on_device != 0, in, n, out, flags); });
 }
 
 }  // extern "C"

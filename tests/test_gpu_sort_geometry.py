@@ -21,7 +21,9 @@ trapdoor value [p(tau)] g and the default geometry's result.
     values whose every 20-bit digit is 2^19 or 2^19 + 1: the carry runs through
     all 13 windows);
   * an override that names a geometry without an instantiation is
-    QG_ERR_INVALID before anything is launched.
+    QG_ERR_INVALID before anything is launched; a side-stream batch that
+    fails this way returns the hand-over event it took (the context's
+    events in use, `events_created` - `events_pooled`, stay as they were).
 """
 import contextlib
 import os
@@ -206,3 +208,36 @@ def test_geometry_without_instantiation_is_rejected(dev, srs_of, bad):
         assert default_result("c20", "random", srs, vec, n) == expected(n)
     finally:
         dev.enable_timing(False)
+
+
+def test_failing_batch_returns_its_events(dev, srs_of):
+    """A side-stream batch that fails after it took its first hand-over event
+    (the bad geometry is found when the batch sizes its scratch) hands the
+    event back: the events in use (created - pooled; the session's context
+    has a well-filled pool, so `events_created` alone would not move) are as
+    many after every failing batch as before, repeating it creates no further
+    event, and the same batch without the override is correct."""
+    from quill_amd._lib import QuillGpuError
+    srs = srs_of("c20")
+    vec, expected = case(dev, "random")
+    ns = [1027, 513]
+
+    def failing_batch():
+        with env(**{k: None for k in OVERRIDES}), env(QG_SORT_BLOCK_A="384", QG_MSM_PIPE=None):
+            with pytest.raises(QuillGpuError) as ei:
+                srs.msm_dev_batch([vec, vec], ns)
+        assert ei.value.code == -1  # QG_ERR_INVALID
+
+    def in_use():
+        return dev.counter("events_created") - dev.counter("events_pooled")
+
+    before = in_use()
+    failing_batch()
+    assert in_use() == before
+    created = dev.counter("events_created")
+    for _ in range(3):
+        failing_batch()
+        assert in_use() == before
+    assert dev.counter("events_created") == created
+    with env(**{k: None for k in OVERRIDES}), env(QG_MSM_PIPE=None):
+        assert srs.msm_dev_batch([vec, vec], ns) == [expected(n) for n in ns]
