@@ -504,19 +504,56 @@ int qg_logup_column_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const qg_
  * undefined.  out_m must not alias an input column (QG_ERR_INVALID).
  * Limits: 1 <= ncols <= 16, 1 <= tab_len < 2^31, 1 <= src_len < 2^32: zero
  * lengths, null pointers and buffers shorter than their stated length return
- * QG_ERR_INVALID, anything over the caps QG_ERR_UNSUPPORTED.  A context with a
- * communicator attached (sharded) returns QG_ERR_UNSUPPORTED.
+ * QG_ERR_INVALID, anything over the caps QG_ERR_UNSUPPORTED.  This host-pointer
+ * entry returns QG_ERR_UNSUPPORTED on a context with a communicator attached
+ * (sharded): a sharded caller holds device blocks, see the _dev entry.
  * QG_LOOKUP_HASH_BITS=<b> (read per call) keeps only the low b bits of the row
  * hash (b = 0: one probe chain; a test switch, the result does not change). */
 int qg_lookup_multiplicities(qg_ctx* ctx, uint32_t ncols,
                              const uint64_t* const* src_cols, size_t src_len,
                              const uint64_t* const* tab_cols, size_t tab_len,
                              uint64_t* out_m, int64_t* first_missing);
-/* Same with device-resident columns and output. */
+/* Same with device-resident columns and output.
+ * With a communicator attached (world W, this rank r) the call is collective:
+ * `src_len` / `tab_len` are this rank's block lengths and every rank passes the
+ * same ncols, src_len and tab_len.  Global source row r*src_len + i and global
+ * table row r*tab_len + j are the rows of the concatenated blocks (the layout of
+ * a sharded VirtualPolynomialStore); out_m receives this rank's block
+ * m[r*tab_len .. (r+1)*tab_len) of the global column, which is the same function
+ * of the inputs as on one context: a tuple at several global rows is counted
+ * whole at the lowest one, also when those rows sit on different ranks.  The
+ * table is replicated on every rank (one allgather per column) and the source
+ * stays where it is; the counters travel in one all-to-all: at most ncols + 3
+ * collectives per call ("lookup_collectives" of qg_ctx_counter).  The caps are
+ * global: W*tab_len >= 2^31 or W*src_len >= 2^32 is QG_ERR_UNSUPPORTED.  When
+ * any rank's own arguments fail their checks, or the ranks pass different
+ * ncols / src_len / tab_len, EVERY rank returns QG_ERR_INVALID (a rank joins the
+ * first exchange even then, so none is left waiting).  A source row in no table
+ * row: every rank returns QG_ERR_ASSERT with the lowest GLOBAL source row in
+ * *first_missing and in qg_last_error; a probe-sequence error on any rank is
+ * QG_ERR_DEVICE on every rank. */
 int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols,
                                  const qg_buf* const* src_cols, size_t src_len,
                                  const qg_buf* const* tab_cols, size_t tab_len,
                                  qg_buf* out_m, int64_t* first_missing);
+
+/* Column materialiser: out[x] = h(tables[.][x]) for every row x of the
+ * hypercube, h a postfix expression over `tables` (the encoding of the sumcheck
+ * and Logup entries above) - what the reference's LookupProof::prove reads
+ * through get_expr for a column that is not a plain input
+ * (hyperplonk/src/piops/lookup.rs:51-59), e.g. a packed column a + 256 b.  Rows
+ * are 2^nvars; with a communicator attached nvars is global and each rank passes
+ * and receives its 2^(nvars - log2(world)) block (no exchange).  Output words
+ * are canonical Montgomery (< r), as qg_lookup_multiplicities compares them.
+ * Limits: <= 128 monomials, <= 512 factors, <= 64 distinct tables; beyond them
+ * QG_ERR_UNSUPPORTED (there is no interpreter fallback).  `out` must not overlap
+ * a table (QG_ERR_INVALID), as are null pointers and short buffers. */
+int qg_expr_column(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const uint64_t* const* tables,
+                   const qg_expr_op* prog, size_t len, const uint64_t* consts, size_t nconsts,
+                   uint64_t* out);
+int qg_expr_column_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
+                       const qg_buf* const* tables, const qg_expr_op* prog, size_t len,
+                       const uint64_t* consts, size_t nconsts, qg_buf* out);
 
 /* Circuit::check_constraints for one constraint expression
  * (hyperplonk/src/frontend/transition_circuit.rs:153-172): `first_row`
@@ -569,7 +606,9 @@ int qg_trace_marker(qg_ctx* ctx, uint32_t tag);
  * returned events was empty (constant once a repeated workload is warm).
  * "events_pooled": events resting in that pool now; created - pooled is the
  * number in use, which a call leaves as it found it (an event that a failed
- * call did not hand back shows here, long before the pool runs dry). */
+ * call did not hand back shows here, long before the pool runs dry).
+ * "lookup_collectives": collectives issued by qg_lookup_multiplicities_dev on
+ * this (sharded) context, at most ncols + 3 per call. */
 int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value);
 /* DensePolynomial::evaluate (pcs/src/kzg.rs:78) on a device vector:
  * out = sum_{i < n} poly[i] * x^(shift + i) (Montgomery in and out), by the

@@ -289,6 +289,7 @@ int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value) {
            : n == "open_check_failures"    ? ctx->open_check_failures
            : n == "events_created"         ? ctx->events_created
            : n == "events_pooled"          ? ctx->event_pool.size()
+           : n == "lookup_collectives"     ? ctx->lookup_collectives
                                            : 0;
   return QG_OK;
 }

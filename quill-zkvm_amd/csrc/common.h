@@ -119,6 +119,9 @@ struct qg_ctx {
   // the next opening call, consumed by the first site of its kind
   uint32_t open_fault_armed = 0, open_fault_live = 0;
   uint64_t open_fault_value = 0;
+  // collectives issued by the sharded lookup multiplicities (lookup.hip): at
+  // most ncols + 3 per call
+  uint64_t lookup_collectives = 0;
 
   // every stream of this context, synchronized (scratch release, destroy)
   static void drain_streams(void* self) { QG_HIP(static_cast<qg_ctx*>(self)->drain_streams_quiet()); }

@@ -31,6 +31,10 @@
 //    the call returns QG_ERR_ASSERT (the reference panics in unwrap()).
 //  * Per-block sums of the outputs feed SetInclusionProof's claimed sums
 //    (set_inclusion.rs:162-166, 193-197) without a second pass.
+//  * k_expr_column (qg_expr_column[_dev]) evaluates one compiled expression per
+//    row into a column of canonical words: a lookup column that is not a plain
+//    input (lookup.rs:51-59) is materialised by it before the multiplicities
+//    are counted (lookup.hip compares 32-byte words).
 #include <string.h>
 
 #include <vector>
@@ -538,6 +542,16 @@ __global__ __launch_bounds__(256) void k_expr_first_nonzero(const LgDev* __restr
   if (!is_zero29(v)) atomicMin(first, (unsigned long long)row);
 }
 
+// out[row] = h(row) (slot 0 compiled at scale 256, so the value is in arkworks
+// Montgomery form), canonical: the lookup count compares the 32-byte words.
+// One table read per factor and one 32-byte write per row.
+__global__ __launch_bounds__(256) void k_expr_column(const LgDev* __restrict__ g, size_t n,
+                                                     Fr* __restrict__ out) {
+  const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  out[row] = from29(canon29(lg_eval(g, 0, row)));
+}
+
 // ---------------------------------------------------------------- host
 static Fr lg_plain_mul(const Fr& x, const Fr& y) { return from_mont(to_mont(x) * to_mont(y)); }
 static L9 lg_l9(const Fr& plain) {
@@ -762,10 +776,90 @@ static Fr logup_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const std::ve
   return logup_total(ctx, d_res, d_err);
 }
 
+// [a, a + na) and [b, b + nb) share an element
+template <class T>
+static bool lg_overlap(const T* a, size_t na, const T* b, size_t nb) {
+  return a < b + nb && b < a + na;
+}
+
+// d_out[x] = h(tabs[.][x]) over this rank's n rows, canonical Montgomery words.
+// Only the compiled image: an expression beyond lg_compile's limits (128
+// monomials, 512 factors, 64 tables) is QG_ERR_UNSUPPORTED, not interpreted.
+static void expr_column_run(qg_ctx* ctx, size_t n, uint32_t ntables,
+                            const std::vector<const Fr*>& tabs, const qg_expr_op* prog, size_t len,
+                            const uint64_t* consts, size_t nconsts, Fr* d_out) {
+  LgDev img;
+  memset(&img, 0, sizeof(img));
+  std::vector<uint32_t> used;
+  uint32_t nfac = 0;
+  // scale 256 + 5f: the value comes out in arkworks form (x 2^256)
+  lg_compile(img, 0, compile_program(prog, len, consts, nconsts, ntables), Fr::zero(), false, 256,
+             used, nfac);
+  for (size_t s = 0; s < used.size(); s++) img.tab[s] = tabs[used[s]];
+  QG_HIP(hipSetDevice(ctx->device));
+  uint8_t* io = ctx->scratch_as<uint8_t>("lg_io", sizeof(LgDev) + 64);
+  LgDev* d_img = reinterpret_cast<LgDev*>(io);
+  QG_HIP(hipMemcpyAsync(d_img, &img, sizeof(img), hipMemcpyHostToDevice, ctx->stream));
+  {
+    QgTimed tm(ctx, "expr_column");
+    hipLaunchKernelGGL(k_expr_column, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_img, n,
+                       d_out);
+    QG_LAUNCH_CHECK();
+  }
+  ctx->sync();
+}
+
 }  // namespace qg
 
 // ---------------------------------------------------------------- C-ABI
 extern "C" {
+
+int qg_expr_column(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const uint64_t* const* tables,
+                   const qg_expr_op* prog, size_t len, const uint64_t* consts, size_t nconsts,
+                   uint64_t* out) {
+  return qg_guard(ctx, [&] {
+    QG_CHECK(ctx && prog && len && out, QG_ERR_INVALID, "null argument");
+    QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
+    QG_CHECK(nconsts == 0 || consts, QG_ERR_INVALID, "null constants");
+    const size_t n = lg_local_size(ctx, nvars);
+    for (uint32_t i = 0; i < ntables; i++) {
+      QG_CHECK(tables[i] != nullptr, QG_ERR_INVALID, "null table");
+      QG_CHECK(!lg_overlap(out, 4 * n, tables[i], 4 * n), QG_ERR_INVALID,
+               "output aliases an input table");
+    }
+    QG_HIP(hipSetDevice(ctx->device));
+    Fr* d = ctx->scratch_as<Fr>("lg_in", n * ((size_t)ntables + 1));
+    std::vector<const Fr*> tabs;
+    for (uint32_t i = 0; i < ntables; i++) {
+      fr_upload(ctx, d + n * i, tables[i], n);
+      tabs.push_back(d + n * i);
+    }
+    Fr* d_out = d + n * ntables;
+    expr_column_run(ctx, n, ntables, tabs, prog, len, consts, nconsts, d_out);
+    fr_download(ctx, out, d_out, n);
+    ctx->sync();
+  });
+}
+
+int qg_expr_column_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const qg_buf* const* tables,
+                       const qg_expr_op* prog, size_t len, const uint64_t* consts, size_t nconsts,
+                       qg_buf* out) {
+  return qg_guard(ctx, [&] {
+    QG_CHECK(ctx && prog && len && out, QG_ERR_INVALID, "null argument");
+    QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
+    QG_CHECK(nconsts == 0 || consts, QG_ERR_INVALID, "null constants");
+    const size_t n = lg_local_size(ctx, nvars);
+    QG_CHECK(out->n >= n, QG_ERR_INVALID, "output buffer too short");
+    std::vector<const Fr*> tabs;
+    for (uint32_t i = 0; i < ntables; i++) {
+      QG_CHECK(tables[i] && tables[i]->n >= n, QG_ERR_INVALID, "table buffer missing or too short");
+      QG_CHECK(!lg_overlap(out->d, n, tables[i]->d, n), QG_ERR_INVALID,
+               "output aliases an input table");
+      tabs.push_back(tables[i]->d);
+    }
+    expr_column_run(ctx, n, ntables, tabs, prog, len, consts, nconsts, out->d);
+  });
+}
 
 int qg_logup_column(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const uint64_t* const* tables,
                     const qg_expr_op* h_prog, size_t h_len, const uint64_t* h_consts,

@@ -34,6 +34,26 @@
 //  * QG_LOOKUP_HASH_BITS=<b> (read per call) keeps only the low b bits of the
 //    hash: b = 0 sends every row down one probe chain (tests).
 //    QG_LOOKUP_BLOCKS=<k> caps the count kernel's grid.
+//
+// Sharded contexts (qg_lookup_multiplicities_dev only; world W, rank r): every
+// rank holds one block of each column, global row = rank x block length + local
+// row, and receives its block of the global m.  The table is replicated, the
+// source stays where it is (lookup_run_sharded):
+//   1. header allgather (32 B per rank: status of the local argument checks,
+//      ncols, src_len, tab_len) - a rank whose checks failed still joins, so all
+//      ranks leave together and none waits in a later collective;
+//   2. one allgather per table column into one global column (rank-major order
+//      is global row order);
+//   3. k_lookup_build over the gathered table (global length), k_lookup_count
+//      over the local source rows into W x tab_len counters - both unchanged,
+//      so the lowest GLOBAL row of a duplicated tuple takes the count;
+//   4. one all-to-all of tab_len x 4 bytes (slice d of the counters to rank d),
+//      k_lookup_finish_parts sums the W slices received into m;
+//   5. one allgather of (lowest missing global row, error word): min and OR.
+// ncols + 3 collectives per call ("lookup_collectives" of qg_ctx_counter).
+// What bounds it: W x tab_len < 2^31 rows of table on every rank (32 x ncols
+// bytes each, plus 12 bytes of slots and counters); a table as large as the
+// source would want a hash-partitioned table instead.
 #include <stdlib.h>
 
 #include <string>
@@ -215,6 +235,21 @@ __global__ __launch_bounds__(LK_BLOCK) void k_lookup_finish(const uint32_t* __re
   out[j] = to_mont(x);
 }
 
+// sharded: m[j] = Fr::from(sum over source ranks s of recv[s * tab_len + j]),
+// recv = the counters every rank held for this rank's block of the table.  The
+// sum is at most the global number of source rows, W x src_len < 2^32
+// (lookup_check_global), so it fits the 32-bit word.
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_finish_parts(
+    const uint32_t* __restrict__ recv, uint32_t world, uint32_t tab_len, Fr* __restrict__ out) {
+  const uint64_t j = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (j >= tab_len) return;
+  uint32_t c = 0;
+  for (uint32_t s = 0; s < world; s++) c += recv[(uint64_t)s * tab_len + j];
+  Fr x = Fr::zero();
+  x.v[0] = c;
+  out[j] = to_mont(x);
+}
+
 // QG_LOOKUP_HASH_BITS=<b>, read per call: keep the low b bits of the hash
 static uint32_t lookup_hash_mask() {
   const char* hb = getenv("QG_LOOKUP_HASH_BITS");
@@ -232,8 +267,7 @@ static size_t lookup_count_blocks(qg_ctx* ctx) {
   return k > 0 ? (size_t)k : 2 * (size_t)ctx->num_cus();
 }
 
-static void lookup_check_lengths(const qg_ctx* ctx, uint32_t ncols, size_t src_len,
-                                 size_t tab_len) {
+static void lookup_check_lengths(uint32_t ncols, size_t src_len, size_t tab_len) {
   QG_CHECK(ncols >= 1 && src_len >= 1 && tab_len >= 1, QG_ERR_INVALID,
            "lookup multiplicities need at least one column, source row and table row");
   QG_CHECK(ncols <= LK_MAXCOLS, QG_ERR_UNSUPPORTED, "lookup multiplicities: more than 16 columns");
@@ -241,14 +275,17 @@ static void lookup_check_lengths(const qg_ctx* ctx, uint32_t ncols, size_t src_l
            "lookup multiplicities: table of 2^31 rows or more");
   QG_CHECK((uint64_t)src_len < (1ull << 32), QG_ERR_UNSUPPORTED,
            "lookup multiplicities: 2^32 source rows or more");
-  QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
-           "lookup multiplicities are not supported on a sharded context (communicator attached)");
 }
 
-// d_out[j] = multiplicity of table row j; returns the lowest source row that is
-// in no table row, or -1
-static int64_t lookup_run(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t src_len,
-                          const LkCols& tab, size_t tab_len, Fr* d_out) {
+// Slots, counters and state words of one call, all filled here (nothing of an
+// earlier call survives), then the build over `tab` (tab_len rows) and the count
+// of the src_len rows of `src` into d_count[0 .. tab_len).
+struct LkWork {
+  uint32_t* d_count;
+  LkState* d_st;
+};
+static LkWork lookup_build_count(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t src_len,
+                                 const LkCols& tab, size_t tab_len) {
   uint64_t cap = 2;
   while (cap < 2 * (uint64_t)tab_len) cap <<= 1;
   const uint32_t hash_mask = lookup_hash_mask();
@@ -279,17 +316,117 @@ static int64_t lookup_run(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t
                          tab, ncols, (uint64_t)src_len, tl, d_slots, cap, hash_mask, d_count, d_st);
     QG_LAUNCH_CHECK();
   }
+  return {d_count, d_st};
+}
+
+// d_out[j] = multiplicity of table row j; returns the lowest source row that is
+// in no table row, or -1
+static int64_t lookup_run(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t src_len,
+                          const LkCols& tab, size_t tab_len, Fr* d_out) {
+  const LkWork w = lookup_build_count(ctx, ncols, src, src_len, tab, tab_len);
   {
     QgTimed tm(ctx, "lookup_finish");
     hipLaunchKernelGGL(k_lookup_finish, dim3(div_up(tab_len, LK_BLOCK)), dim3(LK_BLOCK), 0,
-                       ctx->stream, d_count, tl, d_out);
+                       ctx->stream, w.d_count, (uint32_t)tab_len, d_out);
     QG_LAUNCH_CHECK();
   }
   LkState h;
-  QG_HIP(hipMemcpyAsync(&h, d_st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  QG_HIP(hipMemcpyAsync(&h, w.d_st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   ctx->sync();
   QG_CHECK(!h.err, QG_ERR_DEVICE, "lookup multiplicities: probe sequence exhausted");
   return h.first_missing >= (unsigned long long)src_len ? -1 : (int64_t)h.first_missing;
+}
+
+// ---- sharded flow ----------------------------------------------------------
+// what every rank tells the others before any other collective
+struct LkHeader {
+  int32_t status;  // of this rank's local argument checks
+  uint32_t ncols;
+  uint64_t src_len, tab_len;
+  uint64_t pad;
+};
+static_assert(sizeof(LkHeader) == 32, "lookup header is 32 bytes per rank");
+// ... and after the count
+struct LkResult {
+  unsigned long long first_missing;  // global source row, ~0 when none
+  uint32_t err, pad;
+};
+
+// world x len >= limit, without overflow
+static bool lk_global_over(uint64_t world, uint64_t len, uint64_t limit) {
+  return len >= (limit + world - 1) / world;
+}
+
+// the caps, on the global lengths; every rank evaluates them on the agreed
+// header values, so all ranks take the same branch
+static void lookup_check_global(const qg_ctx* ctx, uint32_t ncols, size_t src_len, size_t tab_len) {
+  QG_CHECK(ncols <= LK_MAXCOLS, QG_ERR_UNSUPPORTED, "lookup multiplicities: more than 16 columns");
+  QG_CHECK(!lk_global_over(ctx->world, tab_len, 1ull << 31), QG_ERR_UNSUPPORTED,
+           "lookup multiplicities: global table of 2^31 rows or more");
+  // also what keeps a row's count inside 32 bits (k_lookup_finish_parts)
+  QG_CHECK(!lk_global_over(ctx->world, src_len, 1ull << 32), QG_ERR_UNSUPPORTED,
+           "lookup multiplicities: 2^32 global source rows or more");
+}
+
+// every rank's `mine`, in rank order; one collective
+template <class T>
+static std::vector<T> lookup_exchange(qg_ctx* ctx, const T& mine) {
+  const size_t W = (size_t)ctx->world;
+  uint8_t* d = ctx->scratch_as<uint8_t>("lk_hdr", sizeof(LkHeader) * (W + 1));
+  static_assert(sizeof(T) <= sizeof(LkHeader), "exchange slot");
+  QG_HIP(hipMemcpyAsync(d, &mine, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  comm_allgather_bytes(ctx, d, d + sizeof(LkHeader), sizeof(T));
+  ctx->lookup_collectives++;
+  std::vector<T> all(W);
+  QG_HIP(hipMemcpyAsync(all.data(), d + sizeof(LkHeader), sizeof(T) * W, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  ctx->sync();
+  return all;
+}
+
+// this rank's block of the global m into d_out; returns the lowest GLOBAL source
+// row that is in no table row, or -1 (the same value on every rank)
+static int64_t lookup_run_sharded(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t src_len,
+                                  const LkCols& tab_blocks, size_t tab_len, Fr* d_out) {
+  const size_t W = (size_t)ctx->world, G = W * tab_len;
+  Fr* d_gtab = ctx->scratch_as<Fr>("lk_gtab", (size_t)ncols * G);
+  uint32_t* d_recv = ctx->scratch_as<uint32_t>("lk_recv", G);
+  LkCols tab{};
+  {
+    QgTimed tm(ctx, "lookup_gather");
+    for (uint32_t c = 0; c < ncols; c++) {
+      Fr* g = d_gtab + (size_t)c * G;
+      comm_allgather_bytes(ctx, tab_blocks.c[c], g, tab_len * sizeof(Fr));
+      ctx->lookup_collectives++;
+      tab.c[c] = g;
+    }
+  }
+  const LkWork w = lookup_build_count(ctx, ncols, src, src_len, tab, G);
+  {
+    QgTimed tm(ctx, "lookup_exchange");
+    comm_alltoall_bytes(ctx, w.d_count, d_recv, tab_len * sizeof(uint32_t));
+    ctx->lookup_collectives++;
+  }
+  {
+    QgTimed tm(ctx, "lookup_finish");
+    hipLaunchKernelGGL(k_lookup_finish_parts, dim3(div_up(tab_len, LK_BLOCK)), dim3(LK_BLOCK), 0,
+                       ctx->stream, d_recv, (uint32_t)W, (uint32_t)tab_len, d_out);
+    QG_LAUNCH_CHECK();
+  }
+  LkState h;
+  QG_HIP(hipMemcpyAsync(&h, w.d_st, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  LkResult mine{~0ull, h.err, 0};
+  if (h.first_missing < (unsigned long long)src_len)
+    mine.first_missing = (unsigned long long)ctx->rank * src_len + h.first_missing;
+  unsigned long long first = ~0ull;
+  uint32_t err = 0;
+  for (const LkResult& r : lookup_exchange(ctx, mine)) {
+    first = std::min(first, r.first_missing);
+    err |= r.err;
+  }
+  QG_CHECK(!err, QG_ERR_DEVICE, "lookup multiplicities: probe sequence exhausted");
+  return first == ~0ull ? -1 : (int64_t)first;
 }
 
 static void lookup_report(int64_t miss, int64_t* first_missing) {
@@ -304,6 +441,30 @@ static bool lk_overlap(const T* a, size_t na, const T* b, size_t nb) {
   return a < b + nb && b < a + na;
 }
 
+// the _dev entry's checks of this rank's own arguments; `check_buffers` is
+// false when the lengths are over a cap (no buffer of such a length exists)
+static void lookup_check_dev_args(uint32_t ncols, const qg_buf* const* src_cols, size_t src_len,
+                                  const qg_buf* const* tab_cols, size_t tab_len,
+                                  const qg_buf* out_m, bool check_buffers, LkCols& src,
+                                  LkCols& tab) {
+  QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
+  QG_CHECK(ncols >= 1 && src_len >= 1 && tab_len >= 1, QG_ERR_INVALID,
+           "lookup multiplicities need at least one column, source row and table row");
+  if (!check_buffers) return;
+  QG_CHECK(out_m->n >= tab_len, QG_ERR_INVALID, "output buffer too short");
+  for (uint32_t c = 0; c < ncols; c++) {
+    QG_CHECK(src_cols[c] && src_cols[c]->n >= src_len, QG_ERR_INVALID,
+             "source column buffer missing or too short");
+    QG_CHECK(tab_cols[c] && tab_cols[c]->n >= tab_len, QG_ERR_INVALID,
+             "table column buffer missing or too short");
+    QG_CHECK(!lk_overlap(out_m->d, tab_len, src_cols[c]->d, src_len) &&
+                 !lk_overlap(out_m->d, tab_len, tab_cols[c]->d, tab_len),
+             QG_ERR_INVALID, "output aliases an input column");
+    src.c[c] = src_cols[c]->d;
+    tab.c[c] = tab_cols[c]->d;
+  }
+}
+
 }  // namespace qg
 
 // ---------------------------------------------------------------- C-ABI
@@ -315,7 +476,11 @@ int qg_lookup_multiplicities(qg_ctx* ctx, uint32_t ncols, const uint64_t* const*
   if (!ctx) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] {
     QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
-    lookup_check_lengths(ctx, ncols, src_len, tab_len);
+    lookup_check_lengths(ncols, src_len, tab_len);
+    // a sharded caller holds device blocks: only the _dev entry has the sharded form
+    QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
+             "lookup multiplicities from host pointers are not supported on a sharded context "
+             "(communicator attached): use qg_lookup_multiplicities_dev");
     for (uint32_t c = 0; c < ncols; c++) {
       QG_CHECK(src_cols[c] && tab_cols[c], QG_ERR_INVALID, "null column");
       QG_CHECK(!lk_overlap(out_m, 4 * tab_len, src_cols[c], 4 * src_len) &&
@@ -347,24 +512,44 @@ int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols, const qg_buf* cons
                                  qg_buf* out_m, int64_t* first_missing) {
   if (!ctx) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] {
-    QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
-    lookup_check_lengths(ctx, ncols, src_len, tab_len);
-    QG_CHECK(out_m->n >= tab_len, QG_ERR_INVALID, "output buffer too short");
     LkCols src{}, tab{};
-    for (uint32_t c = 0; c < ncols; c++) {
-      QG_CHECK(src_cols[c] && src_cols[c]->n >= src_len, QG_ERR_INVALID,
-               "source column buffer missing or too short");
-      QG_CHECK(tab_cols[c] && tab_cols[c]->n >= tab_len, QG_ERR_INVALID,
-               "table column buffer missing or too short");
-      QG_CHECK(!lk_overlap(out_m->d, tab_len, src_cols[c]->d, src_len) &&
-                   !lk_overlap(out_m->d, tab_len, tab_cols[c]->d, tab_len),
-               QG_ERR_INVALID, "output aliases an input column");
-      src.c[c] = src_cols[c]->d;
-      tab.c[c] = tab_cols[c]->d;
+    if (!ctx->sharded) {
+      QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
+      lookup_check_lengths(ncols, src_len, tab_len);
+      lookup_check_dev_args(ncols, src_cols, src_len, tab_cols, tab_len, out_m, true, src, tab);
+      QG_HIP(hipSetDevice(ctx->device));
+      if (first_missing) *first_missing = -1;
+      const int64_t miss = lookup_run(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
+      lookup_report(miss, first_missing);
+      return;
     }
+    // sharded: lengths are this rank's block lengths.  The local checks never
+    // end the call on their own: their status travels in the header, so that
+    // every rank leaves here together or goes on together.
     QG_HIP(hipSetDevice(ctx->device));
+    LkHeader mine{QG_OK, ncols, (uint64_t)src_len, (uint64_t)tab_len, 0};
+    std::string why;
+    try {
+      const bool under = ncols <= LK_MAXCOLS && !lk_global_over(ctx->world, tab_len, 1ull << 31) &&
+                         !lk_global_over(ctx->world, src_len, 1ull << 32);
+      lookup_check_dev_args(ncols, src_cols, src_len, tab_cols, tab_len, out_m, under, src, tab);
+    } catch (const Error& e) {
+      mine.status = e.code;
+      why = e.what();
+    }
+    const std::vector<LkHeader> all = lookup_exchange(ctx, mine);
+    if (mine.status != QG_OK) throw Error(QG_ERR_INVALID, why);
+    for (size_t r = 0; r < all.size(); r++) {
+      QG_CHECK(all[r].status == QG_OK, QG_ERR_INVALID,
+               "lookup multiplicities: rank " + std::to_string(r) + " failed its argument checks");
+      QG_CHECK(all[r].ncols == ncols && all[r].src_len == src_len && all[r].tab_len == tab_len,
+               QG_ERR_INVALID,
+               "lookup multiplicities: rank " + std::to_string(r) +
+                   " passed another ncols, src_len or tab_len (every rank passes the same)");
+    }
+    lookup_check_global(ctx, ncols, src_len, tab_len);
     if (first_missing) *first_missing = -1;
-    const int64_t miss = lookup_run(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
+    const int64_t miss = lookup_run_sharded(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
     lookup_report(miss, first_missing);
   });
 }

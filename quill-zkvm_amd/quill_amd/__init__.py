@@ -12,7 +12,8 @@ from .pcs import (KZG, EvaluationClaim, InnerProductProof, KZGOpeningProof,  # n
                   MLEvalProof, g2_generator, g2_mul, pairing)
 from .transcript import Transcript  # noqa: F401
 from .logup import (LookupMode, LookupProof, MultisetEqualityProof,  # noqa: F401
-                    PermutationCheckProof, SetInclusionProof, lookup_multiplicities)
+                    PermutationCheckProof, SetInclusionProof, expr_column,
+                    lookup_multiplicities)
 from .frontend import StateCell, TransitionCircuit, TransitionCircuitTarget  # noqa: F401
 from .proof import (HyperPlonk, HyperPlonkProof, TracePK, TraceProof, TraceVK,  # noqa: F401
                     TraceWitness)

@@ -168,6 +168,10 @@ PROTOTYPES = {
                                            SZ, U64P, C.POINTER(C.c_int64)]),
     "qg_lookup_multiplicities_dev": (C.c_int, [P, C.c_uint32, C.POINTER(P), SZ, C.POINTER(P), SZ,
                                                P, C.POINTER(C.c_int64)]),
+    "qg_expr_column": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(U64P), C.POINTER(ExprOp), SZ,
+                                 U64P, SZ, U64P]),
+    "qg_expr_column_dev": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(P), C.POINTER(ExprOp),
+                                     SZ, U64P, SZ, P]),
     "qg_expr_first_nonzero_dev": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(P),
                                             C.POINTER(ExprOp), SZ, U64P, SZ,
                                             C.POINTER(C.c_int64)]),

@@ -72,56 +72,103 @@ def logup_column_device(dev: Device, num_vars: int, tables, h_expr: VirtualPolyE
     return fr_from_mont_limbs(list(s))
 
 
-def _input_columns(store: VirtualPolynomialStore, cols):
-    """table indices of virtual polynomials that are plain Input(k) expressions"""
-    out = []
-    for c in cols:
-        e = store.virtual_polys[c]
-        if e.kind != "in":
-            raise ValueError("lookup_multiplicities: column %d is not a plain Input(k) expression "
-                             "(there is no column materialiser)" % c)
-        out.append(e.args[0])
-    return out
-
-
-def lookup_multiplicities(source_store: VirtualPolynomialStore, source_cols,
-                          dest_store: VirtualPolynomialStore, dest_cols, dev: Device = None):
-    """The multiplicity column of a Logup lookup (what lookup.rs:186-193 builds
-    by hand): m[j] = number of source rows equal to table row j, a row being the
-    tuple of its columns; a tuple the table holds at several rows is counted at
-    the lowest of them.  `source_cols` / `dest_cols` are virtual-polynomial
-    indices that must be plain Input(k) expressions (ValueError otherwise).
-    Host stores return a list of ints (qg_lookup_multiplicities), device stores
-    a DeviceVec (qg_lookup_multiplicities_dev).  A source row that is in no
-    table row raises QuillGpuError(QG_ERR_ASSERT) naming the lowest such row."""
-    if len(source_cols) != len(dest_cols):
-        raise ValueError("The number of source and destination columns must be equal")
-    if source_store.on_device != dest_store.on_device:
-        raise ValueError("lookup_multiplicities: source and destination stores must both be "
-                         "host stores or both device stores")
-    sc, dc = _input_columns(source_store, source_cols), _input_columns(dest_store, dest_cols)
-    k = len(sc)
-    ns, nt = source_store.local_len, dest_store.local_len
-    miss = C.c_int64(-1)
-    if source_store.on_device:
-        d = dest_store.dev
-        out = DeviceVec(d, nt, pooled=True)
-        sp = (C.c_void_p * max(k, 1))(*[source_store.polynomials[i].h.value for i in sc])
-        tp = (C.c_void_p * max(k, 1))(*[dest_store.polynomials[i].h.value for i in dc])
+def expr_column(store: VirtualPolynomialStore, h, dev: Device = None):
+    """h(x) for every row of `store` (the column materialiser, qg_expr_column):
+    `h` is a virtual-polynomial index.  Returns the evaluations in the store's
+    residency: a pooled DeviceVec of the store's local length (this rank's block
+    on a sharded device) or a list of ints.  An expression beyond the compiled
+    image (128 monomials, 512 factors, 64 tables) raises
+    QuillGpuError(QG_ERR_UNSUPPORTED)."""
+    prog, plen, carr, nc = _program_c(store.virtual_polys[h])
+    if store.on_device:
+        d = store.dev
+        out = DeviceVec(d, store.local_len, pooled=True)
+        ptrs = (C.c_void_p * max(len(store.polynomials), 1))(*[t.h for t in store.polynomials])
         try:
-            check(lib().qg_lookup_multiplicities_dev(d.h, k, sp, ns, tp, nt, out.h,
-                                                     C.byref(miss)), d.h)
+            check(lib().qg_expr_column_dev(d.h, store.num_vars, len(store.polynomials), ptrs, prog,
+                                           plen, u64p(carr), nc, out.h), d.h)
         except Exception:
             out.close()
             raise
         return out
     dev = dev or _default_device()
-    sa, sp = _tables_c([source_store.polynomials[i] for i in sc])
-    ta, tp = _tables_c([dest_store.polynomials[i] for i in dc])
-    out = np.zeros((max(nt, 1), 4), dtype=np.uint64)
-    check(lib().qg_lookup_multiplicities(dev.h, k, sp, ns, tp, nt, u64p(out), C.byref(miss)),
-          dev.h)
-    return fr_list(out[:nt])
+    arrs, ptrs = _tables_c(store.polynomials)
+    out = np.zeros((1 << store.num_vars, 4), dtype=np.uint64)
+    check(lib().qg_expr_column(dev.h, store.num_vars, len(arrs), ptrs, prog, plen, u64p(carr), nc,
+                               u64p(out)), dev.h)
+    return fr_list(out)
+
+
+def _lookup_columns(store: VirtualPolynomialStore, cols, materialise: bool, dev: Device, temps):
+    """the tables behind virtual polynomials `cols`: Input(k) is table k in
+    place; anything else is evaluated into a temporary (appended to `temps`)
+    when `materialise`, and a ValueError otherwise"""
+    out = []
+    for c in cols:
+        e = store.virtual_polys[c]
+        if e.kind == "in":
+            out.append(store.polynomials[e.args[0]])
+        elif materialise:
+            t = expr_column(store, c, dev)
+            temps.append(t)
+            out.append(t)
+        else:
+            raise ValueError("lookup_multiplicities: column %d is not a plain Input(k) expression "
+                             "(pass materialise=True to evaluate it into a temporary)" % c)
+    return out
+
+
+def lookup_multiplicities(source_store: VirtualPolynomialStore, source_cols,
+                          dest_store: VirtualPolynomialStore, dest_cols, dev: Device = None,
+                          materialise: bool = False):
+    """The multiplicity column of a Logup lookup (what lookup.rs:186-193 builds
+    by hand): m[j] = number of source rows equal to table row j, a row being the
+    tuple of its columns; a tuple the table holds at several rows is counted at
+    the lowest of them.  `source_cols` / `dest_cols` are virtual-polynomial
+    indices.  Plain Input(k) columns are read in place; any other expression is a
+    ValueError unless `materialise` is set, and then it is evaluated into a
+    temporary (expr_column) that is released after the count - nothing is
+    allocated into a store.
+    Host stores return a list of ints (qg_lookup_multiplicities), device stores
+    a DeviceVec (qg_lookup_multiplicities_dev).  On sharded device stores the
+    call is collective: every rank passes its blocks and receives its block of
+    the global column.  A source row that is in no table row raises
+    QuillGpuError(QG_ERR_ASSERT) naming the lowest such (global) row."""
+    if len(source_cols) != len(dest_cols):
+        raise ValueError("The number of source and destination columns must be equal")
+    if source_store.on_device != dest_store.on_device:
+        raise ValueError("lookup_multiplicities: source and destination stores must both be "
+                         "host stores or both device stores")
+    temps = []
+    try:
+        sc = _lookup_columns(source_store, source_cols, materialise, dev, temps)
+        dc = _lookup_columns(dest_store, dest_cols, materialise, dev, temps)
+        k = len(sc)
+        ns, nt = source_store.local_len, dest_store.local_len
+        miss = C.c_int64(-1)
+        if source_store.on_device:
+            d = dest_store.dev
+            out = DeviceVec(d, nt, pooled=True)
+            sp = (C.c_void_p * max(k, 1))(*[v.h.value for v in sc])
+            tp = (C.c_void_p * max(k, 1))(*[v.h.value for v in dc])
+            try:
+                check(lib().qg_lookup_multiplicities_dev(d.h, k, sp, ns, tp, nt, out.h,
+                                                         C.byref(miss)), d.h)
+            except Exception:
+                out.close()
+                raise
+            return out
+        dev = dev or _default_device()
+        sa, sp = _tables_c(sc)
+        ta, tp = _tables_c(dc)
+        out = np.zeros((max(nt, 1), 4), dtype=np.uint64)
+        check(lib().qg_lookup_multiplicities(dev.h, k, sp, ns, tp, nt, u64p(out), C.byref(miss)),
+              dev.h)
+        return fr_list(out[:nt])
+    finally:
+        for t in temps:
+            if isinstance(t, DeviceVec):
+                t.close()
 
 
 def _eq_for(store: VirtualPolynomialStore, dev: Device, z):
@@ -358,16 +405,20 @@ class LookupProof:
               dest_cols, multiplicities, transcript: Transcript, pcs):
         """lookup.rs:28-84 -> (proof, (source point, dest point)).
         multiplicities=None: the column is counted on the device
-        (lookup_multiplicities), allocated in `dest_store` and made a virtual
-        polynomial before anything reaches the transcript, so the proof and the
-        transcript are those of a caller who supplied the same column; a source
-        row that is in no table row raises there."""
+        (lookup_multiplicities with materialise=True: columns that are not plain
+        inputs are evaluated into temporaries that no store keeps), allocated in
+        `dest_store` and made a virtual polynomial before anything reaches the
+        transcript, so the proof and the transcript are those of a caller who
+        supplied the same column; a source row that is in no table row raises
+        there.  Sharded device stores: every rank holds its block of each table
+        and calls this collectively."""
         assert len(source_cols) == len(dest_cols), \
             "The number of source and destination columns must be equal"
         n = len(source_cols)
         if multiplicities is None:
             assert n > 0, "Lookup must be applied to at least one column"
-            m = lookup_multiplicities(source_store, source_cols, dest_store, dest_cols, pcs.dev)
+            m = lookup_multiplicities(source_store, source_cols, dest_store, dest_cols, pcs.dev,
+                                      materialise=True)
             multiplicities = dest_store.new_virtual_from_input(dest_store.allocate_polynomial(m))
         transcript.append_u64(n)
         assert n > 0, "Lookup must be applied to at least one column"
@@ -407,5 +458,5 @@ class LookupProof:
 
 
 __all__ = ["LookupMode", "logup_column", "logup_column_device", "lookup_multiplicities",
-           "MultisetEqualityProof",
+           "expr_column", "MultisetEqualityProof",
            "SetInclusionProof", "PermutationCheckProof", "LookupProof", "EvaluationClaim"]
