@@ -102,91 +102,62 @@ static Fr dot_device(qg_ctx* ctx, const Fr* f, const Fr* g, size_t n) {
 }
 
 // ---------------------------------------------------------------- suffix Horner
-// A_k = sum_{i in chunk k} c_i x^(i - start_k)
-__global__ void k_sh_local(const Fr* __restrict__ c, size_t L, Fr x, Fr* __restrict__ A) {
-  size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t s = k * SH_B;
-  if (s >= L) return;
-  size_t e = s + SH_B < L ? s + SH_B : L;
-  Fr acc = Fr::zero();
-  for (size_t i = e; i-- > s;) acc = c[i] + x * acc;
-  A[k] = acc;
-}
-
-// s_i for every i given T_{k+1} (suffix value at the start of chunk k+1)
-__global__ void k_sh_apply(const Fr* __restrict__ c, size_t L, Fr x, const Fr* __restrict__ T,
-                           size_t nchunks, Fr* __restrict__ s_out) {
-  size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t s = k * SH_B;
-  if (s >= L) return;
-  size_t e = s + SH_B < L ? s + SH_B : L;
-  Fr acc = (k + 1 < nchunks) ? T[k + 1] : Fr::zero();
-  for (size_t i = e; i-- > s;) {
-    acc = c[i] + x * acc;
-    s_out[i] = acc;
-  }
-}
-
-// small case: one thread
-__global__ void k_sh_serial(const Fr* __restrict__ c, size_t L, Fr x, Fr* __restrict__ s_out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  Fr acc = Fr::zero();
-  for (size_t i = L; i-- > 0;) {
-    acc = c[i] + x * acc;
-    s_out[i] = acc;
-  }
-}
-
-// s = suffix Horner of c (length L) at x: s_i = c_i + x s_{i+1}
-static void suffix_horner(qg_ctx* ctx, const Fr* c, size_t L, const Fr& x, Fr* s, int depth = 0) {
-  if (L == 0) return;
-  if (L <= SH_B) {
-    hipLaunchKernelGGL(k_sh_serial, dim3(1), dim3(64), 0, ctx->stream, c, L, x, s);
-    QG_LAUNCH_CHECK();
-    return;
-  }
-  const size_t nch = (L + SH_B - 1) / SH_B;
-  Fr* A = ctx->scratch_as<Fr>("sh_A" + std::to_string(depth), nch);
-  Fr* T = ctx->scratch_as<Fr>("sh_T" + std::to_string(depth), nch);
-  hipLaunchKernelGGL(k_sh_local, dim3(div_up(nch, ML_BLOCK)), dim3(ML_BLOCK), 0, ctx->stream, c,
-                     L, x, A);
-  QG_LAUNCH_CHECK();
-  // T_k = A_k + x^B T_{k+1}
-  Fr xb = fpow_small(x, SH_B);
-  suffix_horner(ctx, A, nch, xb, T, depth + 1);
-  hipLaunchKernelGGL(k_sh_apply, dim3(div_up(nch, ML_BLOCK)), dim3(ML_BLOCK), 0, ctx->stream, c, L,
-                     x, T, nch, s);
-  QG_LAUNCH_CHECK();
-}
-
-// Batched form (up to 4 independent scans per launch, blockIdx.y = scan) in
-// 9 x 29-bit limbs (each step c_i + x s_{i+1}: a canonical coefficient plus a
-// product < 2p, so one conditional subtraction keeps s < 2p): the per-chunk Horner chain is the latency of the whole
-// recursion, and the 29-bit multiply's dependent latency is half the 32-bit
-// one's.  x is passed as x 2^261 (plain limbs), so mul29 keeps the arkworks
-// scale of the coefficients.
+// s_i = c_i + x s_{i+1}, blocked: A_k = sum_{i in chunk k} c_i x^(i - start_k)
+// (local pass), T_k = A_k + x^B T_{k+1} (the same scan one level up), then
+// s_i for every i of chunk k from T_{k+1} (apply pass).  Up to SH_J jobs per
+// launch (blockIdx.y = job), each ONE polynomial at NP points: NP = 1 is a
+// plain scan; NP = 2 is the two scans the inner-product argument opens at r
+// and 1/r (ipa.rs:87-92, and its TODO at :86).  A thread then carries two
+// accumulators over the same coefficient strip and writes two suffix vectors:
+// the coefficient loads and their to29 conversions are shared, and the
+// per-chunk Horner chain runs as two independent chains per thread.  Each
+// chain performs exactly the steps of an NP = 1 job, so the outputs are
+// bit-identical to two single jobs.
+// The arithmetic is in 9 x 29-bit limbs (each step c_i + x s_{i+1}: a canonical
+// coefficient plus a product < 2p, so one conditional subtraction keeps
+// s < 2p): the per-chunk Horner chain is the latency of the whole recursion,
+// and the 29-bit multiply's dependent latency is half the 32-bit one's.  x is
+// passed as x 2^261 (plain limbs), so mul29 keeps the arkworks scale of the
+// coefficients; every stored value is canonical arkworks form.
+template <int NP>
 struct ShJob {
-  const Fr* c;  // coefficients (arkworks form)
+  const Fr* c;      // coefficients (arkworks form)
   size_t L;
-  L9 x;         // x 2^261 mod p
-  Fr* A;        // chunk values (local pass)
-  const Fr* T;  // chunk carries (apply pass)
+  L9 x[NP];         // x_p 2^261 mod p
+  Fr* A[NP];        // chunk values (local pass)
+  const Fr* T[NP];  // chunk carries (apply pass)
   size_t nch;
-  Fr* s;        // output suffixes
+  Fr* s[NP];        // output suffixes
 };
+static constexpr int SH_J = 4;  // jobs per launch
+template <int NP>
 struct ShJobs {
-  ShJob j[4];
+  ShJob<NP> j[SH_J];
 };
+
+// one Horner step of every chain on the shared (converted) coefficient
+template <int NP>
+__device__ __forceinline__ void sh_step(const F29<FrP>& ci, const F29<FrP> (&x)[NP],
+                                        F29<FrP> (&acc)[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; p++) acc[p] = red2p29(add29(ci, mul29(x[p], acc[p])));
+}
 
 // The apply pass on a full chunk runs software-pipelined: its coefficients
 // come in groups of SH_G, the next group's loads issued before the current
 // group's dependent products and stores (one load round trip per group instead
 // of per step, which the stores would otherwise pin in program order); a short
 // last chunk loops.  Every suffix value is written.
+// The outputs are __restrict__ parameters of their own (out1 only at NP = 2):
+// read through the job struct at every store, the NP = 2 pass waits on the
+// pointer reloads between its stores and runs 17 % longer
+// (profiles/r11_open_unify_ab.txt).
 static constexpr int SH_G = 4;
-__device__ __forceinline__ void sh_apply_chunk(const Fr* __restrict__ c, Fr* __restrict__ out,
-                                               size_t s, size_t e, const F29<FrP>& x,
-                                               F29<FrP> acc) {
+template <int NP>
+__device__ __forceinline__ void sh_apply_chunk(const Fr* __restrict__ c, Fr* __restrict__ out0,
+                                               Fr* __restrict__ out1, size_t s, size_t e,
+                                               const F29<FrP> (&x)[NP], F29<FrP> (&acc)[NP]) {
+  static_assert(NP == 1 || NP == 2, "one or two points per polynomial");
   if (e - s == SH_B) {
     Fr cur[SH_G], nxt[SH_G];
 #pragma unroll
@@ -202,8 +173,9 @@ __device__ __forceinline__ void sh_apply_chunk(const Fr* __restrict__ c, Fr* __r
       asm volatile("" ::: "memory");
 #pragma unroll
       for (int j = SH_G - 1; j >= 0; j--) {
-        acc = red2p29(add29(to29(cur[j]), mul29(x, acc)));
-        out[s + (size_t)g * SH_G + j] = from29(canon29(acc));
+        sh_step<NP>(to29(cur[j]), x, acc);
+        out0[s + (size_t)g * SH_G + j] = from29(canon29(acc[0]));
+        if constexpr (NP == 2) out1[s + (size_t)g * SH_G + j] = from29(canon29(acc[1]));
       }
       if (g > 0) {
 #pragma unroll
@@ -212,53 +184,68 @@ __device__ __forceinline__ void sh_apply_chunk(const Fr* __restrict__ c, Fr* __r
     }
   } else {
     for (size_t i = e; i-- > s;) {
-      acc = red2p29(add29(to29(c[i]), mul29(x, acc)));
-      out[i] = from29(canon29(acc));
+      sh_step<NP>(to29(c[i]), x, acc);
+      out0[i] = from29(canon29(acc[0]));
+      if constexpr (NP == 2) out1[i] = from29(canon29(acc[1]));
     }
   }
 }
 
-__global__ void k_sh_local_b(ShJobs jb) {
-  const ShJob& J = jb.j[blockIdx.y];
+template <int NP>
+__global__ void k_sh_local(ShJobs<NP> jb) {
+  const ShJob<NP>& J = jb.j[blockIdx.y];
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t s = k * SH_B;
   if (s >= J.L) return;
   const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
-  const F29<FrP> x = F29<FrP>::from_l9(J.x);
-  F29<FrP> acc = F29<FrP>::zero();
+  F29<FrP> x[NP], acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) x[p] = F29<FrP>::from_l9(J.x[p]), acc[p] = F29<FrP>::zero();
   // no stores in this chain: an unrolled loop lets the loads run ahead
 #pragma unroll 4
-  for (size_t i = e; i-- > s;) acc = red2p29(add29(to29(J.c[i]), mul29(x, acc)));
-  J.A[k] = from29(canon29(acc));
+  for (size_t i = e; i-- > s;) sh_step<NP>(to29(J.c[i]), x, acc);
+#pragma unroll
+  for (int p = 0; p < NP; p++) J.A[p][k] = from29(canon29(acc[p]));
 }
 
-__global__ void k_sh_apply_b(ShJobs jb) {
-  const ShJob& J = jb.j[blockIdx.y];
+template <int NP>
+__global__ void k_sh_apply(ShJobs<NP> jb) {
+  const ShJob<NP>& J = jb.j[blockIdx.y];
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t s = k * SH_B;
   if (s >= J.L) return;
   const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
-  const F29<FrP> x = F29<FrP>::from_l9(J.x);
-  const F29<FrP> acc0 = (k + 1 < J.nch) ? to29(J.T[k + 1]) : F29<FrP>::zero();
-  sh_apply_chunk(J.c, J.s, s, e, x, acc0);
+  const bool carry = k + 1 < J.nch;
+  F29<FrP> x[NP], acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) {
+    x[p] = F29<FrP>::from_l9(J.x[p]);
+    acc[p] = carry ? to29(J.T[p][k + 1]) : F29<FrP>::zero();
+  }
+  sh_apply_chunk<NP>(J.c, J.s[0], J.s[NP - 1], s, e, x, acc);
 }
 
-__global__ void k_sh_serial_b(ShJobs jb) {
-  const ShJob& J = jb.j[blockIdx.y];
+// small case: one thread per job
+template <int NP>
+__global__ void k_sh_serial(ShJobs<NP> jb) {
+  const ShJob<NP>& J = jb.j[blockIdx.y];
   if (threadIdx.x != 0) return;
-  const F29<FrP> x = F29<FrP>::from_l9(J.x);
-  F29<FrP> acc = F29<FrP>::zero();
+  F29<FrP> x[NP], acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) x[p] = F29<FrP>::from_l9(J.x[p]), acc[p] = F29<FrP>::zero();
   for (size_t i = J.L; i-- > 0;) {
-    acc = red2p29(add29(to29(J.c[i]), mul29(x, acc)));
-    J.s[i] = from29(canon29(acc));
+    sh_step<NP>(to29(J.c[i]), x, acc);
+#pragma unroll
+    for (int p = 0; p < NP; p++) J.s[p][i] = from29(canon29(acc[p]));
   }
 }
 
+template <int NP>
 struct ShIn {
   const Fr* c;
   size_t L;
-  Fr x;  // Montgomery
-  Fr* s;
+  Fr x[NP];  // Montgomery
+  Fr* s[NP];
 };
 
 static L9 x261_of(const Fr& x) {
@@ -270,212 +257,69 @@ static L9 x261_of(const Fr& x) {
   return o;
 }
 
-// s_i = c_i + x s_{i+1} for up to 4 independent (c, L, x) at once
-static void suffix_horner_batch(qg_ctx* ctx, const std::vector<ShIn>& in, int depth = 0) {
-  std::vector<ShIn> small, big;
-  for (const ShIn& q : in)
-    if (q.L > SH_B) big.push_back(q);
-    else if (q.L > 0) small.push_back(q);
-  QG_CHECK(in.size() <= 4, QG_ERR_ASSERT, "suffix-Horner batch of at most 4");
-  if (!small.empty()) {
-    ShJobs jb{};
-    for (size_t q = 0; q < small.size(); q++)
-      jb.j[q] = {small[q].c, small[q].L, x261_of(small[q].x), nullptr, nullptr, 0, small[q].s};
-    hipLaunchKernelGGL(k_sh_serial_b, dim3(1, (unsigned)small.size()), dim3(64), 0, ctx->stream, jb);
-    QG_LAUNCH_CHECK();
-  }
-  if (big.empty()) return;
-  ShJobs jb{};
-  std::vector<ShIn> up;
-  size_t maxch = 0;
-  for (size_t q = 0; q < big.size(); q++) {
-    const size_t nch = (big[q].L + SH_B - 1) / SH_B;
-    const std::string tag = std::to_string(depth) + "_" + std::to_string(q);
-    Fr* A = ctx->scratch_as<Fr>("shb_A" + tag, nch);
-    Fr* T = ctx->scratch_as<Fr>("shb_T" + tag, nch);
-    jb.j[q] = {big[q].c, big[q].L, x261_of(big[q].x), A, T, nch, big[q].s};
-    up.push_back({A, nch, fpow_small(big[q].x, SH_B), T});  // T_k = A_k + x^B T_{k+1}
-    maxch = std::max(maxch, nch);
-  }
-  const dim3 grid((unsigned)div_up(maxch, ML_BLOCK), (unsigned)big.size());
-  hipLaunchKernelGGL(k_sh_local_b, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
-  QG_LAUNCH_CHECK();
-  suffix_horner_batch(ctx, up, depth + 1);
-  hipLaunchKernelGGL(k_sh_apply_b, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
-  QG_LAUNCH_CHECK();
-}
+static void suffix_horner_many(qg_ctx* ctx, const std::vector<ShIn<1>>& in, int depth);
 
-// more than four scans: groups of four, one after the other in stream order
-// (the groups share the recursion's chunk scratch, which no group reads after
-// its own apply pass)
-static void suffix_horner_many(qg_ctx* ctx, const std::vector<ShIn>& in) {
-  for (size_t b = 0; b < in.size(); b += 4)
-    suffix_horner_batch(
-        ctx, std::vector<ShIn>(in.begin() + b, in.begin() + std::min(in.size(), b + 4)));
-}
-
-// Paired form: one job is (c, L, x0, x1), the two scans of ONE polynomial that
-// the inner-product argument opens at r and 1/r (ipa.rs:87-92, and its TODO
-// at :86).  A thread carries two accumulators over the same coefficient strip
-// and writes two suffix vectors: the coefficient loads and their to29
-// conversions are shared, and the per-chunk Horner chain - the latency the
-// comment above names - runs as two independent chains per thread.  Each
-// chain performs exactly the steps of the single-job kernels, so the outputs
-// are bit-identical to two single jobs.
-struct ShJob2 {
-  const Fr* c;
-  size_t L;
-  L9 x[2];         // x_k 2^261 mod p
-  Fr* A[2];        // chunk values (local pass)
-  const Fr* T[2];  // chunk carries (apply pass)
-  size_t nch;
-  Fr* s[2];        // output suffixes
-};
-static constexpr int SH_P = 3;  // paired jobs per launch (f, g, S)
-struct ShJobs2 {
-  ShJob2 j[SH_P];
-};
-
-__device__ __forceinline__ void sh_apply_chunk2(const Fr* __restrict__ c, Fr* __restrict__ out0,
-                                                Fr* __restrict__ out1, size_t s, size_t e,
-                                                const F29<FrP>& x0, const F29<FrP>& x1,
-                                                F29<FrP> a0, F29<FrP> a1) {
-  if (e - s == SH_B) {
-    Fr cur[SH_G], nxt[SH_G];
-#pragma unroll
-    for (int j = 0; j < SH_G; j++) cur[j] = c[s + SH_B - SH_G + j];
-#pragma unroll
-    for (int g = SH_B / SH_G - 1; g >= 0; g--) {
-      if (g > 0) {
-#pragma unroll
-        for (int j = 0; j < SH_G; j++) nxt[j] = c[s + (size_t)(g - 1) * SH_G + j];
-      }
-      asm volatile("" ::: "memory");  // (as in sh_apply_chunk)
-#pragma unroll
-      for (int j = SH_G - 1; j >= 0; j--) {
-        const F29<FrP> cj = to29(cur[j]);
-        a0 = red2p29(add29(cj, mul29(x0, a0)));
-        a1 = red2p29(add29(cj, mul29(x1, a1)));
-        out0[s + (size_t)g * SH_G + j] = from29(canon29(a0));
-        out1[s + (size_t)g * SH_G + j] = from29(canon29(a1));
-      }
-      if (g > 0) {
-#pragma unroll
-        for (int j = 0; j < SH_G; j++) cur[j] = nxt[j];
-      }
-    }
-  } else {
-    for (size_t i = e; i-- > s;) {
-      const F29<FrP> ci = to29(c[i]);
-      a0 = red2p29(add29(ci, mul29(x0, a0)));
-      a1 = red2p29(add29(ci, mul29(x1, a1)));
-      out0[i] = from29(canon29(a0));
-      out1[i] = from29(canon29(a1));
-    }
-  }
-}
-
-__global__ void k_sh_local_b2(ShJobs2 jb) {
-  const ShJob2& J = jb.j[blockIdx.y];
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t s = k * SH_B;
-  if (s >= J.L) return;
-  const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
-  const F29<FrP> x0 = F29<FrP>::from_l9(J.x[0]), x1 = F29<FrP>::from_l9(J.x[1]);
-  F29<FrP> a0 = F29<FrP>::zero(), a1 = F29<FrP>::zero();
-#pragma unroll 4
-  for (size_t i = e; i-- > s;) {
-    const F29<FrP> ci = to29(J.c[i]);
-    a0 = red2p29(add29(ci, mul29(x0, a0)));
-    a1 = red2p29(add29(ci, mul29(x1, a1)));
-  }
-  J.A[0][k] = from29(canon29(a0));
-  J.A[1][k] = from29(canon29(a1));
-}
-
-__global__ void k_sh_apply_b2(ShJobs2 jb) {
-  const ShJob2& J = jb.j[blockIdx.y];
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t s = k * SH_B;
-  if (s >= J.L) return;
-  const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
-  const F29<FrP> x0 = F29<FrP>::from_l9(J.x[0]), x1 = F29<FrP>::from_l9(J.x[1]);
-  const bool carry = k + 1 < J.nch;
-  const F29<FrP> a0 = carry ? to29(J.T[0][k + 1]) : F29<FrP>::zero();
-  const F29<FrP> a1 = carry ? to29(J.T[1][k + 1]) : F29<FrP>::zero();
-  sh_apply_chunk2(J.c, J.s[0], J.s[1], s, e, x0, x1, a0, a1);
-}
-
-__global__ void k_sh_serial_b2(ShJobs2 jb) {
-  const ShJob2& J = jb.j[blockIdx.y];
-  if (threadIdx.x != 0) return;
-  const F29<FrP> x0 = F29<FrP>::from_l9(J.x[0]), x1 = F29<FrP>::from_l9(J.x[1]);
-  F29<FrP> a0 = F29<FrP>::zero(), a1 = F29<FrP>::zero();
-  for (size_t i = J.L; i-- > 0;) {
-    const F29<FrP> ci = to29(J.c[i]);
-    a0 = red2p29(add29(ci, mul29(x0, a0)));
-    a1 = red2p29(add29(ci, mul29(x1, a1)));
-    J.s[0][i] = from29(canon29(a0));
-    J.s[1][i] = from29(canon29(a1));
-  }
-}
-
-struct ShIn2 {
-  const Fr* c;
-  size_t L;
-  Fr x[2];  // Montgomery
-  Fr* s[2];
-};
-
-// s^k_i = c_i + x_k s^k_{i+1}, k = 0, 1, for up to SH_P polynomials at once.
-// The chunk values of the two points are two different vectors, so the levels
-// above run as single jobs (suffix_horner_many).
-static void suffix_horner_pairs(qg_ctx* ctx, const std::vector<ShIn2>& in) {
-  QG_CHECK(in.size() <= (size_t)SH_P, QG_ERR_ASSERT, "suffix-Horner pair batch of at most 3");
-  std::vector<ShIn2> small, big;
-  for (const ShIn2& q : in)
+// s^p_i = c_i + x_p s^p_{i+1}, p < NP, for up to SH_J polynomials at once.
+// The chunk values of different points are different vectors, so the levels
+// above run as NP = 1 jobs.
+template <int NP>
+static void suffix_horner(qg_ctx* ctx, const std::vector<ShIn<NP>>& in, int depth = 0) {
+  QG_CHECK(in.size() <= (size_t)SH_J, QG_ERR_ASSERT, "suffix-Horner batch of at most 4");
+  std::vector<ShIn<NP>> small, big;
+  for (const ShIn<NP>& q : in)
     if (q.L > SH_B) big.push_back(q);
     else if (q.L > 0) small.push_back(q);
   if (!small.empty()) {
-    ShJobs2 jb{};
+    ShJobs<NP> jb{};
     for (size_t q = 0; q < small.size(); q++) {
-      ShJob2& j = jb.j[q];
+      ShJob<NP>& j = jb.j[q];
       j.c = small[q].c, j.L = small[q].L;
-      for (int k = 0; k < 2; k++) j.x[k] = x261_of(small[q].x[k]), j.s[k] = small[q].s[k];
+      for (int p = 0; p < NP; p++) j.x[p] = x261_of(small[q].x[p]), j.s[p] = small[q].s[p];
     }
-    hipLaunchKernelGGL(k_sh_serial_b2, dim3(1, (unsigned)small.size()), dim3(64), 0, ctx->stream,
+    hipLaunchKernelGGL(k_sh_serial<NP>, dim3(1, (unsigned)small.size()), dim3(64), 0, ctx->stream,
                        jb);
     QG_LAUNCH_CHECK();
   }
   if (big.empty()) return;
-  ShJobs2 jb{};
-  std::vector<ShIn> up;
+  ShJobs<NP> jb{};
+  std::vector<ShIn<1>> up;
   size_t maxch = 0;
   for (size_t q = 0; q < big.size(); q++) {
     const size_t nch = (big[q].L + SH_B - 1) / SH_B;
-    ShJob2& j = jb.j[q];
+    ShJob<NP>& j = jb.j[q];
     j.c = big[q].c, j.L = big[q].L, j.nch = nch;
-    for (int k = 0; k < 2; k++) {
-      const std::string tag = std::to_string(2 * q + k);
-      Fr* A = ctx->scratch_as<Fr>("shp_A" + tag, nch);
-      Fr* T = ctx->scratch_as<Fr>("shp_T" + tag, nch);
-      j.x[k] = x261_of(big[q].x[k]), j.A[k] = A, j.T[k] = T, j.s[k] = big[q].s[k];
-      up.push_back({A, nch, fpow_small(big[q].x[k], SH_B), T});  // T_k = A_k + x^B T_{k+1}
+    for (int p = 0; p < NP; p++) {
+      const std::string tag = std::to_string(depth) + "_" + std::to_string(NP * q + p);
+      Fr* A = ctx->scratch_as<Fr>("sh_A" + tag, nch);
+      Fr* T = ctx->scratch_as<Fr>("sh_T" + tag, nch);
+      j.x[p] = x261_of(big[q].x[p]), j.A[p] = A, j.T[p] = T, j.s[p] = big[q].s[p];
+      up.push_back({A, nch, {fpow_small(big[q].x[p], SH_B)}, {T}});  // T_k = A_k + x^B T_{k+1}
     }
     maxch = std::max(maxch, nch);
   }
   const dim3 grid((unsigned)div_up(maxch, ML_BLOCK), (unsigned)big.size());
-  hipLaunchKernelGGL(k_sh_local_b2, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
+  hipLaunchKernelGGL(k_sh_local<NP>, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
   QG_LAUNCH_CHECK();
-  suffix_horner_many(ctx, up);
-  hipLaunchKernelGGL(k_sh_apply_b2, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
+  suffix_horner_many(ctx, up, depth + 1);
+  hipLaunchKernelGGL(k_sh_apply<NP>, grid, dim3(ML_BLOCK), 0, ctx->stream, jb);
   QG_LAUNCH_CHECK();
 }
+
+// more than SH_J scans: groups of SH_J, one after the other in stream order
+// (the groups share the recursion's chunk scratch, which no group reads after
+// its own apply pass)
+static void suffix_horner_many(qg_ctx* ctx, const std::vector<ShIn<1>>& in, int depth = 0) {
+  for (size_t b = 0; b < in.size(); b += SH_J)
+    suffix_horner<1>(
+        ctx, std::vector<ShIn<1>>(in.begin() + b, in.begin() + std::min(in.size(), b + SH_J)),
+        depth);
+}
+
 
 // ---------------------------------------------------------------- polynomial evaluation
 // DensePolynomial::evaluate (kzg.rs:78) as a reduction: sum_i c_i x^i of up to
 // EV_MAXJ vectors per launch (blockIdx.y = job, like ShJobs) in the 29-bit
-// limbs of k_sh_local_b.  A thread runs Horner over a contiguous strip of S
+// limbs of k_sh_local.  A thread runs Horner over a contiguous strip of S
 // coefficients; a block combines its 256 strip values with powers of x^S
 // (shuffle tree inside a wave: lane l takes x^(S 2^k) times lane l + 2^k;
 // then the four wave values through LDS) and writes one value per block span
@@ -1532,18 +1376,18 @@ static void kzg_quotients_batch(qg_ctx* ctx, const qg_srs* srs, const Fr* const 
                                 qg_kzg_opening* const outs[4], std::vector<const Fr*>& qs,
                                 std::vector<size_t>& qns, Fr* h_y, const OpenCkOut& ck,
                                 size_t slot = 0) {
-  std::vector<ShIn> jobs;
+  std::vector<ShIn<1>> jobs;
   Fr* s[4] = {nullptr, nullptr, nullptr, nullptr};
   for (int i = 0; i < 4; i++) {
     fr_export(xs[i], outs[i]->x);
     if (Lt[i] == 0) continue;
     QG_CHECK(Lt[i] - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
     s[i] = ctx->scratch_as<Fr>("open_s#" + std::to_string(4 * slot + i), Lt[i]);
-    jobs.push_back({polys[i], Lt[i], xs[i], s[i]});
+    jobs.push_back({polys[i], Lt[i], {xs[i]}, {s[i]}});
   }
   {
     QgTimed tm(ctx, "kzg_division");
-    suffix_horner_batch(ctx, jobs);
+    suffix_horner<1>(ctx, jobs);
   }
   for (int i = 0; i < 4; i++)
     if (s[i]) fault_quotient(ctx, s[i] + 1, Lt[i] - 1);
@@ -1577,39 +1421,34 @@ static void kzg_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t 
                             qg_kzg_opening* out) {
   fr_export(x, out->x);
   // DensePolynomial::from_coefficients_slice trims
-  size_t Lt = fault_short_trim(ctx, trimmed_len(ctx, c, L));
+  const size_t Lt = fault_short_trim(ctx, trimmed_len(ctx, c, L));
   Fr y = Fr::zero();
   G1Affine pi = G1Affine::infinity();
-  if (Lt > 0) {
-    Fr* s = ctx->scratch_as<Fr>("open_s", Lt);
+  Fr* s = Lt ? ctx->scratch_as<Fr>("open_s#0", Lt) : nullptr;
+  if (s) {
     {
       QgTimed tm(ctx, "kzg_division");
-      suffix_horner(ctx, c, Lt, x, s);
+      suffix_horner<1>(ctx, {{c, Lt, {x}, {s}}});
     }
     fault_quotient(ctx, s + 1, Lt - 1);
     QG_HIP(hipMemcpyAsync(&y, s, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-    // kzg.rs:85: p over all L coefficients, q as the MSM will read it
-    const bool check = open_check_on();
-    uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
-    if (check) {
-      uint32_t* d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
-      const OpenCk c4[4] = {{c, L, s + 1, Lt - 1, s, x}, {}, {}, {}};
-      open_check_queue(ctx, c4, d_w);
-      QG_HIP(hipMemcpyAsync(h_w, d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    ctx->sync();
-    if (check) open_check_settle(ctx, {h_w[0]}, {CK_QUOT}, 1, OPEN_UNAME);
+  }
+  // kzg.rs:85: p over all L coefficients, q as the MSM will read it; trimmed to
+  // nothing: all L coefficients must be 0
+  const bool check = L > 0 && open_check_on();
+  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
+  if (check) {
+    uint32_t* d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
+    const OpenCk c4[4] = {{c, L, s ? s + 1 : nullptr, s ? Lt - 1 : 0, s, x}, {}, {}, {}};
+    open_check_queue(ctx, c4, d_w);
+    QG_HIP(hipMemcpyAsync(h_w, d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (s || check) ctx->sync();
+  if (check) open_check_settle(ctx, {h_w[0]}, {s ? CK_QUOT : CK_ZERO}, 1, OPEN_UNAME);
+  if (s) {
     // q_i = s_{i+1}, i < Lt - 1; commit(q) (kzg.rs:88-89)
     QG_CHECK(Lt - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
     pi = msm_device(ctx, srs, s + 1, Lt - 1);
-  } else if (L > 0 && open_check_on()) {  // trimmed to nothing: all L coefficients must be 0
-    uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
-    uint32_t* d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
-    const OpenCk c4[4] = {{c, L, nullptr, 0, nullptr, x}, {}, {}, {}};
-    open_check_queue(ctx, c4, d_w);
-    QG_HIP(hipMemcpyAsync(h_w, d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    open_check_settle(ctx, {h_w[0]}, {CK_ZERO}, 1, OPEN_UNAME);
   }
   fr_export(y, out->y);
   g1_export(pi, out->proof_xy, &out->proof_inf);
@@ -1637,68 +1476,6 @@ static void allgather_host(qg_ctx* ctx, const void* src, size_t bytes, void* dst
   QG_HIP(hipMemcpyAsync(dst_all, dr, bytes * (size_t)ctx->world, hipMemcpyDeviceToHost,
                         ctx->stream));
   ctx->sync();
-}
-
-// global trimmed length of a vector sliced as [rank * L, rank * L + nloc)
-static size_t trimmed_len_global(qg_ctx* ctx, const Fr* a, size_t nloc, size_t L) {
-  const uint64_t loc = nloc ? fault_short_trim(ctx, trimmed_len(ctx, a, nloc)) : 0;
-  const uint64_t mine = loc ? (uint64_t)ctx->rank * L + loc : 0;
-  std::vector<uint64_t> all(ctx->world);
-  allgather_host(ctx, &mine, sizeof mine, all.data());
-  uint64_t m = 0;
-  for (uint64_t v : all) m = v > m ? v : m;
-  return (size_t)m;
-}
-
-// KZG::open of a sharded polynomial (global trimmed length Lt, slices of L):
-// every rank gets the same opening; the quotient MSM is sharded.
-// With d_qev set, this rank's part of q(sigma) (its slice's sigma-power offset
-// included) is queued into *d_qev for the caller's quotient check.
-static void kzg_open_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t L, size_t Lt,
-                             const Fr& x, qg_kzg_opening* out, Fr* d_qev = nullptr) {
-  const int world = ctx->world, rank = ctx->rank;
-  const size_t off = (size_t)rank * L;
-  const size_t le = Lt > off ? std::min(L, Lt - off) : 0;  // this rank's live coefficients
-  fr_export(x, out->x);
-  Fr* s = ctx->scratch_as<Fr>("open_s", le + 1);
-  Fr T = Fr::zero();
-  if (le > 0) {
-    QgTimed tm(ctx, "kzg_division");
-    suffix_horner(ctx, c, le, x, s);
-    QG_HIP(hipMemcpyAsync(&T, s, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-  }
-  std::vector<Fr> Ts(world);
-  allgather_host(ctx, &T, sizeof(Fr), Ts.data());
-  // C_r = sum_{r' > r} T_r' x^((r' - r - 1) L);  y = sum_r T_r x^(r L)
-  const Fr xL = fpow_small(x, L);
-  Fr C = Fr::zero(), y = Fr::zero();
-  for (int r = world - 1; r >= 0; r--) {
-    if (r == rank) C = y;  // y accumulated over r' > rank so far, in powers of x^L
-    y = Ts[r] + xL * y;
-  }
-  if (le > 0) {
-    QgTimed tm(ctx, "kzg_division");
-    Fr* pw = ctx->scratch_as<Fr>("open_pw", le + 1);
-    const int K = 64;
-    hipLaunchKernelGGL(k_powers_ml, dim3(div_up(div_up(le + 1, (size_t)K), ML_BLOCK)), dim3(ML_BLOCK),
-                       0, ctx->stream, x, le + 1, K, pw);
-    QG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sh_carry, dim3(div_up(le + 1, ML_BLOCK)), dim3(ML_BLOCK), 0, ctx->stream,
-                       s, le, pw, C);
-    QG_LAUNCH_CHECK();
-  }
-  // q_i = s_{i+1} for global i < Lt - 1; this rank's part starts at s + 1
-  const size_t qn = (Lt > 0 && Lt - 1 > off) ? std::min(le, Lt - 1 - off) : 0;
-  QG_CHECK(qn <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-  fault_quotient(ctx, s + 1, qn);
-  if (d_qev) {
-    QgTimed tm(ctx, "kzg_open_check");
-    poly_eval_queue(ctx, {{s + 1, qn, (uint64_t)off}}, ctx->open_sigma, d_qev);
-  }
-  const G1Affine pi = msm_device(ctx, srs, s + 1, qn);
-  fr_export(y, out->y);
-  g1_export(pi, out->proof_xy, &out->proof_inf);
 }
 
 // ---------------------------------------------------------------- sharded S polynomial
@@ -1928,107 +1705,6 @@ static void s_poly_sharded(qg_ctx* ctx, const Fr* f, size_t M, const uint64_t* p
   QG_LAUNCH_CHECK();
 }
 
-// MLEvalProof::prove with a communicator: this rank holds poly[rank L, (rank+1) L)
-// of the 2^nvars evaluations (L = 2^nvars / world) and the matching SRS shard.
-// eq table and the dot product per slice; the S polynomial's transform is split
-// by frequency residue over the ranks (s_poly_sharded: the slices are
-// allgathered for its forward pre-sum, one all-to-all returns every rank its
-// slice of S); its commitment and all four quotient commitments are sharded MSMs.
-static void mle_open_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* dpoly, size_t L,
-                             const uint64_t* point, size_t nvars, uint8_t state[32],
-                             qg_mle_proof* out) {
-  const size_t N = (size_t)1 << nvars;
-  QG_CHECK(L * (size_t)ctx->world == N, QG_ERR_UNSUPPORTED,
-           "sharded opening needs world * local length == 2^nvars");
-  const size_t off = (size_t)ctx->rank * L;
-  Fr* dz = ctx->scratch_as<Fr>("mle_z", nvars ? nvars : 1);
-  Fr* dpr = ctx->scratch_as<Fr>("mle_pr", N);
-  Fr* dfull = ctx->scratch_as<Fr>("mle_full", N);
-  fr_upload(ctx, dz, point, nvars);
-  eq_table_device(ctx, dz, (uint32_t)nvars, dpr);
-  // evaluation: local dot over the slice, summed over ranks
-  const Fr part = dot_device(ctx, dpoly, dpr + off, L);
-  std::vector<Fr> parts(ctx->world);
-  allgather_host(ctx, &part, sizeof(Fr), parts.data());
-  Fr evaluation = Fr::zero();
-  for (const Fr& v : parts) evaluation = evaluation + v;
-  // S: this rank's slice from the residue-split transform (s_poly_sharded) or,
-  // with QG_S_REPLICATED=1 (A/B runs), the whole S on every rank
-  comm_allgather_bytes(ctx, dpoly, dfull, L * sizeof(Fr));
-  const char* rep = getenv("QG_S_REPLICATED");  // read per call: tests toggle it in-process
-  const bool replicated = rep && atoi(rep) != 0;
-  Fr* Sl = ctx->scratch_as<Fr>("mle_S_local", L);
-  size_t Slen = 0;
-  if (N > 1) {
-    if (replicated) {
-      Fr* dS = ctx->scratch_as<Fr>("mle_S", N);
-      s_poly_device(ctx, dfull, N, dpr, N, dS, point, nvars);
-      QG_HIP(hipMemsetAsync(dS + N - 1, 0, sizeof(Fr), ctx->stream));  // h[2M - 1] = 0
-      QG_HIP(hipMemcpyAsync(Sl, dS + off, L * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-      s_poly_sharded(ctx, dfull, N, point, nvars, Sl);
-    }
-    Slen = trimmed_len_global(ctx, Sl, L, L);
-  } else {
-    QG_HIP(hipMemsetAsync(Sl, 0, L * sizeof(Fr), ctx->stream));
-  }
-  const size_t sloc = Slen > off ? std::min(L, Slen - off) : 0;
-  QG_CHECK(sloc <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-  G1Affine s_comm = msm_device(ctx, srs, Sl, sloc);
-  // transcript: point (Vec<Fr>), evaluation, s_comm; draw r (mlpcs.rs:100-107)
-  std::vector<uint8_t> msg(8 + 32 * nvars);
-  u64_to_bytes(nvars, msg.data());
-  for (size_t i = 0; i < nvars; i++) fr_to_bytes(fr_import(point + 4 * i), msg.data() + 8 + 32 * i);
-  transcript_append(state, msg.data(), msg.size());
-  uint8_t b32[32], b64[64];
-  fr_to_bytes(evaluation, b32);
-  transcript_append(state, b32, 32);
-  g1_serialize(s_comm, b64);
-  transcript_append(state, b64, 64);
-  Fr r = transcript_draw_fr(state);
-  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-  Fr r_inv = finv(r);
-  fr_export(evaluation, out->evaluation);
-  g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
-  const size_t Lt = trimmed_len_global(ctx, dpoly, L, L);
-  // the quotient check: this rank's parts of p(sigma), S(sigma) over its whole
-  // slices and of the four q(sigma), one exchange, the same sums and so the
-  // same decision on every rank
-  const bool check = open_check_on();
-  Fr* d_ev = check ? ctx->scratch_as<Fr>("open_ck_ev_sh", 6) : nullptr;
-  if (check) {
-    QgTimed tm(ctx, "kzg_open_check");
-    poly_eval_queue(ctx, {{dpoly, L, (uint64_t)off}, {Sl, L, (uint64_t)off}}, ctx->open_sigma, d_ev);
-  }
-  kzg_open_sharded(ctx, srs, dpoly, L, Lt, r, &out->poly_opening, check ? d_ev + 2 : nullptr);
-  kzg_open_sharded(ctx, srs, dpoly, L, Lt, r_inv, &out->poly_opening_inv, check ? d_ev + 3 : nullptr);
-  kzg_open_sharded(ctx, srs, Sl, L, Slen, r, &out->s_opening, check ? d_ev + 4 : nullptr);
-  kzg_open_sharded(ctx, srs, Sl, L, Slen, r_inv, &out->s_opening_inv, check ? d_ev + 5 : nullptr);
-  if (check) {
-    const size_t W = (size_t)ctx->world;
-    Fr* d_all = ctx->scratch_as<Fr>("open_ck_ev_all", 6 * W);
-    comm_allgather_bytes(ctx, d_ev, d_all, 6 * sizeof(Fr));
-    std::vector<Fr> all(6 * W);
-    QG_HIP(hipMemcpyAsync(all.data(), d_all, 6 * W * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    const qg_kzg_opening* o4[4] = {&out->poly_opening, &out->poly_opening_inv, &out->s_opening,
-                                   &out->s_opening_inv};
-    const size_t glt[4] = {Lt, Lt, Slen, Slen};
-    std::vector<uint32_t> bad(4, 0);
-    std::vector<uint8_t> checked(4, 0);
-    for (int i = 0; i < 4; i++) {
-      Fr P = Fr::zero(), Q = Fr::zero();
-      for (size_t rk = 0; rk < W; rk++) {
-        P = P + all[6 * rk + (i < 2 ? 0 : 1)];
-        Q = Q + all[6 * rk + 2 + i];
-      }
-      checked[i] = glt[i] ? CK_QUOT : CK_ZERO;  // length 0: y = 0, q = 0, so p(sigma) == 0
-      bad[i] = open_check_host(P, fr_import(o4[i]->y), Q, ctx->open_sigma, fr_import(o4[i]->x));
-    }
-    open_check_settle(ctx, bad, checked, 4, OPEN_QNAME);
-  }
-}
-
 struct MleOpenItem {
   const Fr* poly;
   size_t n;
@@ -2038,6 +1714,35 @@ struct MleOpenItem {
   uint64_t id;
   size_t off;
 };
+
+// the transcript step of one opening (mlpcs.rs:100-107): append the point
+// (Vec<Fr>), the evaluation and s_comm; draw r
+struct OpenChallenge {
+  Fr r, r_inv;
+};
+static OpenChallenge open_transcript_step(uint8_t state[32], const uint64_t* point, size_t nvars,
+                                          const Fr& evaluation, const G1Affine& s_comm) {
+  std::vector<uint8_t> msg(8 + 32 * nvars);
+  u64_to_bytes(nvars, msg.data());
+  for (size_t i = 0; i < nvars; i++) fr_to_bytes(fr_import(point + 4 * i), msg.data() + 8 + 32 * i);
+  transcript_append(state, msg.data(), msg.size());
+  uint8_t b32[32], b64[64];
+  fr_to_bytes(evaluation, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr r = transcript_draw_fr(state);
+  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  return {r, finv(r)};
+}
+
+// the four KZG openings of a proof in quotient order (OPEN_QNAME)
+struct Open4 {
+  qg_kzg_opening* o[4];
+};
+static Open4 open4(qg_mle_proof& p) {
+  return {{&p.poly_opening, &p.poly_opening_inv, &p.s_opening, &p.s_opening_inv}};
+}
 
 // Per-item scratch of a batch of openings (S vectors, quotient vectors, eq
 // points) and the per-MSM slots of its MSM batches (msm.hip: partials, owners,
@@ -2060,17 +1765,21 @@ static void open_batch_trim_scratch(qg_ctx* ctx, size_t K) {
   }
 }
 
-// K openings on a sharded context: mle_open_sharded's data flow, batched the
-// way mle_open_batch_device batches the single-context one.  Per item the eq
-// table, the local dot, the gathered vector's residue-split S slice and the
-// local trimmed lengths are queued; ONE allgather carries every item's dot
+// MLEvalProof::prove for K >= 1 openings with a communicator: this rank holds
+// poly[rank L, (rank+1) L) of each item's 2^nvars evaluations (L = 2^nvars /
+// world) and the matching SRS shard.  The data flow is batched the way
+// mle_open_batch_device batches the single-context one.  Per item the eq
+// table, the local dot, the gathered vector's residue-split S slice
+// (s_poly_sharded; QG_S_REPLICATED=1: the whole S on every rank, A/B runs) and
+// the local trimmed lengths are queued; ONE allgather carries every item's dot
 // part and local lengths; the S commitments run as ONE MSM batch (one
 // allgather of the per-rank partials); the transcript steps run on the host
 // in item order; the 4K quotients' local suffix-Horner scans are queued, ONE
 // allgather carries their slice-end values T; the carries (x^(le - i) C) are
-// applied; the 4K quotient commitments run as ONE MSM batch.  Four exchanges
-// per trace instead of ~11 per opening; the proofs and the final transcript
-// state equal K successive mle_open_sharded calls (tests/test_gpu_multirank.py).
+// applied; the 4K quotient commitments run as ONE sharded MSM batch.  Four
+// exchanges per call; the proofs and the final transcript state of a batch of
+// K equal K batches of one, and the single-context ones
+// (tests/test_gpu_multirank.py).
 static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
                                    const std::vector<MleOpenItem>& items, uint8_t state[32],
                                    qg_mle_proof* outs) {
@@ -2138,7 +1847,7 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
     for (size_t k = 0; k < K; k++) {
       evaluation[k] = evaluation[k] + parts[k];
       const size_t L = items[k].n;
-      // trimmed_len_global: the largest (rank offset + local length) of a nonzero slice
+      // the global trimmed length: the largest (rank offset + local length) of a nonzero slice
       if (lens[2 * k]) Lt[k] = std::max(Lt[k], r * L + (size_t)lens[2 * k]);
       if (lens[2 * k + 1]) Slen[k] = std::max(Slen[k], r * L + (size_t)lens[2 * k + 1]);
     }
@@ -2156,29 +1865,16 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
   // the transcript steps in item order (mlpcs.rs:100-107)
   std::vector<Fr> xs(4 * K);
   for (size_t k = 0; k < K; k++) {
-    const MleOpenItem& it = items[k];
-    std::vector<uint8_t> msg(8 + 32 * it.nvars);
-    u64_to_bytes(it.nvars, msg.data());
-    for (size_t i = 0; i < it.nvars; i++)
-      fr_to_bytes(fr_import(it.point + 4 * i), msg.data() + 8 + 32 * i);
-    transcript_append(state, msg.data(), msg.size());
-    uint8_t b32[32], b64[64];
-    fr_to_bytes(evaluation[k], b32);
-    transcript_append(state, b32, 32);
-    g1_serialize(s_comm[k], b64);
-    transcript_append(state, b64, 64);
-    const Fr r = transcript_draw_fr(state);
-    QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-    const Fr r_inv = finv(r);
+    const OpenChallenge ch =
+        open_transcript_step(state, items[k].point, items[k].nvars, evaluation[k], s_comm[k]);
     fr_export(evaluation[k], outs[k].evaluation);
     g1_export(s_comm[k], outs[k].s_comm_xy, &outs[k].s_comm_inf);
-    xs[4 * k] = r;
-    xs[4 * k + 1] = r_inv;
-    xs[4 * k + 2] = r;
-    xs[4 * k + 3] = r_inv;
+    xs[4 * k] = xs[4 * k + 2] = ch.r;
+    xs[4 * k + 1] = xs[4 * k + 3] = ch.r_inv;
   }
-  // the 4K quotients' local scans (kzg_open_sharded, batched): job j = 4k + i
-  // scans this rank's le live coefficients into s_j[0..le); T_j = s_j[0]
+  // the 4K quotients' local scans: job j = 4k + i (global trimmed length
+  // glt_j, slices of L) scans this rank's le live coefficients into
+  // s_j[0..le); T_j = s_j[0]
   const size_t J = 4 * K;
   std::vector<size_t> le(J, 0), glt(J, 0);
   std::vector<Fr*> sq(J, nullptr);
@@ -2186,17 +1882,17 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
   QG_HIP(hipMemsetAsync(d_T, 0, J * sizeof(Fr), ctx->stream));
   for (size_t k = 0; k < K; k++) {
     const size_t L = items[k].n, off = rank * L;
-    std::vector<ShIn> jobs;
+    std::vector<ShIn<1>> jobs;
     for (int i = 0; i < 4; i++) {
       const size_t j = 4 * k + i;
       glt[j] = i < 2 ? Lt[k] : Slen[k];
       le[j] = glt[j] > off ? std::min(L, glt[j] - off) : 0;
       sq[j] = ctx->scratch_as<Fr>("open_s#" + std::to_string(j), le[j] + 1);
-      if (le[j]) jobs.push_back({i < 2 ? items[k].poly : Sl[k], le[j], xs[j], sq[j]});
+      if (le[j]) jobs.push_back({i < 2 ? items[k].poly : Sl[k], le[j], {xs[j]}, {sq[j]}});
     }
     {
       QgTimed tm(ctx, "kzg_division");
-      suffix_horner_batch(ctx, jobs);
+      suffix_horner<1>(ctx, jobs);
     }
     for (int i = 0; i < 4; i++) {
       const size_t j = 4 * k + i;
@@ -2282,153 +1978,44 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
     open_check_settle(ctx, bad, checked, 4, OPEN_QNAME);
   }
   for (size_t k = 0; k < K; k++) {
-    qg_kzg_opening* o4[4] = {&outs[k].poly_opening, &outs[k].poly_opening_inv,
-                             &outs[k].s_opening, &outs[k].s_opening_inv};
+    const Open4 o4 = open4(outs[k]);
     for (int i = 0; i < 4; i++) {
-      fr_export(xs[4 * k + i], o4[i]->x);
-      fr_export(ys[4 * k + i], o4[i]->y);
-      g1_export(pis[4 * k + i], o4[i]->proof_xy, &o4[i]->proof_inf);
+      fr_export(xs[4 * k + i], o4.o[i]->x);
+      fr_export(ys[4 * k + i], o4.o[i]->y);
+      g1_export(pis[4 * k + i], o4.o[i]->proof_xy, &o4.o[i]->proof_inf);
     }
   }
   open_batch_trim_scratch(ctx, K);
 }
 
-// MLEvalProof::prove (mlpcs.rs:83-124) on a device-resident evaluation vector.
-// Two host round trips per opening, both for values the transcript or the
-// caller needs: the S commitment and the four quotient commitments.  The
-// inner product, the trimmed lengths (DensePolynomial trims, kzg.rs / ipa.rs)
-// and the values y are queued into pinned memory and read after those
-// synchronizations; the trimmed length of the opened vector is reused while
-// the caller guarantees it unchanged (QG_OPEN_UNCHANGED contract, same
-// allocation id and offset).
-static void mle_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* dpoly, size_t n,
-                            const uint64_t* point, size_t nvars, uint8_t state[32],
-                            qg_mle_proof* out, bool unchanged = false, uint64_t poly_id = 0,
-                            size_t poly_off = 0) {
-  if (ctx->sharded) return mle_open_sharded(ctx, srs, dpoly, n, point, nvars, state, out);
-  const size_t N = (size_t)1 << nvars;
-  unsigned long long* h_len =
-      reinterpret_cast<unsigned long long*>(ctx->pinned_get("mle_len_h", 2 * sizeof(unsigned long long)));
-  unsigned long long* d_len = ctx->scratch_as<unsigned long long>("mle_len", 2);
-  // trimmed length of the opened vector: queued first (or remembered)
-  const std::string lt_key = poly_id ? std::to_string(poly_id) + "+" + std::to_string(poly_off) +
-                                           ":" + std::to_string(n) + "="
-                                     : std::string();
-  std::string& lt_memo = ctx->arena.memo["mle_poly_len"];
-  const bool lt_known = unchanged && poly_id && lt_memo.compare(0, lt_key.size(), lt_key) == 0;
-  if (!lt_known) {
-    trim_launch(ctx, dpoly, n, d_len);
-    QG_HIP(hipMemcpyAsync(h_len, d_len, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                          ctx->stream));
-  }
-  Fr* dz = ctx->scratch_as<Fr>("mle_z", nvars ? nvars : 1);
-  Fr* dpr = ctx->scratch_as<Fr>("mle_pr", N);
-  fr_upload(ctx, dz, point, nvars);
-  // P_r coefficients = eq table (mlpcs.rs:68-78)
-  eq_table_device(ctx, dz, (uint32_t)nvars, dpr);
-  // evaluation = <poly, P_r> over the common prefix (mlpcs.rs:91-94)
-  Fr* d_eval = ctx->scratch_as<Fr>("mle_eval", 1);
-  Fr* h_eval = reinterpret_cast<Fr*>(ctx->pinned_get("mle_eval_h", sizeof(Fr)));
-  dot_to_device(ctx, dpoly, dpr, n < N ? n : N, d_eval);
-  QG_HIP(hipMemcpyAsync(h_eval, d_eval, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  // S polynomial (mlpcs.rs:95-97) and its trimmed length
-  const size_t M = n > N ? n : N;
-  const size_t Sn = M > 1 ? M - 1 : 0;
-  Fr* dS = ctx->scratch_as<Fr>("mle_S", Sn ? Sn : 1);
-  if (Sn) s_poly_device(ctx, dpoly, n, dpr, N, dS, point, nvars, unchanged, poly_id, poly_off);
-  trim_launch(ctx, dS, Sn, d_len + 1);
-  QG_HIP(hipMemcpyAsync(h_len + 1, d_len + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                        ctx->stream));
-  // its commitment: over all Sn coefficients when they fit the SRS (trailing
-  // zeros add nothing), else the trimmed length first (the degree check)
-  size_t s_msm = Sn;
-  if (Sn > srs->n) {
-    ctx->sync();
-    s_msm = (size_t)h_len[1];
-    QG_CHECK(s_msm <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-  }
-  G1Affine s_comm = msm_device(ctx, srs, dS, s_msm);
-  ctx->sync();  // (drained already unless the MSM was empty)
-  const Fr evaluation = *h_eval;
-  size_t Lt = 0;
-  if (lt_known) {
-    Lt = (size_t)std::stoull(lt_memo.substr(lt_key.size()));
-  } else {
-    Lt = (size_t)h_len[0];
-    lt_memo = poly_id ? lt_key + std::to_string(Lt) : std::string();
-    Lt = fault_short_trim(ctx, Lt);  // (after the memo: a faulted length is never remembered)
-  }
-  const size_t Slen = fault_short_trim(ctx, (size_t)h_len[1]);
-  // transcript: point (Vec<Fr>), evaluation, s_comm; draw r (mlpcs.rs:100-107)
-  std::vector<uint8_t> msg(8 + 32 * nvars);
-  u64_to_bytes(nvars, msg.data());
-  for (size_t i = 0; i < nvars; i++) fr_to_bytes(fr_import(point + 4 * i), msg.data() + 8 + 32 * i);
-  transcript_append(state, msg.data(), msg.size());
-  uint8_t b32[32], b64[64];
-  fr_to_bytes(evaluation, b32);
-  transcript_append(state, b32, 32);
-  g1_serialize(s_comm, b64);
-  transcript_append(state, b64, 64);
-  Fr r = transcript_draw_fr(state);
-  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-  Fr r_inv = finv(r);
-  fr_export(evaluation, out->evaluation);
-  g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
-  // four KZG openings (mlpcs.rs:108-113): the four quotients first, then their
-  // commitments as one MSM batch (shared reduction launches)
-  qg_kzg_opening* outs[4] = {&out->poly_opening, &out->poly_opening_inv, &out->s_opening,
-                             &out->s_opening_inv};
-  const Fr* polys[4] = {dpoly, dpoly, dS, dS};
-  const size_t ns[4] = {n, n, Sn, Sn};
-  const size_t lts[4] = {Lt, Lt, Slen, Slen};
-  const Fr xs[4] = {r, r_inv, r, r_inv};
-  std::vector<const Fr*> qs;
-  std::vector<size_t> qns;
-  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("open_y_h", 4 * sizeof(Fr)));
-  OpenCkOut ck;
-  std::vector<uint8_t> checked(4, 0);
-  if (open_check_on()) {
-    ck.d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
-    ck.h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
-    ck.checked = checked.data();
-  }
-  kzg_quotients_batch(ctx, srs, polys, ns, lts, xs, outs, qs, qns, h_y, ck);
-  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
-  ctx->sync();  // (drained already unless every quotient was empty)
-  if (ck.d_w)
-    open_check_settle(ctx, std::vector<uint32_t>(ck.h_w, ck.h_w + 4), checked, 4, OPEN_QNAME);
-  for (int i = 0; i < 4; i++) {
-    fr_export(h_y[i], outs[i]->y);
-    g1_export(pis[i], outs[i]->proof_xy, &outs[i]->proof_inf);
-  }
-}
-
-// K ML openings with the transcript steps in item order — the same proofs and
-// final state as K successive mle_open_device calls — restructured around the
-// protocol's data flow (mlpcs.rs:83-124): S, its commitment, the evaluation
-// and the trimmed lengths depend on the polynomial and the point only, and
-// the transcript absorbs no quotient commitment, so
+// MLEvalProof::prove (mlpcs.rs:83-124) for K >= 1 device-resident evaluation
+// vectors, the transcript steps in item order — the same proofs and final
+// state as K successive batches of one — laid out around the protocol's data
+// flow: S, its commitment, the evaluation and the trimmed lengths depend on
+// the polynomial and the point only, and the transcript absorbs no quotient
+// commitment, so
 //   1. every item's evaluation, S polynomial and trimmed lengths (queued),
 //   2. the K S commitments as ONE MSM batch (one synchronization),
 //   3. the K transcript steps on the host (append point, evaluation, s_comm;
 //      draw r),
 //   4. the 4K quotients and their commitments as ONE MSM batch.
-// Inside a batch the bucketing of MSM i + 1 runs on the side stream beside
-// MSM i's accumulation, and the batch pays one set of reduction launches and
-// one host round trip (msm.hip).  Sharded contexts open item by item.
-
+// Two host round trips per call, both for values the transcript or the caller
+// needs; the inner products, the trimmed lengths (DensePolynomial trims,
+// kzg.rs / ipa.rs) and the values y are queued into pinned memory and read
+// after those synchronizations.  Inside a batch the bucketing of MSM i + 1
+// runs on the side stream beside MSM i's accumulation, and the batch pays one
+// set of reduction launches and one host round trip (msm.hip).  A sharded
+// context runs mle_open_batch_sharded.
 static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
                                   const std::vector<MleOpenItem>& items, uint8_t state[32],
                                   qg_mle_proof* outs) {
   const size_t K = items.size();
-  // QG_OPEN_BATCH_SHARDED=0: a sharded context opens item by item (A/B runs)
-  const char* sb = getenv("QG_OPEN_BATCH_SHARDED");
-  if (ctx->sharded && K > 1 && !(sb && atoi(sb) == 0))
-    return mle_open_batch_sharded(ctx, srs, items, state, outs);
-  if (ctx->sharded || K <= 1) {
-    for (size_t k = 0; k < K; k++)
-      mle_open_device(ctx, srs, items[k].poly, items[k].n, items[k].point, items[k].nvars, state,
-                      &outs[k], items[k].unchanged, items[k].id, items[k].off);
+  if (K == 0) return;
+  if (ctx->sharded) {
+    // QG_OPEN_BATCH_SHARDED=0: a sharded context opens item by item (A/B runs)
+    const char* sb = getenv("QG_OPEN_BATCH_SHARDED");
+    if (!(sb && atoi(sb) == 0)) return mle_open_batch_sharded(ctx, srs, items, state, outs);
+    for (size_t k = 0; k < K; k++) mle_open_batch_sharded(ctx, srs, {items[k]}, state, &outs[k]);
     return;
   }
   unsigned long long* h_len = reinterpret_cast<unsigned long long*>(
@@ -2437,11 +2024,11 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
   Fr* h_eval = reinterpret_cast<Fr*>(ctx->pinned_get("mleb_eval_h", K * sizeof(Fr)));
   Fr* d_eval = ctx->scratch_as<Fr>("mleb_eval", K);
   QG_HIP(hipMemsetAsync(d_len, 0, 2 * K * sizeof(unsigned long long), ctx->stream));
-  // the opened vectors' trimmed lengths: remembered for the QG_OPEN_UNCHANGED
-  // contract exactly as K successive mle_open_device calls would (the memo
-  // holds the last opened vector's key and length): item k reuses it when
-  // flagged and item k - 1 (item 0: the memo from before this call) opened
-  // the same vector
+  // the opened vectors' trimmed lengths: remembered while the caller
+  // guarantees the vector unchanged (QG_OPEN_UNCHANGED contract, same
+  // allocation id and offset).  The memo holds the last opened vector's key and
+  // length: item k reuses it when flagged and item k - 1 (item 0: the memo
+  // from before this call) opened the same vector
   std::string& lt_memo = ctx->arena.memo["mle_poly_len"];
   const std::string memo_in = lt_memo;
   std::vector<std::string> lt_key(K);
@@ -2503,19 +2090,9 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
     }
     lt_memo = it.id ? lt_key[k] + std::to_string(Lt[k]) : std::string();
     const Fr evaluation = h_eval[k];
-    std::vector<uint8_t> msg(8 + 32 * it.nvars);
-    u64_to_bytes(it.nvars, msg.data());
-    for (size_t i = 0; i < it.nvars; i++)
-      fr_to_bytes(fr_import(it.point + 4 * i), msg.data() + 8 + 32 * i);
-    transcript_append(state, msg.data(), msg.size());
-    uint8_t b32[32], b64[64];
-    fr_to_bytes(evaluation, b32);
-    transcript_append(state, b32, 32);
-    g1_serialize(s_comm[k], b64);
-    transcript_append(state, b64, 64);
-    rs[k] = transcript_draw_fr(state);
-    QG_CHECK(!rs[k].is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-    rinv[k] = finv(rs[k]);
+    const OpenChallenge ch =
+        open_transcript_step(state, it.point, it.nvars, evaluation, s_comm[k]);
+    rs[k] = ch.r, rinv[k] = ch.r_inv;
     fr_export(evaluation, outs[k].evaluation);
     g1_export(s_comm[k], outs[k].s_comm_xy, &outs[k].s_comm_inf);
   }
@@ -2533,8 +2110,6 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
     poly_eval_reserve(ctx, 6, nmax);
   }
   for (size_t k = 0; k < K; k++) {
-    qg_kzg_opening* o4[4] = {&outs[k].poly_opening, &outs[k].poly_opening_inv,
-                             &outs[k].s_opening, &outs[k].s_opening_inv};
     const Fr* polys[4] = {items[k].poly, items[k].poly, dS[k], dS[k]};
     const size_t slen = fault_short_trim(ctx, (size_t)h_len[2 * k + 1]);
     const size_t ns[4] = {items[k].n, items[k].n, Sn[k], Sn[k]};
@@ -2544,7 +2119,8 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
     std::vector<size_t> qns;
     OpenCkOut ck;
     if (check) ck.d_w = d_w + 4 * k, ck.h_w = h_w + 4 * k, ck.checked = checked.data() + 4 * k;
-    kzg_quotients_batch(ctx, srs, polys, ns, lts, xs, o4, qs, qns, h_y + 4 * k, ck, k);
+    const Open4 o4 = open4(outs[k]);
+    kzg_quotients_batch(ctx, srs, polys, ns, lts, xs, o4.o, qs, qns, h_y + 4 * k, ck, k);
     qs_all.insert(qs_all.end(), qs.begin(), qs.end());
     qns_all.insert(qns_all.end(), qns.begin(), qns.end());
   }
@@ -2555,14 +2131,22 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
     open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + 4 * K), checked, 4, OPEN_QNAME);
   }
   for (size_t k = 0; k < K; k++) {
-    qg_kzg_opening* o4[4] = {&outs[k].poly_opening, &outs[k].poly_opening_inv,
-                             &outs[k].s_opening, &outs[k].s_opening_inv};
+    const Open4 o4 = open4(outs[k]);
     for (int i = 0; i < 4; i++) {
-      fr_export(h_y[4 * k + i], o4[i]->y);
-      g1_export(pis[4 * k + i], o4[i]->proof_xy, &o4[i]->proof_inf);
+      fr_export(h_y[4 * k + i], o4.o[i]->y);
+      g1_export(pis[4 * k + i], o4.o[i]->proof_xy, &o4.o[i]->proof_inf);
     }
   }
   open_batch_trim_scratch(ctx, K);
+}
+
+// a single opening is a batch of one
+static void mle_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* dpoly, size_t n,
+                            const uint64_t* point, size_t nvars, uint8_t state[32],
+                            qg_mle_proof* out, bool unchanged = false, uint64_t poly_id = 0,
+                            size_t poly_off = 0) {
+  mle_open_batch_device(ctx, srs, {{dpoly, n, point, nvars, unchanged, poly_id, poly_off}}, state,
+                        out);
 }
 
 // One opening call: draws its check point sigma and makes an armed test fault
@@ -2605,7 +2189,7 @@ struct OpenCall {
 
 // ---------------------------------------------------------------- inner-product argument
 // InnerProductProof::prove (ipa.rs:59-112) on two device-resident coefficient
-// vectors, shaped like mle_open_device: two host round trips, one for the S
+// vectors, shaped like mle_open_batch_device: two host round trips, one for the S
 // commitment the transcript absorbs, one for the six quotient commitments.
 // The trimmed lengths, the inner product and the six values y are queued into
 // pinned memory and read after those synchronizations.  S is computed by the
@@ -2614,7 +2198,7 @@ struct OpenCall {
 // opening finds a transform to reuse (ntt_F now holds f's).
 // The six openings are three polynomials at r and 1/r (the TODO at ipa.rs:86):
 // six single suffix-Horner jobs, or with QG_IPA_PAIRED=1 (read per call) three
-// paired ones (suffix_horner_pairs); the same bits either way.  Measured
+// paired ones (suffix_horner<2>); the same bits either way.  Measured
 // (profiles/ipa_cost.json): the single jobs' kzg_division is
 // 2-3 % shorter at 2^20 coefficients; at 2^22 the two are within 2 %.
 static const char* const IPA_QNAME[6] = {"f at r", "f at 1/r", "g at r",
@@ -2644,7 +2228,7 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
   trim_launch(ctx, dS, Sn, d_len + 2);
   QG_HIP(hipMemcpyAsync(h_len, d_len, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                         ctx->stream));
-  // its commitment (ipa.rs:73), as mle_open_device commits its S
+  // its commitment (ipa.rs:73), as mle_open_batch_device commits its S
   size_t s_msm = Sn;
   if (Sn > srs->n) {
     ctx->sync();
@@ -2688,14 +2272,14 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
   {
     QgTimed tm(ctx, "kzg_division");
     if (paired) {
-      std::vector<ShIn2> jobs;
+      std::vector<ShIn<2>> jobs;
       for (int p = 0; p < 3; p++)
         if (lts[p]) jobs.push_back({polys[p], lts[p], {r, r_inv}, {s[2 * p], s[2 * p + 1]}});
-      suffix_horner_pairs(ctx, jobs);
+      suffix_horner<2>(ctx, jobs);
     } else {
-      std::vector<ShIn> jobs;
+      std::vector<ShIn<1>> jobs;
       for (int i = 0; i < 6; i++)
-        if (s[i]) jobs.push_back({polys[i >> 1], lts[i >> 1], xs[i & 1], s[i]});
+        if (s[i]) jobs.push_back({polys[i >> 1], lts[i >> 1], {xs[i & 1]}, {s[i]}});
       suffix_horner_many(ctx, jobs);
     }
   }

@@ -10,7 +10,7 @@ product code it mirrors:
   rank allgathers its block of that round's SOURCE tables and finishes
   redundantly.  Gather points before round 0, mid-way and after the last
   local round; bit-exact against the single-process proof.
-* ML-PCS opening (mle_open_sharded / kzg_open_sharded): partial evaluations,
+* ML-PCS opening (mle_open_batch_sharded, one item): partial evaluations,
   replicated S, the suffix-Horner carry exchange and partial MSMs; bit-exact
   against the single-process MLEvalProof incl. trimmed lengths that end
   inside a lower rank's slice.
@@ -112,7 +112,7 @@ def sharded_sumcheck(rank, world, nv, tabs, expr, claimed, domain, gather_log=16
 
 
 def sharded_mle_open(rank, world, poly, point, tau, domain):
-    """mle_open_sharded + kzg_open_sharded (csrc/mlpcs.hip) restated: rank r
+    """mle_open_batch_sharded (csrc/mlpcs.hip) for one item, restated: rank r
     holds poly[r L, (r+1) L) and SRS shard [tau^(rL + i)] g.
     * eq table, local dot -> allgather of the partial evaluations;
     * allgather of the slices; S split by frequency residue (s_poly_sharded,

@@ -378,7 +378,13 @@ def test_sharded_mle_open_batch_matches_sequential(world):
     (QG_OPEN_BATCH_SHARDED=0) and the single-context batch, proof for proof,
     with the same transcript state, at 2^14 evaluations: full vectors, a
     zero tail ending in a lower rank's slice, a vector trimming to one entry,
-    a smaller variable count, and one vector opened twice."""
+    a smaller variable count, and one vector opened twice.
+    The item-by-item openings are K batches of one through the same function,
+    so that comparison checks the batching itself (slot indexing, the
+    exchanges' layouts, the transcript order); the independent witnesses of
+    the sharded path are the single-context reference proofs compared here
+    (single-context openings are pinned to the oracle and its verifier in
+    test_gpu_parity.py and test_gpu_open_check.py)."""
     import os
     import quill_amd as q
     from quill_amd import KZG, Transcript

@@ -228,6 +228,39 @@ def test_kzg_open_large(dev):
     assert op.proof == o.g1_mul(o.G1_GEN, q_tau)
 
 
+SCAN_TAU = 0x5343414E4544474553
+
+
+@pytest.fixture(scope="module")
+def scan_kzg(dev):
+    from quill_amd import KZG
+    k = KZG.trusted_setup(1 << 15, SCAN_TAU, dev)
+    yield k
+    k.close()
+
+
+# (length, trailing zeros): 1, 2, 32 serial only; 33 the first chunked length
+# (a short last chunk); 64 two full chunks; 1024 = 32 chunks (one level, the
+# chunk values serial); 1025 = 33 chunks (a second recursion level); 32769 a
+# third level, its quotient's 32768 coefficients what an SRS of 2^15 holds;
+# 1025 with 40 trailing zeros: the trimmed length 985 ends mid-chunk
+@pytest.mark.parametrize("n,zeros", [(1, 0), (2, 0), (32, 0), (33, 0), (64, 0), (1024, 0),
+                                     (1025, 0), (32769, 0), (1025, 40)])
+def test_kzg_open_scan_edges(dev, scan_kzg, n, zeros):
+    """the univariate opening through the suffix-Horner scan at its structural
+    edges: x, y and the proof point against the oracle's KZG::open at the same
+    tau.  (The inner-product argument's paired and single jobs at 33 and 1025
+    coefficients: test_gpu_ipa.py, cases 33x2 and 1025x1025.)"""
+    rnd = random.Random(n * 64 + zeros)
+    poly = [rnd.randrange(1, R) for _ in range(n - zeros)] + [0] * zeros
+    x = rnd.randrange(R)
+    f0 = dev.counter("open_check_failures")
+    op = scan_kzg.open_univariate(poly, x)
+    want = o.KZG(1 << 15, SCAN_TAU, points=[]).open(poly, x)
+    assert (op.x, op.y, op.proof) == want
+    assert dev.counter("open_check_failures") == f0
+
+
 @pytest.mark.parametrize("case", range(5))
 def test_mle_open_golden(dev, case):
     from quill_amd import KZG, Transcript
@@ -456,7 +489,7 @@ def test_mle_open_zero_tail_matches_oracle(dev, n, nv, live):
     """Vectors whose trailing entries are zero (only the first `live` nonzero;
     live = 0: the zero polynomial): the ML opening commits S over all its
     coefficients and runs the quotients on the trimmed lengths read back after
-    the commitment's synchronization (mlpcs.hip mle_open_device), and every
+    the commitment's synchronization (mlpcs.hip mle_open_batch_device), and every
     field of the proof and the transcript state equal the oracle prover's
     (DensePolynomial trims, kzg.rs:75-96).  The same buffer is then opened
     again with QG_OPEN_UNCHANGED (the trimmed length remembered), and after

@@ -104,7 +104,7 @@ def test_rccl_zerocheck_matches_single(rdev, dev):
 
 @pytest.mark.parametrize("nv,tail_zeros", [(9, 0), (9, 131), (16, 0)])
 def test_rccl_mle_open_matches_single(rdev, dev, nv, tail_zeros):
-    """mle_open_sharded at world 1: the residue-split S polynomial (one block,
+    """mle_open_batch_sharded (a batch of one) at world 1: the residue-split S polynomial (one block,
     half of it zero padding) and its ncclSend/ncclRecv all-to-all, the sharded
     quotients and MSMs; equal to the single-context proof and transcript."""
     import quill_amd as q
