@@ -608,7 +608,28 @@ int qg_trace_marker(qg_ctx* ctx, uint32_t tag);
  * number in use, which a call leaves as it found it (an event that a failed
  * call did not hand back shows here, long before the pool runs dry).
  * "lookup_collectives": collectives issued by qg_lookup_multiplicities_dev on
- * this (sharded) context, at most ncols + 3 per call. */
+ * this (sharded) context, at most ncols + 3 per call.
+ * The sumcheck prover's paths, counted on the host where each kernel is
+ * launched (cumulative over the context's calls):
+ * "sc_big_pure_rounds": large rounds run by the thread-per-pair kernel on a
+ * product of distinct tables (k_sc_big<K,4,true>); "sc_big_sop_rounds": those
+ * it ran on any other expression of at most 4 tables and degree at most 3
+ * (k_sc_big<4,4,false>); "sc_staged_rounds": large rounds run by the
+ * LDS-staged kernel (k_sc_round<K,NP>).
+ * "sc_slice_tails" / "sc_stream_tails": calls whose remaining rounds ran in
+ * the slice tail (k_sc_slice) / in the streaming tail (k_sc_tail).
+ * "sc_generic_calls": calls proved by the interpreted path (expressions
+ * outside the compiled envelope, and every qg_sumcheck_prove_cb call).
+ * "sc_tail_first_round": the round the last compiled call's tail started at
+ * (not cumulative); its parity selects the tail's limb accumulator.
+ * Tuning switches of the compiled prover, read from the environment on every
+ * call: QG_SC_PERS_LOG=<1..30> (tables of at most 2^k entries go to the tail;
+ * default 16, never above what the slice tail holds), QG_SC_BIG_BLOCKS and
+ * QG_SC_BLOCKS=<1..2048> (grid caps of k_sc_big and k_sc_round), QG_SC_STAGED
+ * (set: k_sc_round runs every large round), QG_SC_NO_SKIP0 (set: t = 0 is
+ * evaluated in every round), QG_SC_OLD_TAIL=1 (k_sc_tail instead of
+ * k_sc_slice).  A value outside its range, or not a whole number, makes the
+ * call return QG_ERR_INVALID. */
 int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value);
 /* DensePolynomial::evaluate (pcs/src/kzg.rs:78) on a device vector:
  * out = sum_{i < n} poly[i] * x^(shift + i) (Montgomery in and out), by the

@@ -1692,6 +1692,90 @@ int oc_sumcheck_ref_expr(int nvars, int ntab, const uint64_t* tables, const uint
   return rc;
 }
 
+/* SumcheckProof::prove (sumcheck.rs:28-114) for any expression in evaluation
+ * form, single-threaded: the round message has degree < maxw, so it is fixed
+ * by its values at t = 0..maxw-1.  Per pair every table is low + t (high - low)
+ * (stepped by additions), the postfix program is evaluated at each t, the
+ * values are summed over the pairs, interpolated on the nodes 0..maxw-1 and
+ * trimmed of trailing zeros as ark's DensePolynomial is.  Inputs and outputs
+ * as oc_sumcheck_ref_expr (canonical); with tables_mont != 0 the tables are
+ * Montgomery words (arkworks' in-memory Fr) and are taken as they are.
+ * -1: maxw outside 1..16. */
+int oc_sumcheck_eval_expr(int nvars, int ntab, const uint64_t* tables, const uint32_t* prog,
+                          int plen, const uint64_t* consts, int nconsts, const uint64_t claimed[4],
+                          uint8_t state[32], int maxw, uint64_t* coeffs, uint32_t* lens,
+                          uint64_t* point, uint64_t evaluation[4], int tables_mont) {
+  if (maxw < 1 || maxw > 16) return -1;
+  size_t N = (size_t)1 << nvars;
+  const int nt = ntab ? ntab : 1;
+  fp** gs = (fp**)malloc(sizeof(fp*) * nt);
+  for (int i = 0; i < ntab; i++) {
+    if (tables_mont) {
+      gs[i] = (fp*)malloc(sizeof(fp) * N);
+      memcpy(gs[i], tables + 4 * N * i, sizeof(fp) * N);
+    } else {
+      gs[i] = canon_vec(tables + 4 * N * i, N);
+    }
+  }
+  fp* cs = canon_vec(consts, (size_t)nconsts);
+  fp* lo = (fp*)malloc(sizeof(fp) * nt);
+  fp* df = (fp*)malloc(sizeof(fp) * nt);
+  uint8_t m8[8], b32[32];
+  for (int i = 0; i < 8; i++) m8[i] = (uint8_t)((uint64_t)nvars >> (8 * i));
+  tr_append(state, m8, 8);
+  fr_bytes(canon_in(claimed), b32);
+  tr_append(state, b32, 32);
+  fp V[16][16];
+  sc_vandermonde(maxw, V);
+  const fp zero = {{0, 0, 0, 0}};
+  for (int j = 0; j < nvars; j++) {
+    const size_t half = N >> 1;
+    fp sums[16];
+    for (int t = 0; t < maxw; t++) sums[t] = zero;
+    for (size_t p = 0; p < half; p++) {
+      for (int i = 0; i < ntab; i++) {
+        lo[i] = gs[i][2 * p];
+        df[i] = f_sub(&FR, gs[i][2 * p + 1], gs[i][2 * p]);
+      }
+      for (int t = 0; t < maxw; t++) {
+        sums[t] = f_add(&FR, sums[t], expr_eval_scalar(prog, plen, cs, lo));
+        for (int i = 0; i < ntab; i++) lo[i] = f_add(&FR, lo[i], df[i]);
+      }
+    }
+    /* coefficients, trimmed length; append_serializable(&poly): u64 length +
+     * coefficients; then the challenge */
+    fp co[16];
+    int len = 0;
+    for (int t = 0; t < maxw; t++) {
+      fp acc = zero;
+      for (int u = 0; u < maxw; u++) acc = f_add(&FR, acc, f_mul(&FR, V[t][u], sums[u]));
+      co[t] = acc;
+      if (!f_is_zero(acc)) len = t + 1;
+    }
+    uint8_t buf[8 + 16 * 32];
+    for (int i = 0; i < 8; i++) buf[i] = (uint8_t)((uint64_t)len >> (8 * i));
+    for (int t = 0; t < len; t++) fr_bytes(co[t], buf + 8 + 32 * t);
+    tr_append(state, buf, 8 + 32 * (size_t)len);
+    lens[j] = (uint32_t)len;
+    for (int t = 0; t < maxw; t++)
+      canon_out(t < len ? co[t] : zero, coeffs + 4 * ((size_t)j * maxw + t));
+    const fp r = tr_draw_fr(state);
+    canon_out(r, point + 4 * j);
+    for (int i = 0; i < ntab; i++)
+      for (size_t p = 0; p < half; p++)
+        gs[i][p] = f_add(&FR, gs[i][2 * p], f_mul(&FR, r, f_sub(&FR, gs[i][2 * p + 1], gs[i][2 * p])));
+    N = half;
+  }
+  for (int i = 0; i < ntab; i++) lo[i] = gs[i][0];
+  canon_out(expr_eval_scalar(prog, plen, cs, lo), evaluation);
+  for (int i = 0; i < ntab; i++) free(gs[i]);
+  free(gs);
+  free(cs);
+  free(lo);
+  free(df);
+  return 0;
+}
+
 /* logup_column (multiset_check.rs:43-95): out = m(x) / (beta + h(x)); batch
  * inversion; -2 on a zero denominator (the reference's inverse().unwrap()) */
 int oc_logup_expr(int ntab, size_t n, const uint64_t* tables, const uint32_t* hprog, int hlen,

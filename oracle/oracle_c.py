@@ -57,6 +57,8 @@ def lib():
                                   U64P, U8P, U64P]
         L.oc_sumcheck_ref_expr.argtypes = [C.c_int, C.c_int, U64P, U32P, C.c_int, U64P, C.c_int,
                                            U64P, U8P, C.c_int, U64P, U32P, U64P, U64P]
+        L.oc_sumcheck_eval_expr.argtypes = [C.c_int, C.c_int, U64P, U32P, C.c_int, U64P, C.c_int,
+                                            U64P, U8P, C.c_int, U64P, U32P, U64P, U64P, C.c_int]
         L.oc_logup_expr.argtypes = [C.c_int, C.c_size_t, U64P, U32P, C.c_int, U64P, C.c_int,
                                     U32P, C.c_int, U64P, C.c_int, U64P, U64P]
         L.oc_eq_table.argtypes = [U64P, C.c_int, U64P]
@@ -150,6 +152,74 @@ def sumcheck_prod_mont(nvars, mont_tables, claimed, state: bytes, variant="mt", 
                 for i in range(lens[j])] for j in range(nvars)]
     point = [_unmont(pt[4 * j:4 * j + 4], R_MOD) for j in range(nvars)]
     return r_polys, point, _unmont(ev[:], R_MOD), bytes(st)
+
+
+def expr_postfix(expr):
+    """(op, arg) pairs of an expression tree (.kind in / const / add / mul,
+    .args) and its constants: 0 INPUT, 1 CONST, 2 ADD, 3 MUL"""
+    ops, consts = [], []
+
+    def rec(e):
+        if e.kind == "in":
+            ops.append((0, e.args[0]))
+        elif e.kind == "const":
+            ops.append((1, len(consts)))
+            consts.append(e.args[0] % R_MOD)
+        else:
+            rec(e.args[0])
+            rec(e.args[1])
+            ops.append((2 if e.kind == "add" else 3, 0))
+
+    rec(expr)
+    return ops, consts
+
+
+def sumcheck_expr(nvars, tables, expr, claimed, state: bytes, variant="eval", mont=False):
+    """SumcheckProof::prove of any expression over `tables`; returns (r_polys,
+    point, evaluation, new_state) like sumcheck_prod.
+    variant: "eval" (oc_sumcheck_eval_expr: evaluation form, 1 thread) or "ref"
+    (oc_sumcheck_ref_expr: the reference's per-pair DensePolynomial structure).
+    tables: lists of canonical ints, or with mont=True (2^nvars, 4) uint64 arrays
+    of Montgomery limbs as DeviceVec.to_numpy returns ("eval" only)."""
+    N = 1 << nvars
+    ops, consts = expr_postfix(expr)
+    prog = np.array([v for op in ops for v in op], dtype=np.uint32)
+    maxw = expr.degree() + 1
+
+    def canon(xs):
+        b = b"".join((int(x) % R_MOD).to_bytes(32, "little") for x in xs)
+        return np.frombuffer(b, dtype="<u8").copy() if xs else np.zeros(4, "<u8")
+
+    if mont:
+        assert variant == "eval", "only the evaluation-form oracle takes Montgomery tables"
+        flat = np.ascontiguousarray(np.concatenate(
+            [np.asarray(t, dtype=np.uint64).reshape(N, 4) for t in tables]))
+    else:
+        flat = canon([x for t in tables for x in t])
+    cs, cl = canon(consts), canon([claimed])
+    st = (C.c_uint8 * 32).from_buffer_copy(state)
+    co = np.zeros(4 * nvars * maxw, dtype=np.uint64)
+    lens = np.zeros(nvars, dtype=np.uint32)
+    pt = np.zeros(4 * nvars, dtype=np.uint64)
+    ev = np.zeros(4, dtype=np.uint64)
+    U32P = C.POINTER(C.c_uint32)
+    args = [nvars, len(tables), flat.ctypes.data_as(U64P), prog.ctypes.data_as(U32P), len(ops),
+            cs.ctypes.data_as(U64P), len(consts), cl.ctypes.data_as(U64P), st, maxw,
+            co.ctypes.data_as(U64P), lens.ctypes.data_as(U32P), pt.ctypes.data_as(U64P),
+            ev.ctypes.data_as(U64P)]
+    if variant == "ref":
+        rc = lib().oc_sumcheck_ref_expr(*args)
+    else:
+        rc = lib().oc_sumcheck_eval_expr(*args, 1 if mont else 0)
+    assert rc == 0, "sumcheck message longer than the degree bound"
+
+    def ints(a):
+        b = a.tobytes()
+        return [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(len(b) // 32)]
+
+    allc = ints(co)
+    r_polys = [allc[j * maxw:j * maxw + int(lens[j])] for j in range(nvars)]
+    return r_polys, ints(pt), ints(ev)[0], bytes(st)
 
 
 def cpu_model():

@@ -290,6 +290,13 @@ int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value) {
            : n == "events_created"         ? ctx->events_created
            : n == "events_pooled"          ? ctx->event_pool.size()
            : n == "lookup_collectives"     ? ctx->lookup_collectives
+           : n == "sc_big_pure_rounds"     ? ctx->sc_big_pure_rounds
+           : n == "sc_big_sop_rounds"      ? ctx->sc_big_sop_rounds
+           : n == "sc_staged_rounds"       ? ctx->sc_staged_rounds
+           : n == "sc_slice_tails"         ? ctx->sc_slice_tails
+           : n == "sc_stream_tails"        ? ctx->sc_stream_tails
+           : n == "sc_generic_calls"       ? ctx->sc_generic_calls
+           : n == "sc_tail_first_round"    ? ctx->sc_tail_first_round
                                            : 0;
   return QG_OK;
 }

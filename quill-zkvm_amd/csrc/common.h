@@ -122,6 +122,16 @@ struct qg_ctx {
   // collectives issued by the sharded lookup multiplicities (lookup.hip): at
   // most ncols + 3 per call
   uint64_t lookup_collectives = 0;
+  // which sumcheck kernels ran (sumcheck.hip, counted on the host at the launch
+  // sites): large rounds by kernel, tails by kind, calls of the interpreted
+  // path, and the first round of the last call's tail
+  uint64_t sc_big_pure_rounds = 0;  // k_sc_big<K,4,true>
+  uint64_t sc_big_sop_rounds = 0;   // k_sc_big<4,4,false>
+  uint64_t sc_staged_rounds = 0;    // k_sc_round<K,NP>
+  uint64_t sc_slice_tails = 0;      // k_sc_slice
+  uint64_t sc_stream_tails = 0;     // k_sc_tail
+  uint64_t sc_generic_calls = 0;    // sumcheck_run_generic
+  uint64_t sc_tail_first_round = 0;
 
   // every stream of this context, synchronized (scratch release, destroy)
   static void drain_streams(void* self) { QG_HIP(static_cast<qg_ctx*>(self)->drain_streams_quiet()); }

@@ -24,6 +24,7 @@
 //  * Once a table has <= 2^PERS_LOG entries the remaining rounds run inside one
 //    workgroup (fold + evaluate + transcript per round, synchronized by
 //    barriers), removing 2 launches per round.
+#include <errno.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -89,22 +90,43 @@ static constexpr int SC_MAX_BLOCKS = 2048;  // partial-sum capacity (blocks per 
 // blocks of a big round: ~3 resident blocks per CU, each striding over many
 // pair groups (measured on MI355X at 2^20 vars: 768 blocks 0.764 ms vs 2048
 // blocks 0.798 ms; QG_SC_BLOCKS overrides, for tuning)
-static unsigned sc_round_blocks(qg_ctx* ctx, size_t npairs) {
-  static int ov = [] {
-    const char* e = getenv("QG_SC_BLOCKS");
-    return e ? atoi(e) : 0;
-  }();
+static unsigned sc_round_blocks(qg_ctx* ctx, size_t npairs, int ov) {
   size_t cap = ov > 0 ? (size_t)ov : (size_t)3 * ctx->num_cus();
   cap = std::min<size_t>(cap, SC_MAX_BLOCKS);
   return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, div_up(npairs, SC_BLOCK)));
 }
-// QG_SC_STAGED=1 selects the LDS-staged round kernels (k_sc_round) for the big
-// rounds on one GPU, for A/B runs
-static bool sc_use_staged() {
-  static const bool v = getenv("QG_SC_STAGED") != nullptr;
-  return v;
-}
 static constexpr int PERS_LOG = 16;     // tables of <= 2^16 entries: rounds run in one persistent launch
+
+// The QG_SC_* tuning switches, read once per proof (like QG_SC_OLD_TAIL: tests
+// and A/B runs toggle them in-process).  A number must be whole and within its
+// range: anything else is QG_ERR_INVALID, never a silent default.
+static int sc_env_int(const char* name, long lo, long hi, int unset) {
+  const char* e = getenv(name);
+  if (!e) return unset;
+  char* end = nullptr;
+  errno = 0;
+  const long v = strtol(e, &end, 10);
+  QG_CHECK(end != e && *end == '\0' && errno == 0 && v >= lo && v <= hi, QG_ERR_INVALID,
+           std::string(name) + " must be a whole number in [" + std::to_string(lo) + ", " +
+               std::to_string(hi) + "]");
+  return (int)v;
+}
+struct ScSwitches {
+  int pers_log;      // QG_SC_PERS_LOG: where the persistent tail takes over (default PERS_LOG)
+  int big_blocks;    // QG_SC_BIG_BLOCKS: grid cap of k_sc_big (0: 2 per CU)
+  int round_blocks;  // QG_SC_BLOCKS: grid cap of k_sc_round (0: 3 per CU)
+  bool staged;       // QG_SC_STAGED set: k_sc_round runs every large round (A/B runs)
+  bool no_skip0;     // QG_SC_NO_SKIP0 set: t = 0 is evaluated in every round (A/B runs)
+};
+static ScSwitches sc_switches() {
+  ScSwitches s;
+  s.pers_log = sc_env_int("QG_SC_PERS_LOG", 1, 30, PERS_LOG);
+  s.big_blocks = sc_env_int("QG_SC_BIG_BLOCKS", 1, SC_MAX_BLOCKS, 0);
+  s.round_blocks = sc_env_int("QG_SC_BLOCKS", 1, SC_MAX_BLOCKS, 0);
+  s.staged = getenv("QG_SC_STAGED") != nullptr;
+  s.no_skip0 = getenv("QG_SC_NO_SKIP0") != nullptr;
+  return s;
+}
 
 // device-side program image.  The header and byte arrays are copied into LDS
 // by every block (one parallel load, no dependent scalar-cache misses on the
@@ -1933,16 +1955,13 @@ static bool launch_slice_tail(qg_ctx* ctx, size_t cus, TablePtrs t0, const SopDe
                      gat, d_sp, h, nvars, j0, fold0, pending0, ro, acc_j0, bar8, acc64, d_final,
                      d_eval);
   QG_LAUNCH_CHECK();
+  ctx->sc_slice_tails++;
   return true;
 }
 
 // thread-per-pair round kernel (k_sc_big) for product expressions and for
 // expressions of <= 4 slots at degree <= 3; false: use the staged k_sc_round
-static unsigned sc_big_blocks(qg_ctx* ctx, size_t npairs) {
-  static int ov = [] {
-    const char* e = getenv("QG_SC_BIG_BLOCKS");
-    return e ? atoi(e) : 0;
-  }();
+static unsigned sc_big_blocks(qg_ctx* ctx, size_t npairs, int ov) {
   size_t cap = ov > 0 ? (size_t)ov : (size_t)2 * ctx->num_cus();  // measured best (256 / 512 / 2048 blocks at 2^20: 0.289 / 0.264 / 0.333 ms)
   cap = std::min<size_t>(cap, SC_MAX_BLOCKS);
   return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, div_up(npairs, SC_BLOCK)));
@@ -1952,14 +1971,14 @@ static unsigned sc_big_blocks(qg_ctx* ctx, size_t npairs) {
 template <int K, int NP>
 static int launch_big(qg_ctx* ctx, const std::vector<const Fr*>& src, Fr* X, Fr* Y, size_t N,
                        uint32_t j, const SopDev* d_sp, SopHdr h, size_t npairs, RoundOut ro,
-                       int pending, Fr* loc, uint64_t* a0, uint64_t* a1, uint32_t* bar8) {
+                       int pending, Fr* loc, uint64_t* a0, uint64_t* a1, uint32_t* bar8,
+                       const ScSwitches& sw) {
   // rounds j >= 1: h(0) = h_{j-1}(r_{j-1}) - h(1), exact by construction (the
   // folded table's pair sums ARE the previous message at r); round 0 evaluates
   // every point, so a wrong caller claim still yields the reference's bytes.
   // QG_SC_NO_SKIP0=1 evaluates t = 0 in every round (A/B runs).
-  static const bool no_skip0 = getenv("QG_SC_NO_SKIP0") != nullptr;
-  const int skip0 = (j >= 1 && h.np >= 2 && !no_skip0) ? 1 : 0;
-  if (sc_use_staged() || NP > 4) return -1;
+  const int skip0 = (j >= 1 && h.np >= 2 && !sw.no_skip0) ? 1 : 0;
+  if (sw.staged || NP > 4) return -1;
   const bool pure = (h.pad & SOP_PURE) != 0;
   if (!pure && K > 4) return -1;
   AllBufs tb{};
@@ -1968,7 +1987,7 @@ static int launch_big(qg_ctx* ctx, const std::vector<const Fr*>& src, Fr* X, Fr*
   tb.Y = Y;
   tb.capX = N / 2;
   tb.capY = std::max<size_t>(1, N / 4);
-  const unsigned blocks = sc_big_blocks(ctx, npairs);
+  const unsigned blocks = sc_big_blocks(ctx, npairs, sw.big_blocks);
   // QG_SC_WPE=4: the product sweep compiled for 4 waves per SIMD (<= 128 VGPRs,
   // spills; tuning.  3 waves measured too: 0.214 -> 0.288 ms of big rounds,
   // profiles/r04_sumcheck_wpe_blocks_ab.txt)
@@ -1986,6 +2005,7 @@ static int launch_big(qg_ctx* ctx, const std::vector<const Fr*>& src, Fr* X, Fr*
                        tb, j, d_sp, h, npairs, ro, pending, loc, skip0, (j & 1) ? a1 : a0,
                        (j & 1) ? a0 : a1, bar8);
   QG_LAUNCH_CHECK();
+  (pure ? ctx->sc_big_pure_rounds : ctx->sc_big_sop_rounds)++;
   return skip0;
 }
 
@@ -1994,7 +2014,7 @@ static int launch_big(qg_ctx* ctx, const std::vector<const Fr*>& src, Fr* X, Fr*
 template <int K, int NP>
 static uint32_t run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
                        const SopDev* d_sp, SopHdr h, RoundOut ro, uint32_t* bar, Fr* d_final,
-                       Fr* d_eval) {
+                       Fr* d_eval, const ScSwitches& sw) {
 
   const uint32_t nslots = h.nslots;
   const size_t N = (size_t)1 << nvars;
@@ -2023,10 +2043,7 @@ static uint32_t run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const 
   uint32_t j = 0;
   int parity = 0;  // next destination: 0 -> X, 1 -> Y
   // QG_SC_PERS_LOG overrides where the persistent tail takes over (tuning)
-  static const int pers_log = [] {
-    const char* e = getenv("QG_SC_PERS_LOG");
-    return e ? atoi(e) : PERS_LOG;
-  }();
+  const int pers_log = sw.pers_log;
   {
     QgTimed tm(ctx, "sumcheck_round");
     // the slice tail starts once a round's table fits the blocks' LDS slices
@@ -2042,11 +2059,13 @@ static uint32_t run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const 
         for (int i = 0; i < 8; i++) tp.dst[i] = d.dst[i];
       }
       if (launch_big<K, NP>(ctx, src, X, Y, N, j, d_sp, h, npairs, ro, pending, nullptr, a0, a1,
-                            bar8) < 0) {
-        hipLaunchKernelGGL((k_sc_round<K, NP>), dim3(sc_round_blocks(ctx, npairs)), dim3(SC_BLOCK),
-                           0, ctx->stream, tp, d_sp, h, npairs, fold, ro, j, pending, partial,
+                            bar8, sw) < 0) {
+        hipLaunchKernelGGL((k_sc_round<K, NP>),
+                           dim3(sc_round_blocks(ctx, npairs, sw.round_blocks)), dim3(SC_BLOCK), 0,
+                           ctx->stream, tp, d_sp, h, npairs, fold, ro, j, pending, partial,
                            (Fr*)nullptr);
         staged = true;
+        ctx->sc_staged_rounds++;
       }
       QG_LAUNCH_CHECK();
       if (fold) {
@@ -2078,6 +2097,7 @@ static uint32_t run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const 
     // round j's accumulator slot was cleared by the last big round (or the
     // per-call header when there is none)
     clear_tail_slot(j);
+    ctx->sc_tail_first_round = j;
     if (!launch_slice_tail<K, NP>(ctx, ctx->num_cus(), t0, d_sp, h, nvars, j, fold, pending, ro,
                                   bar, (j & 1) ? a1 : a0, d_final, d_eval)) {
       // persistent launch: one block per CU at most (co-residency for the grid
@@ -2091,6 +2111,7 @@ static uint32_t run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const 
                          bufA, bufB, d_sp, h, nvars, j, fold, pending, ro, ppart, bar, d_final,
                          d_eval);
       QG_LAUNCH_CHECK();
+      ctx->sc_stream_tails++;
     }
   }
   return j;
@@ -2120,7 +2141,7 @@ static constexpr uint32_t SC_GATHER_LOG = 16;
 template <int K, int NP>
 static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
                             const SopDev* d_sp, SopHdr h, RoundOut ro, uint32_t* bar, Fr* d_final,
-                            Fr* d_eval) {
+                            Fr* d_eval, const ScSwitches& sw) {
   const uint32_t nslots = h.nslots;
   const uint32_t world = (uint32_t)ctx->world;
   uint32_t lw = 0;
@@ -2166,12 +2187,15 @@ static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<c
         const TablePtrs& d = parity ? tY : tX;
         for (int i = 0; i < 8; i++) tp.dst[i] = d.dst[i];
       }
-      int skip0 = launch_big<K, NP>(ctx, src, X, Y, NL, j, d_sp, h, npairs, ro, 0, loc, a0, a1, bar8);
+      int skip0 =
+          launch_big<K, NP>(ctx, src, X, Y, NL, j, d_sp, h, npairs, ro, 0, loc, a0, a1, bar8, sw);
       if (skip0 < 0) {
         skip0 = 0;
         staged = true;
-        hipLaunchKernelGGL((k_sc_round<K, NP>), dim3(sc_round_blocks(ctx, npairs)), dim3(SC_BLOCK),
-                           0, ctx->stream, tp, d_sp, h, npairs, fold, ro, j, 0, partial, loc);
+        hipLaunchKernelGGL((k_sc_round<K, NP>),
+                           dim3(sc_round_blocks(ctx, npairs, sw.round_blocks)), dim3(SC_BLOCK), 0,
+                           ctx->stream, tp, d_sp, h, npairs, fold, ro, j, 0, partial, loc);
+        ctx->sc_staged_rounds++;
       }
       QG_LAUNCH_CHECK();
       comm_allgather_bytes(ctx, loc, all, sizeof(Fr) * NP);
@@ -2230,6 +2254,7 @@ static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<c
     const size_t cus = comm_is_loopback(ctx) ? std::max<size_t>(1, ctx->num_cus() / world)
                                              : (size_t)ctx->num_cus();
     clear_tail_slot(js);
+    ctx->sc_tail_first_round = js;
     if (!launch_slice_tail<K, NP>(ctx, cus, t0, d_sp, h, nvars, js, js >= 1 ? 1 : 0, 0, ro, bar,
                                   (js & 1) ? a1 : a0, d_final, d_eval)) {
       const unsigned grid = (unsigned)std::max<size_t>(
@@ -2239,6 +2264,7 @@ static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<c
                          bufA, bufB, d_sp, h, nvars, js, js >= 1 ? 1 : 0, 0, ro, ppart, bar,
                          d_final, d_eval);
       QG_LAUNCH_CHECK();
+      ctx->sc_stream_tails++;
     }
   }
   return js;
@@ -2247,9 +2273,10 @@ static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<c
 template <int K, int NP>
 static uint32_t run_rounds_any(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
                                const SopDev* d_sp, SopHdr h, RoundOut ro, uint32_t* bar,
-                               Fr* d_final, Fr* d_eval) {
-  if (ctx->sharded) return run_rounds_dist<K, NP>(ctx, nvars, src, d_sp, h, ro, bar, d_final, d_eval);
-  return run_rounds<K, NP>(ctx, nvars, src, d_sp, h, ro, bar, d_final, d_eval);
+                               Fr* d_final, Fr* d_eval, const ScSwitches& sw) {
+  if (ctx->sharded)
+    return run_rounds_dist<K, NP>(ctx, nvars, src, d_sp, h, ro, bar, d_final, d_eval, sw);
+  return run_rounds<K, NP>(ctx, nvars, src, d_sp, h, ro, bar, d_final, d_eval, sw);
 }
 
 // inverse Vandermonde on nodes 0..np-1 for any np <= GEN_NPMAX: V[t][u]
@@ -2409,6 +2436,7 @@ static void sumcheck_run_generic(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
                                  const uint64_t claimed_sum[4], uint8_t state[32],
                                  uint64_t* round_coeffs, uint32_t* round_lens, uint64_t* point,
                                  uint64_t evaluation[4], const ScChallengeCb* cb = nullptr) {
+  ctx->sc_generic_calls++;
   const uint32_t world = (uint32_t)ctx->world;
   uint32_t lw = 0;
   while ((1u << lw) < world) lw++;
@@ -2611,6 +2639,7 @@ static void sumcheck_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
                          const uint64_t claimed_sum[4], uint8_t state[32], uint64_t* round_coeffs,
                          uint32_t* round_lens, uint64_t* point, uint64_t evaluation[4]) {
   QG_CHECK(nvars >= 1 && nvars <= 40, QG_ERR_INVALID, "nvars out of range");
+  const ScSwitches sw = sc_switches();
   std::shared_ptr<const ScProgram> P;
   try {
     P = get_program(prog, prog_len, consts, nconsts, ntables);
@@ -2671,13 +2700,13 @@ static void sumcheck_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
   // (with no used slots, nslots = 0 and loads are skipped)
   uint32_t tail0;
   if (np <= 4) {
-    if (nsrc <= 4) tail0 = run_rounds_any<4, 4>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval);
-    else tail0 = run_rounds_any<8, 4>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval);
+    if (nsrc <= 4) tail0 = run_rounds_any<4, 4>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
+    else tail0 = run_rounds_any<8, 4>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
   } else if (np <= 8) {
-    if (nsrc <= 4) tail0 = run_rounds_any<4, 8>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval);
-    else tail0 = run_rounds_any<8, 8>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval);
+    if (nsrc <= 4) tail0 = run_rounds_any<4, 8>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
+    else tail0 = run_rounds_any<8, 8>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
   } else {
-    tail0 = run_rounds_any<8, 16>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval);
+    tail0 = run_rounds_any<8, 16>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
   }
 
   QG_HIP(hipMemcpyAsync(hio, io, io_bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -167,3 +167,73 @@ def test_c_sumcheck_mont_entry_matches_list_entry():
     for variant in ("mt", "eval"):
         b = oc.sumcheck_prod_mont(nv, [_to_limbs(t) for t in tabs], 1234, st, variant=variant)
         assert a == b
+
+
+# --- oc_sumcheck_eval_expr: the fast expression-general oracle ----------------
+def _eval_expr_triple(case_name, nv, tabs=None, claimed=None, mont=False):
+    """(prove_fast, oc_sumcheck_eval_expr, oc_sumcheck_ref_expr) on one input"""
+    import sumcheck_cases as sc
+    case = sc.BY_NAME[case_name]
+    if tabs is None:
+        tabs = sc.tables(nv, case.ntab, seed=5)
+    if claimed is None:
+        claimed = sc.true_sum(case, tabs)
+    expr = sc.oracle_expr(case)
+    label = b"eval-expr"
+    py = sc.oracle_prove(nv, tabs, expr, claimed, label)
+    st0 = o.Transcript(label).state
+    ev = oc.sumcheck_expr(nv, tabs, expr, claimed, st0, variant="eval")
+    ref = oc.sumcheck_expr(nv, tabs, expr, claimed, st0, variant="ref")
+    return py, ev, ref
+
+
+def _eval_expr_names():
+    import sumcheck_cases as sc
+    return [c.name for c in sc.CASES]
+
+
+@pytest.mark.parametrize("nv", [1, 2, 5, 10])
+@pytest.mark.parametrize("name", _eval_expr_names())
+def test_c_eval_expr_matches_python_and_ref(name, nv):
+    """Round messages (with their trimmed lengths), point, final evaluation and
+    transcript state of oc_sumcheck_eval_expr equal, bit for bit, the Python
+    evaluation-form prover and the reference-structured C prover."""
+    py, ev, ref = _eval_expr_triple(name, nv)
+    assert ev == py
+    assert ev == ref
+
+
+@pytest.mark.parametrize("name", ["fac_sop", "fac_k4d4"])
+@pytest.mark.parametrize("kind", ["zero_factor", "const_bit0", "const_bits01", "small_values",
+                                  "false_claim"])
+def test_c_eval_expr_degenerate_tables(name, kind):
+    """Trimming: an all-zero factor (every message empty), tables constant in
+    the low index bits (round messages of lower degree), tables of 0 / 1 / r-1,
+    and a false claimed sum."""
+    import sumcheck_cases as sc
+    nv = 5
+    case = sc.BY_NAME[name]
+    tabs = sc.degenerate_tables(kind, nv, case.ntab)
+    claimed = sc.true_sum(case, tabs)
+    if kind == "false_claim":
+        claimed = (claimed + 1) % o.R_MOD
+    py, ev, ref = _eval_expr_triple(name, nv, tabs, claimed)
+    assert ev == py
+    assert ev == ref
+    if kind == "zero_factor":
+        assert all(len(m) == 0 for m in ev[0])
+    if kind == "const_bit0":
+        assert len(ev[0][0]) < case.degree + 1 and len(ev[0][1]) == case.degree + 1
+
+
+def test_c_eval_expr_montgomery_tables():
+    """Montgomery words in (as DeviceVec.to_numpy gives them): the same proof"""
+    import numpy as np
+    import sumcheck_cases as sc
+    nv, case = 6, sc.BY_NAME["k8d5"]
+    tabs = sc.tables(nv, case.ntab, seed=6)
+    expr = sc.oracle_expr(case)
+    st0 = o.Transcript(b"mont").state
+    a = oc.sumcheck_expr(nv, tabs, expr, 99, st0)
+    mont = [np.array([oc._mont(x, o.R_MOD) for x in t], dtype=np.uint64) for t in tabs]
+    assert oc.sumcheck_expr(nv, mont, expr, 99, st0, mont=True) == a
