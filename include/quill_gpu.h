@@ -622,14 +622,24 @@ int qg_trace_marker(qg_ctx* ctx, uint32_t tag);
  * outside the compiled envelope, and every qg_sumcheck_prove_cb call).
  * "sc_tail_first_round": the round the last compiled call's tail started at
  * (not cumulative); its parity selects the tail's limb accumulator.
- * Tuning switches of the compiled prover, read from the environment on every
- * call: QG_SC_PERS_LOG=<1..30> (tables of at most 2^k entries go to the tail;
- * default 16, never above what the slice tail holds), QG_SC_BIG_BLOCKS and
- * QG_SC_BLOCKS=<1..2048> (grid caps of k_sc_big and k_sc_round), QG_SC_STAGED
- * (set: k_sc_round runs every large round), QG_SC_NO_SKIP0 (set: t = 0 is
- * evaluated in every round), QG_SC_OLD_TAIL=1 (k_sc_tail instead of
- * k_sc_slice).  A value outside its range, or not a whole number, makes the
- * call return QG_ERR_INVALID. */
+ * Tuning switches of the compiled prover, all read from the environment once
+ * per proof (csrc/sumcheck_plan.h, sc_switches):
+ *   QG_SC_PERS_LOG=<1..30>    tables of at most 2^k entries go to the tail
+ *                             (default 16, never above what the slice tail
+ *                             holds); on a sharded context it also lowers the
+ *                             gather point: the ranks gather their blocks once
+ *                             the folded tables' global size is at most
+ *                             2^min(16, k)
+ *   QG_SC_BIG_BLOCKS=<1..2048> grid cap of k_sc_big (default 2 per CU)
+ *   QG_SC_BLOCKS=<1..2048>    grid cap of k_sc_round (default 3 per CU)
+ *   QG_SC_STAGED (set)        k_sc_round runs every large round
+ *   QG_SC_NO_SKIP0 (set)      t = 0 is evaluated in every round
+ *   QG_SC_OLD_TAIL=<non-zero> k_sc_tail instead of k_sc_slice
+ *   QG_SC_WPE (set)           the product sweep built for 4 waves per SIMD
+ *   QG_SC_TAIL_BPC=<k>        blocks per CU of a tail's grid cap (default 1;
+ *                             below 1 counts as 1; never above occupancy - 1)
+ * For the first three, a value outside its range, or not a whole number, makes
+ * the call return QG_ERR_INVALID. */
 int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value);
 /* DensePolynomial::evaluate (pcs/src/kzg.rs:78) on a device vector:
  * out = sum_{i < n} poly[i] * x^(shift + i) (Montgomery in and out), by the

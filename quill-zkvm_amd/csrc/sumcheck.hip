@@ -17,13 +17,16 @@
 //  * Round j (j >= 1) fuses the fold by r_{j-1} with the round-j evaluation:
 //    each thread reads 4 entries of every table, writes the 2 folded entries
 //    and evaluates the pair they form — one HBM pass per round.
-//  * Per-block partial sums -> a one-block "finish" kernel that sums them,
-//    interpolates (inverse Vandermonde on t = 0..d), trims, serializes, runs the
-//    BLAKE3 transcript on the device and writes r_j for the next fold.  No host
-//    round trip inside the protocol.
-//  * Once a table has <= 2^PERS_LOG entries the remaining rounds run inside one
-//    workgroup (fold + evaluate + transcript per round, synchronized by
-//    barriers), removing 2 launches per round.
+//  * The block sums of a round go into a limb accumulator; the round's last
+//    block collects them, interpolates (inverse Vandermonde on t = 0..d), trims,
+//    serializes, runs the BLAKE3 transcript on the device and writes r_j for
+//    the next fold.  No host round trip inside the protocol.
+//  * Once a table has <= 2^PERS_LOG entries the remaining rounds run in one
+//    persistent launch (fold + evaluate + transcript per round, synchronized by
+//    grid barriers).
+//  * Which kernel runs which round on which grid, where the tail takes over,
+//    which buffer a round reads and writes and the io region's layout are host
+//    decisions on plain integers: sumcheck_plan.h.
 #include <errno.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -40,6 +43,7 @@
 #include "common.h"
 #include "expr.h"
 #include "field29.h"
+#include "sumcheck_plan.h"
 
 using namespace qg;
 
@@ -84,50 +88,6 @@ __device__ unsigned long long g_sc_wtrace[4 * 512 * 8 * 2];
   } while (0)
 #endif
 
-static constexpr int SC_BLOCK = 256;
-static constexpr int SC_MAX_BLOCKS = 2048;  // partial-sum capacity (blocks per big round)
-
-// blocks of a big round: ~3 resident blocks per CU, each striding over many
-// pair groups (measured on MI355X at 2^20 vars: 768 blocks 0.764 ms vs 2048
-// blocks 0.798 ms; QG_SC_BLOCKS overrides, for tuning)
-static unsigned sc_round_blocks(qg_ctx* ctx, size_t npairs, int ov) {
-  size_t cap = ov > 0 ? (size_t)ov : (size_t)3 * ctx->num_cus();
-  cap = std::min<size_t>(cap, SC_MAX_BLOCKS);
-  return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, div_up(npairs, SC_BLOCK)));
-}
-static constexpr int PERS_LOG = 16;     // tables of <= 2^16 entries: rounds run in one persistent launch
-
-// The QG_SC_* tuning switches, read once per proof (like QG_SC_OLD_TAIL: tests
-// and A/B runs toggle them in-process).  A number must be whole and within its
-// range: anything else is QG_ERR_INVALID, never a silent default.
-static int sc_env_int(const char* name, long lo, long hi, int unset) {
-  const char* e = getenv(name);
-  if (!e) return unset;
-  char* end = nullptr;
-  errno = 0;
-  const long v = strtol(e, &end, 10);
-  QG_CHECK(end != e && *end == '\0' && errno == 0 && v >= lo && v <= hi, QG_ERR_INVALID,
-           std::string(name) + " must be a whole number in [" + std::to_string(lo) + ", " +
-               std::to_string(hi) + "]");
-  return (int)v;
-}
-struct ScSwitches {
-  int pers_log;      // QG_SC_PERS_LOG: where the persistent tail takes over (default PERS_LOG)
-  int big_blocks;    // QG_SC_BIG_BLOCKS: grid cap of k_sc_big (0: 2 per CU)
-  int round_blocks;  // QG_SC_BLOCKS: grid cap of k_sc_round (0: 3 per CU)
-  bool staged;       // QG_SC_STAGED set: k_sc_round runs every large round (A/B runs)
-  bool no_skip0;     // QG_SC_NO_SKIP0 set: t = 0 is evaluated in every round (A/B runs)
-};
-static ScSwitches sc_switches() {
-  ScSwitches s;
-  s.pers_log = sc_env_int("QG_SC_PERS_LOG", 1, 30, PERS_LOG);
-  s.big_blocks = sc_env_int("QG_SC_BIG_BLOCKS", 1, SC_MAX_BLOCKS, 0);
-  s.round_blocks = sc_env_int("QG_SC_BLOCKS", 1, SC_MAX_BLOCKS, 0);
-  s.staged = getenv("QG_SC_STAGED") != nullptr;
-  s.no_skip0 = getenv("QG_SC_NO_SKIP0") != nullptr;
-  return s;
-}
-
 // device-side program image.  The header and byte arrays are copied into LDS
 // by every block (one parallel load, no dependent scalar-cache misses on the
 // evaluation path), followed by the 29-bit-limb constants.
@@ -147,7 +107,6 @@ struct SopDev {
   uint8_t skip29[SOP_MAXM];  // 1: product already at scale S (no multiply)
   uint8_t fac[SOP_MAXF];
   L9 c29[SOP_MAXM];          // per-monomial multiplier (or constant term), plain integer
-  L9 vm29[16 * 16];          // interpolation -> Montgomery coefficients (R = 2^256)
   L9 vc29[16 * 16];          // interpolation -> canonical coefficients (transcript bytes)
   L9 t29[16];                // t * 2^261 mod p (evaluation-point offsets, NP > 4)
   L9 cr29[4];                // 2^522, 2^778 (-> r * 2^261); 2^517, 2^773 (-> r * 2^256)
@@ -171,7 +130,6 @@ template <int NP>
 struct SopLds {
   uint32_t w[SOP_HDR_WORDS];
   R29 c29[SOP_MAXM];
-  R29 vm[NP * NP];
   R29 vc[NP * NP];
   R29 t29[NP];
   R29 cr[4];
@@ -181,6 +139,7 @@ struct SopLds {
   QG_DEV uint32_t fac(uint32_t f) const { return ((const uint8_t*)w)[16 + 2 * SOP_MAXM + f]; }
 };
 
+// vinv: with the interpolation rows (the blocks that run a transcript step)
 template <int NP>
 QG_DEV void sop_load(SopLds<NP>& s, const SopDev* __restrict__ g, const SopHdr& h, bool vinv) {
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
@@ -196,7 +155,6 @@ QG_DEV void sop_load(SopLds<NP>& s, const SopDev* __restrict__ g, const SopHdr& 
   if (vinv) {
     for (uint32_t i = tid; i < h.np * h.np * 9; i += nt) {
       const uint32_t e = i / 9, k = i % 9, t = e / h.np, u = e % h.np;
-      s.vm[t * NP + u].l[k] = g->vm29[t * 16 + u].v[k];
       s.vc[t * NP + u].l[k] = g->vc29[t * 16 + u].v[k];
     }
   }
@@ -242,10 +200,7 @@ QG_DEV Fr sop_eval_final(const SopDev* __restrict__ g, uint32_t nmono, const Fr 
   return acc;
 }
 
-struct TablePtrs {
-  const Fr* src[8];
-  Fr* dst[8];
-};
+using RoundBufs = RoundBufsT<Fr>;  // sumcheck_plan.h: where round j reads and writes
 
 // ---------------------------------------------------------------- in-launch hand-offs
 // Data handed between workgroups INSIDE one launch (partial rows, the
@@ -314,6 +269,58 @@ QG_DEV Fr lt_p(const Fr& x) {
   return r;
 }
 
+// the fold of one pair, x0 + r (x1 - x0): x1 - x0 + 4p (lazy) times r (< 2p)
+// -> < 2p; + x0 -> < 4p; stored < 2p
+QG_DEV R29 fold29(const R29& x0, const R29& x1, const R29& r) {
+  return red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
+}
+
+// the fold multiplier of the round: the last challenge * 2^261 (< 2p)
+QG_DEV R29 load_r29(const ScState* st) {
+  R29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = st->r29[i];
+  return r;
+}
+
+// Thread (pair pl, point t): h at lo + t (hi - lo) over the staged entries
+// F[slot * ss + 2 pl + half] (ss: the slot stride), added into acc (< 2p).
+template <int NP>
+QG_DEV void eval_pair_point(const R29* F, uint32_t ss, const SopLds<NP>& sp, const SopHdr& h,
+                            uint32_t pl, uint32_t t, R29& acc) {
+  R29 sum = R29::zero();
+  uint32_t f = 0;
+  for (uint32_t m = 0; m < h.nmono; m++) {
+    const uint32_t len = sp.mono_len(m);
+    R29 prod;
+    if (len == 0) {
+      prod = sp.c29[m];
+    } else {
+      for (uint32_t q = 0; q < len; q++) {
+        const uint32_t s = sp.fac(f + q);
+        const R29 lo = F[s * ss + 2 * pl], hi = F[s * ss + 2 * pl + 1];
+        R29 v;
+        if constexpr (NP <= 4) {
+          // lo + t (hi - lo + 4p): lazy, < 20p; the first factor takes one carry
+          // pass, later ones stay lazy (see at_point_lazy)
+          const R29 d = norm29(sub29(hi, lo));
+          R29 a = lo;
+          if (t & 1u) a = add29(a, d);
+          if (t & 2u) a = add29(a, add29(d, d));
+          v = q == 0 ? norm29(a) : a;
+        } else {
+          v = norm29(add29(lo, mul29(sub29(hi, lo), sp.t29[t])));  // < 4p
+        }
+        prod = q == 0 ? v : mul29(prod, v);
+      }
+      if (!sp.skip(m) || len == 1) prod = mul29(prod, sp.c29[m]);
+    }
+    f += len;
+    sum = red6p(add29(sum, prod));
+  }
+  acc = red6p(add29(acc, sum));
+}
+
 // ---------------------------------------------------------------------------
 // Work layout of a round.  A block handles PB = BLOCK / NP pairs per step:
 //   phase F: items (slot, pair, half) — fold (x0 + r (x1 - x0)) or copy one
@@ -347,9 +354,7 @@ QG_DEV void round_sweep(RoundLds<K, NP, BLOCK>& L, const SopLds<NP>& sp, const S
       if (p < npairs) {
         if (fold) {
           const Fr* src = L.src[s] + 4 * p + 2 * (e & 1);
-          const R29 x0 = to29(src[0]), x1 = to29(src[1]);
-          // x0 + r (x1 - x0): x1 - x0 + 4p (lazy) times r (< 2p) -> < 2p; + x0 -> < 4p
-          v = red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
+          v = fold29(to29(src[0]), to29(src[1]), r);
           L.dst[s][2 * p + (e & 1)] = from29(v);
         } else {
           v = to29(L.src[s][2 * p + (e & 1)]);
@@ -358,39 +363,7 @@ QG_DEV void round_sweep(RoundLds<K, NP, BLOCK>& L, const SopLds<NP>& sp, const S
       L.F[s * PB * 2 + e] = v;
     }
     __syncthreads();
-    if (t < h.np && base + pl < npairs) {
-      R29 sum = R29::zero();
-      uint32_t f = 0;
-      for (uint32_t m = 0; m < h.nmono; m++) {
-        const uint32_t len = sp.mono_len(m);
-        R29 prod;
-        if (len == 0) {
-          prod = sp.c29[m];
-        } else {
-          for (uint32_t q = 0; q < len; q++) {
-            const uint32_t s = sp.fac(f + q);
-            const R29 lo = L.F[(s * PB + pl) * 2], hi = L.F[(s * PB + pl) * 2 + 1];
-            R29 v;
-            if constexpr (NP <= 4) {
-              // lo + t (hi - lo + 4p): lazy, < 20p, then one carry pass
-              const R29 d = norm29(sub29(hi, lo));
-              R29 a = lo;
-              if (t & 1u) a = add29(a, d);
-              if (t & 2u) a = add29(a, add29(d, d));
-              v = norm29(a);
-            } else {
-              v = add29(lo, mul29(sub29(hi, lo), sp.t29[t]));  // < 4p, lazy
-              v = norm29(v);
-            }
-            prod = q == 0 ? v : mul29(prod, v);
-          }
-          if (!sp.skip(m) || len == 1) prod = mul29(prod, sp.c29[m]);
-        }
-        f += len;
-        sum = red6p(add29(sum, prod));
-      }
-      acc = red6p(add29(acc, sum));
-    }
+    if (t < h.np && base + pl < npairs) eval_pair_point<NP>(L.F, 2 * PB, sp, h, pl, t, acc);
     __syncthreads();
   }
 }
@@ -484,23 +457,11 @@ QG_DEV void sum_rows29(const Fr* rows, uint32_t nrows, uint32_t np, R29* red, R2
   block_reduce_pts<NP>(a, np, red, res);
 }
 
-// Round bookkeeping.  The transcript state, the deferred absorb, the current
-// challenge in 29-bit form and the last-block election counter live in one
-// small device struct.
-struct ScState {
-  uint32_t state[8];  // absorbed transcript state
-  uint32_t pend[20];  // state' || 48 challenge bytes of the last round, not yet absorbed
-  uint32_t ticket;    // blocks of the current round that have published partials
-  uint32_t err;       // persistent-kernel barrier timeout flag
-  uint32_t r29[9];    // last challenge * 2^261 mod p (< 2p), the fold multiplier
-  uint32_t pad[1];
-  uint32_t claim[8];  // this round's claim h_{j-1}(r_{j-1}) at scale S (big rounds, j >= 1)
-};
-
+// the outputs of a round in the io region (ScState and ScIo: sumcheck_plan.h)
 struct RoundOut {
   ScState* st;
   Fr* chal;          // nvars challenges (Montgomery, R = 2^256)
-  Fr* coeffs;        // nvars x width (Montgomery)
+  Fr* coeffs;        // nvars x width (canonical words: the host converts the rows)
   uint32_t* lens;    // nvars
   uint32_t width;    // row width (>= np)
 };
@@ -517,26 +478,23 @@ struct FinSmem {
 // Round message, transcript and challenge from the np round sums ev[] (LDS,
 // canonical words at scale S).  Whole block calls (barriers); wave 0 works.
 // Interpolation is lane-parallel over (coefficient t, node u): each lane
-// multiplies by the inverse-Vandermonde entry scaled to give the Montgomery
-// coefficient (proof output) and the canonical one (transcript bytes), then a
-// shuffle sum over u.  Trim by ballot; BLAKE3 on one DPP quad; r from four
-// lanes (r * 2^261 for the fold and r * 2^256 for the output, each lo + hi).
-// Absorbing the 48 challenge bytes is deferred when pend_out != nullptr.
+// multiplies by the inverse-Vandermonde entry scaled to give the canonical
+// coefficient (the transcript's bytes), then a shuffle sum over u.  The writer
+// stores those canonical words in ro.coeffs (the host converts the rows to
+// Montgomery form, keeping ~1 us off every round).  Trim by ballot; BLAKE3 on
+// one DPP quad; r from four lanes (r * 2^261 for the fold and r * 2^256 for
+// the output, each lo + hi).  Absorbing the 48 challenge bytes is deferred
+// when pend_out != nullptr.
 template <int NP>
-// canon_out: the writer stores the CANONICAL coefficients (the transcript's) in
-// ro.coeffs right away and skips the Montgomery pass after the challenge (the
-// persistent tail: the host converts those rows, keeping ~1 us off every round)
 QG_DEV void finish_core(const SopLds<NP>& sp, uint32_t np, const R29* ev, const RoundOut& ro,
                         uint32_t j, FinSmem& fs, const uint32_t* state_in, uint32_t* pend_out,
-                        uint32_t* state_out, uint32_t tr = 4096, bool writer = true,
-                        bool canon_out = false) {
+                        uint32_t* state_out, uint32_t tr = 4096, bool writer = true) {
   constexpr uint32_t U = NP <= 8 ? NP : 4;  // lanes per coefficient
   const uint32_t tid = threadIdx.x;
   const bool w0 = tid < 64;
   const uint32_t ct = tid / U, cu = tid % U;
-  // canonical coefficients (transcript bytes) first; the Montgomery ones (proof
-  // output) after the challenge.  Lazy sums: <= 4 terms < 2p per lane, U <= 8
-  // lanes: < 64p before the one reduction.
+  // Lazy sums: <= 4 terms < 2p per lane, U <= 8 lanes: < 64p before the one
+  // reduction.
   R29 cc = R29::zero();
   if (w0 && ct < np) {
     for (uint32_t u = cu; u < np; u += U) cc = add29(cc, mul29(sp.vc[ct * NP + u], ev[u]));
@@ -547,7 +505,7 @@ QG_DEV void finish_core(const SopLds<NP>& sp, uint32_t np, const R29* ev, const 
   // U <= 8 products < 2p each: < 16p
   const Fr ccw = from29(canon29(red16p29<FrP>(cc)));
   const bool lead = w0 && cu == 0 && ct < np;
-  if (writer && canon_out && lead) ro.coeffs[(size_t)j * ro.width + ct] = ccw;
+  if (writer && lead) ro.coeffs[(size_t)j * ro.width + ct] = ccw;
   if (writer) {
     for (uint32_t i = np + tid; i < ro.width; i += blockDim.x)
       ro.coeffs[(size_t)j * ro.width + i] = Fr::zero();
@@ -605,107 +563,21 @@ QG_DEV void finish_core(const SopLds<NP>& sp, uint32_t np, const R29* ev, const 
   __syncthreads();
   SC_TR(tr + 6);
   if (!pend_out && w0) b3_hash_quad(fs.ab, 80, state_out, 8);
-  if (writer && !canon_out) {
-    // Montgomery coefficients for the proof output (off the challenge path)
-    R29 cm = R29::zero();
-    if (w0 && ct < np) {
-      for (uint32_t u = cu; u < np; u += U) cm = add29(cm, mul29(sp.vm[ct * NP + u], ev[u]));
-    }
-    cm = norm29(cm);
-#pragma unroll
-    for (uint32_t m = 1; m < U; m <<= 1) cm = norm29(add29(cm, shfl_xor29(cm, m)));
-    if (lead) ro.coeffs[(size_t)j * ro.width + ct] = from29(canon29(red128p(cm)));
-  }
 }
 
-// round kernel: fused fold(r_{j-1}) + evaluate at t = 0..np-1, per-block
-// partial sums; the last block to publish (ticket election) sums the partials
-// and, with loc == nullptr, runs the round's transcript step itself; with
-// loc != nullptr (sharded) it writes this rank's local sums for the allgather.
-template <int K, int NP>
-__global__ void __launch_bounds__(SC_BLOCK)
-    k_sc_round(TablePtrs tp, const SopDev* __restrict__ spg, SopHdr h, size_t npairs, int fold,
-               RoundOut ro, uint32_t j, int pending, Fr* __restrict__ partial, Fr* __restrict__ loc) {
-  __shared__ SopLds<NP> sp;
-  __shared__ RoundLds<K, NP, SC_BLOCK> L;
-  __shared__ R29 red[(SC_BLOCK / 64) * NP];
-  __shared__ R29 res[NP];
-  __shared__ FinSmem fs;
-  __shared__ uint32_t last;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t tr = 1024 + 16 * j;
-  if (blockIdx.x == 0) SC_TR(tr + 0);
-  sop_load<NP>(sp, spg, h, loc == nullptr);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    if (tid == (uint32_t)i) {
-      L.src[i] = tp.src[i];
-      L.dst[i] = tp.dst[i];
-    }
-  }
-  R29 r = R29::zero();
-  if (fold) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = ro.st->r29[i];
-  }
-  if (pending && blockIdx.x == 0 && tid >= 64 && tid < 128) {
-    // deferred absorb of round j-1's challenge bytes (wave 1 of block 0),
-    // handed to the last block write-through (see k_sc_big)
-    if (tid - 64 < 32) fs.ab[tid - 64] = tid - 64 < 20 ? ro.st->pend[tid - 64] : 0u;
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    b3_hash_quad(fs.ab, 80, fs.chin, 8);
-    __builtin_amdgcn_wave_barrier();
-    if (tid - 64 < 8) st_sc1_u32(&ro.st->state[tid - 64], fs.chin[tid - 64]);
-  }
-  __syncthreads();
-  constexpr uint32_t PB = SC_BLOCK / NP;
-  R29 acc = R29::zero();
-  round_sweep<K, NP, SC_BLOCK>(L, sp, h, npairs, fold != 0, r, (size_t)blockIdx.x * PB,
-                               (size_t)gridDim.x * PB, acc);
-  if (blockIdx.x == 0) SC_TR(tr + 1);
-  block_reduce_pts<NP>(acc, h.np, red, res);
-  if (tid < h.np) st_sc1(partial + (size_t)blockIdx.x * NP + tid, from29(canon29(res[tid])));
-  drain_stores();
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t old = __hip_atomic_fetch_add((gu32*)&ro.st->ticket, 1u, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-    last = old + 1 == gridDim.x;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  __syncthreads();
-  if (!last) return;
-  SC_TR(tr + 2);
-  __shared__ uint32_t st_in[8];
-  if (tid < 8) st_in[tid] = ld_sc1_u32(&ro.st->state[tid]);
-  acc = R29::zero();
-  {
-    const uint32_t t = tid % NP;
-    if (t < h.np)
-      for (uint32_t b = tid / NP; b < gridDim.x; b += SC_BLOCK / NP)
-        acc = red6p(add29(acc, to29(ld_sc1(partial + (size_t)b * NP + t))));
-  }
-  block_reduce_pts<NP>(acc, h.np, red, res);
-  if (tid == 0) ro.st->ticket = 0;
-  if (loc) {
-    if (tid < NP) loc[tid] = tid < h.np ? from29(canon29(res[tid])) : Fr::zero();
-    return;
-  }
-  finish_core<NP>(sp, h.np, res, ro, j, fs, st_in, ro.st->pend, nullptr, tr, true, true);
-  if (tid < 9) ro.st->r29[tid] = fs.r.l[tid];
-  SC_TR(tr + 7);
+// Deferred absorb of round j-1's challenge bytes, on wave 1 of block 0 beside
+// the sweep (callers: tid in [64, 128)).  The new state is handed to the
+// round's last block write-through (sc1) and drained before this block's
+// ticket.
+QG_DEV void absorb_pending(ScState* st, FinSmem& fs) {
+  const uint32_t l = threadIdx.x - 64;
+  if (l < 32) fs.ab[l] = l < 20 ? st->pend[l] : 0u;
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  b3_hash_quad(fs.ab, 80, fs.chin, 8);
+  __builtin_amdgcn_wave_barrier();
+  if (l < 8) st_sc1_u32(&st->state[l], fs.chin[l]);
 }
-
-// ---------------------------------------------------------------------------
-// Throughput form of a large round for product expressions (SOP_PURE, e.g.
-// the h = g1 g2 g3 of config 3): one thread per pair (grid-stride), no LDS
-// staging and no per-step barriers.  Slot by slot the thread folds its 4
-// entries by r_{j-1} (2 throughput multiplies; the folded pair is written back
-// < 2p) and multiplies lo + t (hi - lo) into the running product of every
-// point t = 0..np-1; the points accumulate lazily.  Other expressions use the
-// LDS-staged k_sc_round.
-// ---------------------------------------------------------------------------
 
 // Barrier over the G blocks of the slice tail with its arrival counter split
 // in 8 shards (block b adds to shard b % 8, its XCD under round-robin
@@ -765,8 +637,9 @@ QG_DEV R29 limbsum29(const uint64_t* a) {
 //    other expressions (K <= 4) keep every slot's lo / hi and run the
 //    compiled monomials with uniform-index selects.  The points accumulate
 //    lazily (three additions per reduction).
-//  * Round end: per-block partial rows; the last block to publish (ticket)
-//    sums them and runs the transcript step.
+//  * Round end (big_round_end, shared with the LDS-staged k_sc_round): the
+//    block sums go into the round's limb accumulator; the last block to
+//    publish (two-level ticket) collects them and runs the transcript step.
 // ---------------------------------------------------------------------------
 // lo + t (hi - lo + 4p) for point t (d = norm29(hi - lo + 4p) < 6p)
 // the same value left lazy (limbs < 2^31 + 32, value < 20p) for NP <= 4: a
@@ -841,23 +714,8 @@ QG_DEV R29 pick29(const R29 (&v)[K], uint32_t i) {
   return r;
 }
 
-// source / destination tables of round j of k_sc_big: round 0 reads the
-// input tables; round j >= 1 folds into X (j odd, N/2 per slot) or Y (j even,
-// N/4 per slot) and reads round j - 1's output
-struct AllBufs {
-  TablePtrs in;  // src[] = input tables
-  Fr* X;
-  Fr* Y;
-  size_t capX, capY;
-  QG_DEV const Fr* src(uint32_t j, uint32_t s) const {
-    if (j <= 1) return in.src[s];
-    return (j & 1) ? Y + capY * s : X + capX * s;
-  }
-  QG_DEV Fr* dst(uint32_t j, uint32_t s) const { return (j & 1) ? X + capX * s : Y + capY * s; }
-};
-
 template <int K, int NP, bool PURE>
-QG_DEV void sweep_pairs(const AllBufs& tb, uint32_t j, bool fold, const R29& r, size_t npairs,
+QG_DEV void sweep_pairs(const RoundBufs& tb, uint32_t j, bool fold, const R29& r, size_t npairs,
                         size_t p0, size_t stride, const SopLds<NP>& sp, const SopHdr& h,
                         bool skip0, R29 (&acc)[NP]) {
   const uint32_t nslots = h.nslots, np = h.np;
@@ -979,21 +837,106 @@ QG_DEV void sweep_pairs(const AllBufs& tb, uint32_t j, bool fold, const R29& r, 
   for (int t = 0; t < NP; t++) acc[t] = red16p29<FrP>(acc[t]);
 }
 
+// Limb accumulator of a round: [shard 8][points][9 limbs] u64, shard stride ss
+// (16 x 9 in the large rounds' slots, NP x 9 in the slice tail's own).
+// Publish: the limbs of the block sums res[] (< 2p, normalized) added into the
+// block's shard (b % 8, its XCD under round-robin dispatch) by agent-scope u64
+// atomics, executed at the memory side.
+QG_DEV void acc_publish(uint64_t* ar, uint32_t ss, uint32_t np, const R29* res) {
+  const uint32_t tid = threadIdx.x;
+  if (tid < np * 9)
+    __hip_atomic_fetch_add((gu64*)(ar + (blockIdx.x & 7) * ss + tid),
+                           (uint64_t)res[tid / 9].l[tid % 9], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+// Collect (after the round's barrier or ticket): the 8 shards fetched with
+// returning atomics, one memory round trip, and the sums rebuilt: res[t] < 2p.
+// Whole block calls; res is visible after the caller's next barrier.
+QG_DEV void acc_collect(uint64_t* ar, uint32_t ss, uint32_t np, uint64_t* lsum, R29* res) {
+  const uint32_t tid = threadIdx.x;
+  if (tid < np * 9) {
+    uint64_t v[8], a = 0;
+#pragma unroll
+    for (int x = 0; x < 8; x++)
+      v[x] = __hip_atomic_fetch_add((gu64*)(ar + x * ss + tid), (uint64_t)0, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int x = 0; x < 8; x++) a += v[x];
+    lsum[tid] = a;
+  }
+  __syncthreads();
+  if (tid < np) res[tid] = limbsum29(lsum + 9 * tid);
+}
+
+// The end of a large round, from the block sums res[] on (whole block calls).
+// Publish into this round's accumulator, every wave drains, then a two-level
+// ticket: the block completing its shard (blocks b with b % 8 = x, one 128-B
+// counter line per shard) adds to the round's ticket, and the one completing
+// that is the last block.  It collects the sums, puts the counters back to
+// zero and clears the next round's accumulator (the next kernel on the stream
+// sees both), then writes this rank's local sums (sharded, loc != nullptr:
+// k_sc_finish applies the claim to the global sums) or runs the transcript
+// step and leaves r_j for the next fold.
+template <int NP>
+QG_DEV void big_round_end(const SopLds<NP>& sp, uint32_t np, const RoundOut& ro, uint32_t j,
+                          uint32_t tr, Fr* __restrict__ loc, int skip0, uint64_t* __restrict__ acc_j,
+                          uint64_t* __restrict__ acc_next, uint32_t* __restrict__ bar8, R29* res,
+                          FinSmem& fs) {
+  __shared__ uint32_t last;
+  __shared__ uint64_t lsum[NP * 9];
+  __shared__ uint32_t st_in[8];
+  const uint32_t tid = threadIdx.x;
+  acc_publish(acc_j, 16 * 9, np, res);
+  drain_stores();
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t x = blockIdx.x & 7, nx = (gridDim.x + 7 - x) / 8;
+    bool done = false;
+    const uint32_t o1 = __hip_atomic_fetch_add((gu32*)(bar8 + 32 * x), 1u, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+    if (o1 + 1 == nx) {
+      const uint32_t o2 = __hip_atomic_fetch_add((gu32*)&ro.st->ticket, 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT);
+      done = o2 + 1 == (gridDim.x < 8 ? gridDim.x : 8u);
+    }
+    last = done;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: loads stay below
+  }
+  __syncthreads();
+  if (!last) return;
+  SC_TR(tr + 2);
+  if (tid < 8) st_in[tid] = ld_sc1_u32(&ro.st->state[tid]);
+  acc_collect(acc_j, 16 * 9, np, lsum, res);
+  if (tid < 8) st_sc1_u32(bar8 + 32 * tid, 0u);
+  for (uint32_t i = tid; i < 8 * 16 * 9; i += SC_BLOCK)
+    __hip_atomic_store((gu64*)(acc_next + i), (uint64_t)0, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  SC_TR(tr + 8);
+  if (tid == 0) ro.st->ticket = 0;
+  if (loc) {
+    if (tid < NP) loc[tid] = tid < np ? from29(canon29(res[tid])) : Fr::zero();
+    return;
+  }
+  if (skip0 && tid == 0)  // h(0) = claim - h(1)
+    res[0] = red6p(sub29(to29(ld_sc1(reinterpret_cast<const Fr*>(ro.st->claim))), res[1]));
+  __syncthreads();
+  finish_core<NP>(sp, np, res, ro, j, fs, st_in, ro.st->pend, nullptr, tr);
+  if (tid < 9) ro.st->r29[tid] = fs.r.l[tid];
+  SC_TR(tr + 7);
+}
+
 // One large round (tables > 2^PERS_LOG) in one launch: thread-per-pair sweep
-// (sweep_pairs), per-block partial rows, and the last block to publish
-// (ticket election) sums the rows and runs the transcript step (or, sharded,
-// writes this rank's local sums).
+// (sweep_pairs), then the shared round end.
 template <int K, int NP, bool PURE, int WPE = 1>
 __global__ void __launch_bounds__(SC_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE)))
-    k_sc_big(AllBufs tb, uint32_t j, const SopDev* __restrict__ spg, SopHdr h, size_t npairs,
+    k_sc_big(RoundBufs tb, uint32_t j, const SopDev* __restrict__ spg, SopHdr h, size_t npairs,
              RoundOut ro, int pending, Fr* __restrict__ loc, int skip0, uint64_t* __restrict__ acc_j,
              uint64_t* __restrict__ acc_next, uint32_t* __restrict__ bar8) {
   __shared__ SopLds<NP> sp;
   __shared__ R29 red[(SC_BLOCK / 64) * NP];
   __shared__ R29 res[NP];
   __shared__ FinSmem fs;
-  __shared__ uint32_t last;
-  __shared__ uint64_t lsum[NP * 9];
   const uint32_t tid = threadIdx.x;
   const uint32_t tr = 1024 + 16 * j;
   const bool fold = j > 0;
@@ -1001,21 +944,8 @@ __global__ void __launch_bounds__(SC_BLOCK) __attribute__((amdgpu_waves_per_eu(W
   SC_TB(j, 0);
   sop_load<NP>(sp, spg, h, loc == nullptr);
   R29 r = R29::zero();
-  if (fold) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = ro.st->r29[i];
-  }
-  if (pending && blockIdx.x == 0 && tid >= 64 && tid < 128) {
-    // deferred absorb of round j-1's challenge bytes (wave 1 of block 0); the
-    // new state is handed to the last block write-through (sc1) and drained
-    // before this block's ticket
-    if (tid - 64 < 32) fs.ab[tid - 64] = tid - 64 < 20 ? ro.st->pend[tid - 64] : 0u;
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    b3_hash_quad(fs.ab, 80, fs.chin, 8);
-    __builtin_amdgcn_wave_barrier();
-    if (tid - 64 < 8) st_sc1_u32(&ro.st->state[tid - 64], fs.chin[tid - 64]);
-  }
+  if (fold) r = load_r29(ro.st);
+  if (pending && blockIdx.x == 0 && tid >= 64 && tid < 128) absorb_pending(ro.st, fs);
   if (skip0 && blockIdx.x == 0 && tid == 128) {
     // this round's claim h_{j-1}(r_{j-1}) at scale S, for the finisher's
     // h(0) = claim - h(1): Horner over round j-1's canonical coefficients
@@ -1039,66 +969,47 @@ __global__ void __launch_bounds__(SC_BLOCK) __attribute__((amdgpu_waves_per_eu(W
   SC_TB(j, 1);
   SC_TW(j);
   block_sums29<NP>(acc, np, red, res);
-  // publish: the limbs of the block sums added into this round's accumulator
-  // shard (agent-scope u64 atomics, executed at the memory side), every wave
-  // drains, then a two-level ticket: the block completing its shard (blocks b
-  // with b % 8 = x, one 128-B counter line per shard) adds to the round's
-  // ticket, and the one completing that is the last block
-  if (tid < np * 9)
-    __hip_atomic_fetch_add((gu64*)(acc_j + (blockIdx.x & 7) * (16 * 9) + tid),
-                           (uint64_t)res[tid / 9].l[tid % 9], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-  drain_stores();
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t x = blockIdx.x & 7, nx = (gridDim.x + 7 - x) / 8;
-    bool done = false;
-    const uint32_t o1 = __hip_atomic_fetch_add((gu32*)(bar8 + 32 * x), 1u, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT);
-    if (o1 + 1 == nx) {
-      const uint32_t o2 = __hip_atomic_fetch_add((gu32*)&ro.st->ticket, 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-      done = o2 + 1 == (gridDim.x < 8 ? gridDim.x : 8u);
+  big_round_end<NP>(sp, np, ro, j, tr, loc, skip0, acc_j, acc_next, bar8, res, fs);
+}
+
+// The LDS-staged form of a large round, for every expression k_sc_big does not
+// take: fused fold(r_{j-1}) + evaluation at t = 0..np-1 by (pair, point)
+// threads (round_sweep), then the shared round end.  Every point is evaluated
+// (no skip-0).  Same parameter list as k_sc_big: launch_big picks a pointer.
+template <int K, int NP>
+__global__ void __launch_bounds__(SC_BLOCK)
+    k_sc_round(RoundBufs tb, uint32_t j, const SopDev* __restrict__ spg, SopHdr h, size_t npairs,
+               RoundOut ro, int pending, Fr* __restrict__ loc, int /*skip0: never*/,
+               uint64_t* __restrict__ acc_j, uint64_t* __restrict__ acc_next,
+               uint32_t* __restrict__ bar8) {
+  __shared__ SopLds<NP> sp;
+  __shared__ RoundLds<K, NP, SC_BLOCK> L;
+  __shared__ R29 red[(SC_BLOCK / 64) * NP];
+  __shared__ R29 res[NP];
+  __shared__ FinSmem fs;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t tr = 1024 + 16 * j;
+  const bool fold = j > 0;
+  if (blockIdx.x == 0) SC_TR(tr + 0);
+  sop_load<NP>(sp, spg, h, loc == nullptr);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    if (tid == (uint32_t)i) {
+      L.src[i] = tb.src(j, i);
+      L.dst[i] = tb.dst(j, i);
     }
-    last = done;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: loads stay below
   }
+  R29 r = R29::zero();
+  if (fold) r = load_r29(ro.st);
+  if (pending && blockIdx.x == 0 && tid >= 64 && tid < 128) absorb_pending(ro.st, fs);
   __syncthreads();
-  if (!last) return;
-  SC_TR(tr + 2);
-  __shared__ uint32_t st_in[8];
-  if (tid < 8) st_in[tid] = ld_sc1_u32(&ro.st->state[tid]);
-  if (tid < np * 9) {
-    uint64_t v[8], a = 0;
-#pragma unroll
-    for (int x = 0; x < 8; x++)
-      v[x] = __hip_atomic_fetch_add((gu64*)(acc_j + x * (16 * 9) + tid), (uint64_t)0,
-                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int x = 0; x < 8; x++) a += v[x];
-    lsum[tid] = a;
-  }
-  __syncthreads();
-  if (tid < np) res[tid] = limbsum29(lsum + 9 * tid);
-  // counters back to zero and the next round's accumulator cleared (the next
-  // kernel on the stream sees both)
-  if (tid < 8) st_sc1_u32(bar8 + 32 * tid, 0u);
-  for (uint32_t i = tid; i < 8 * 16 * 9; i += SC_BLOCK)
-    __hip_atomic_store((gu64*)(acc_next + i), (uint64_t)0, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  SC_TR(tr + 8);
-  if (tid == 0) ro.st->ticket = 0;
-  if (loc) {  // sharded: k_sc_finish applies the claim to the global sums
-    if (tid < NP) loc[tid] = tid < np ? from29(canon29(res[tid])) : Fr::zero();
-    return;
-  }
-  if (skip0 && tid == 0)
-    res[0] = red6p(sub29(to29(ld_sc1(reinterpret_cast<const Fr*>(ro.st->claim))), res[1]));
-  __syncthreads();
-  finish_core<NP>(sp, np, res, ro, j, fs, st_in, ro.st->pend, nullptr, tr, true, true);
-  if (tid < 9) ro.st->r29[tid] = fs.r.l[tid];
-  SC_TR(tr + 7);
+  constexpr uint32_t PB = SC_BLOCK / NP;
+  R29 acc = R29::zero();
+  round_sweep<K, NP, SC_BLOCK>(L, sp, h, npairs, fold, r, (size_t)blockIdx.x * PB,
+                               (size_t)gridDim.x * PB, acc);
+  if (blockIdx.x == 0) SC_TR(tr + 1);
+  block_reduce_pts<NP>(acc, h.np, red, res);
+  big_round_end<NP>(sp, h.np, ro, j, tr, loc, 0, acc_j, acc_next, bar8, res, fs);
 }
 
 // sharded: the transcript step over the allgathered [rank][NP] local sums
@@ -1126,7 +1037,7 @@ __global__ void __launch_bounds__(SC_BLOCK)
   if (skip0 && tid == 0)  // h(0) = claim - h(1) on the global sums
     res[0] = red6p(sub29(to29(*reinterpret_cast<const Fr*>(ro.st->claim)), res[1]));
   __syncthreads();
-  finish_core<NP>(sp, h.np, res, ro, j, fs, st, nullptr, ro.st->state, 4096, true, true);
+  finish_core<NP>(sp, h.np, res, ro, j, fs, st, nullptr, ro.st->state);
   if (tid < 9) ro.st->r29[tid] = fs.r.l[tid];
 }
 
@@ -1172,17 +1083,6 @@ QG_DEV void grid_barrier(uint32_t* ctr, uint32_t n, uint32_t* err) {
 // the small rounds, beside the sweep.  Final fold + claim by block 0.
 // PB is chosen at run time from the slot count (tail_pb, shared with the
 // host's grid computation) so the two staging arrays fit TAIL_FBYTES.
-static constexpr int TAIL_BLOCK = 256;
-static constexpr uint32_t TAIL_FBYTES = 32 * 1024;  // LDS for the staging arrays
-// np: the kernel's point stride NP (threads per pair), not the expression's np
-QG_HD uint32_t tail_pb(uint32_t nslots, uint32_t np) {
-  // F0: nslots x 2 PB entries, F1: nslots x PB entries, 36 B each
-  const uint32_t per = nslots ? nslots * 108u : 108u;
-  uint32_t pb = 1;
-  while (pb * 2 * per <= TAIL_FBYTES && pb * 2 * np <= (uint32_t)TAIL_BLOCK) pb *= 2;
-  return pb;
-}
-
 // Per-point sums when only the first `n` threads (n <= 64: wave 0) hold
 // values: a shuffle tree of exactly log2(n / NP) steps inside wave 0, no LDS
 // staging; else the block reduction.  res[t] (LDS, < 2p) on return.
@@ -1201,46 +1101,51 @@ QG_DEV void tail_reduce(R29 acc, uint32_t n, uint32_t np, R29* red, R29* res) {
   __syncthreads();
 }
 
+// What both tails start with: the program, the transcript state and the
+// deferred absorb of round j0 - 1 into LDS; returns the fold multiplier of
+// round j0 (r_{j0-1}; none in round 0).  The caller's barrier follows.
 template <int NP>
-QG_DEV void tail_eval(const R29* F, uint32_t ss, const SopLds<NP>& sp, const SopHdr& h,
-                      uint32_t pl, uint32_t t, R29& acc) {
-  R29 sum = R29::zero();
-  uint32_t f = 0;
-  for (uint32_t m = 0; m < h.nmono; m++) {
-    const uint32_t len = sp.mono_len(m);
-    R29 prod;
-    if (len == 0) {
-      prod = sp.c29[m];
-    } else {
-      for (uint32_t q = 0; q < len; q++) {
-        const uint32_t s = sp.fac(f + q);
-        const R29 lo = F[s * ss + 2 * pl], hi = F[s * ss + 2 * pl + 1];
-        R29 v;
-        if constexpr (NP <= 4) {
-          const R29 d = norm29(sub29(hi, lo));
-          R29 a = lo;
-          if (t & 1u) a = add29(a, d);
-          if (t & 2u) a = add29(a, add29(d, d));
-          v = q == 0 ? norm29(a) : a;  // later factors stay lazy (see at_point_lazy)
-        } else {
-          v = norm29(add29(lo, mul29(sub29(hi, lo), sp.t29[t])));
-        }
-        prod = q == 0 ? v : mul29(prod, v);
+QG_DEV R29 tail_prologue(SopLds<NP>& sp, const SopDev* __restrict__ spg, const SopHdr& h,
+                         const ScState* st, uint32_t j0, int pending0, uint32_t* state,
+                         uint32_t* pend) {
+  const uint32_t tid = threadIdx.x;
+  sop_load<NP>(sp, spg, h, true);
+  if (tid < 8) state[tid] = st->state[tid];
+  if (tid < 32) pend[tid] = (pending0 && tid < 20) ? st->pend[tid] : 0u;
+  return j0 ? load_r29(st) : R29::zero();
+}
+
+// What both tails end with (block 0): the final fold with r_{n-1} on the
+// 32-bit path over the last round's two entries per slot (F[i * ss], F[i * ss
+// + 1]), the claim h(final values), and the absorb of the last challenge.
+template <int K>
+QG_DEV void tail_final(const R29* F, uint32_t ss, const SopDev* __restrict__ spg, const SopHdr& h,
+                       const FinSmem& fs, const uint32_t* pend, int pending, ScState* st,
+                       Fr* __restrict__ final_vals, Fr* __restrict__ evaluation) {
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) {
+    const Fr rr = fs.r256;
+    Fr val[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+      if ((uint32_t)i < h.nslots) {
+        const Fr a = lt_p(from29(F[i * ss])), b = lt_p(from29(F[i * ss + 1]));
+        val[i] = a + rr * (b - a);
+        final_vals[i] = val[i];
+      } else {
+        val[i] = Fr::zero();
       }
-      if (!sp.skip(m) || len == 1) prod = mul29(prod, sp.c29[m]);
     }
-    f += len;
-    sum = red6p(add29(sum, prod));
+    *evaluation = sop_eval_final<K>(spg, h.nmono, val);
   }
-  acc = red6p(add29(acc, sum));
+  if (pending && tid < 64) b3_hash_quad(pend, 80, st->state, 8);
 }
 
 template <int K, int NP>
 __global__ void __launch_bounds__(TAIL_BLOCK)
-    k_sc_tail(TablePtrs tp0, TablePtrs bufA, TablePtrs bufB, const SopDev* __restrict__ spg,
-              SopHdr h, uint32_t nvars, uint32_t j0, int fold0, int pending0, RoundOut ro,
-              Fr* __restrict__ partial, uint32_t* __restrict__ bar, Fr* __restrict__ final_vals,
-              Fr* __restrict__ evaluation) {
+    k_sc_tail(RoundBufs tb, const SopDev* __restrict__ spg, SopHdr h, uint32_t nvars, uint32_t j0,
+              int pending0, RoundOut ro, Fr* __restrict__ partial, uint32_t* __restrict__ bar,
+              Fr* __restrict__ final_vals, Fr* __restrict__ evaluation) {
   __shared__ SopLds<NP> sp;
   __shared__ R29 Fbuf[TAIL_FBYTES / sizeof(R29)];
   __shared__ R29 red[(TAIL_BLOCK / 64) * NP];
@@ -1248,6 +1153,8 @@ __global__ void __launch_bounds__(TAIL_BLOCK)
   __shared__ FinSmem fs;
   __shared__ uint32_t st[8];
   __shared__ uint32_t pend[32];
+  __shared__ const Fr* src[8];  // the HBM tables the current round reads and writes
+  __shared__ Fr* dst[8];
   const uint32_t tid = threadIdx.x, blk = blockIdx.x;
   const uint32_t nslots = h.nslots, np = h.np;
   const uint32_t PB = tail_pb(nslots, NP);  // (pair, point) threads: NP per pair
@@ -1257,18 +1164,19 @@ __global__ void __launch_bounds__(TAIL_BLOCK)
   // F0 (slot stride 2 PB) and F1 (slot stride PB)
   R29* const F0 = Fbuf;
   R29* const F1 = Fbuf + (size_t)(nslots ? nslots : 1) * 2 * PB;
-  sop_load<NP>(sp, spg, h, true);
-  if (tid < 8) st[tid] = ro.st->state[tid];
-  if (tid < 32) pend[tid] = (pending0 && tid < 20) ? ro.st->pend[tid] : 0u;
-  R29 r = R29::zero();
-  if (fold0) {
+  R29 r = tail_prologue<NP>(sp, spg, h, ro.st, j0, pending0, st, pend);
+  auto round_tables = [&](uint32_t j) {
 #pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = ro.st->r29[i];
-  }
+    for (int i = 0; i < 8; i++)
+      if (tid == (uint32_t)i) {
+        src[i] = tb.src(j, i);
+        dst[i] = tb.dst(j, i);
+      }
+  };
+  round_tables(j0);
   __syncthreads();
-  TablePtrs cur = tp0;
-  int fold = fold0, pending = pending0;
-  // where this round's source lives: HBM (cur.src) or LDS (prev, slot stride ss_prev)
+  int pending = pending0;
+  // where this round's source lives: HBM (src) or LDS (prev, slot stride ss_prev)
   const R29* prev = nullptr;
   uint32_t ss_prev = 0;
   R29* wr = F0;
@@ -1280,7 +1188,7 @@ __global__ void __launch_bounds__(TAIL_BLOCK)
     const bool single = nb == 1 && npairs <= PB;
     if (writer) SC_TR(16 * j + 0);
     if (pending && last_wave) b3_hash_quad(pend, 80, st, 8);  // beside the sweep
-    // ---- phase F: fold (or copy) this round's table into the staging array
+    // ---- phase F: fold (or, in round 0, copy) this round's table into the staging array
     R29 acc = R29::zero();
     const size_t stride = (size_t)nb * PB;
     for (size_t base = (size_t)blk * PB; base < npairs; base += stride) {
@@ -1291,21 +1199,19 @@ __global__ void __launch_bounds__(TAIL_BLOCK)
         const size_t idx = 2 * base + e;  // entry of this round's (folded) table
         R29 v;
         if (prev) {  // LDS-resident source: entries 2e, 2e+1 of the previous table
-          const R29 x0 = prev[s * ss_prev + 2 * e], x1 = prev[s * ss_prev + 2 * e + 1];
-          v = red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
-        } else if (fold) {
-          const Fr* src = cur.src[s] + 2 * idx;
-          const R29 x0 = to29(ld_sc1(src)), x1 = to29(ld_sc1(src + 1));
-          v = red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
-          if (!single) st_sc1(cur.dst[s] + idx, from29(v));
+          v = fold29(prev[s * ss_prev + 2 * e], prev[s * ss_prev + 2 * e + 1], r);
+        } else if (j > 0) {
+          const Fr* x = src[s] + 2 * idx;
+          v = fold29(to29(ld_sc1(x)), to29(ld_sc1(x + 1)), r);
+          if (!single) st_sc1(dst[s] + idx, from29(v));
         } else {
-          v = to29(ld_sc1(cur.src[s] + idx));
+          v = to29(ld_sc1(src[s] + idx));
         }
         wr[s * ss_wr + e] = v;
       }
       __syncthreads();
       // ---- phase E: thread (pair pl, point t)
-      if (t < np && pl < cnt) tail_eval<NP>(wr, ss_wr, sp, h, pl, t, acc);
+      if (t < np && pl < cnt) eval_pair_point<NP>(wr, ss_wr, sp, h, pl, t, acc);
       if (base + stride < npairs) __syncthreads();  // the staging array is refilled
     }
     if (writer) SC_TR(16 * j + 1);
@@ -1339,49 +1245,24 @@ __global__ void __launch_bounds__(TAIL_BLOCK)
       tail_reduce<NP>(acc, std::min<uint32_t>(nb, TAIL_BLOCK / NP) * NP, np, red, res);
     }
     if (writer) SC_TR(16 * j + 2);
-    finish_core<NP>(sp, np, res, ro, j, fs, st, pend, nullptr, writer ? 16 * j : 4096, writer,
-                    true);
+    finish_core<NP>(sp, np, res, ro, j, fs, st, pend, nullptr, writer ? 16 * j : 4096, writer);
+    // next round's source: the staging array just written when this round was a
+    // single block step, else the HBM tables this round folded into
+    if (!single) round_tables(j + 1);
     __syncthreads();
     r = fs.r;
     pending = 1;
-    // next round's source: the staging array just written when this round was a
-    // single block step, else the HBM tables this round folded into
     if (single) {
       prev = wr;
       ss_prev = ss_wr;
       const bool w0 = wr == F0;
       wr = w0 ? F1 : F0;
       ss_wr = w0 ? PB : 2 * PB;
-    } else {
-      TablePtrs nxt;
-      const TablePtrs& w = ((j - j0) & 1) ? bufB : bufA;
-      for (int i = 0; i < 8; i++) {
-        nxt.src[i] = fold ? cur.dst[i] : cur.src[i];
-        nxt.dst[i] = w.dst[i];
-      }
-      cur = nxt;
     }
-    fold = 1;
   }
-  // final fold with r_{n-1} on the 32-bit path: the last round (one pair) is
-  // always a single block step, so its two folded entries per slot are in prev
-  if (tid == 0) {
-    const Fr rr = fs.r256;
-    Fr val[K];
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-      if ((uint32_t)i < nslots) {
-        const Fr a = lt_p(from29(prev[i * ss_prev])), b = lt_p(from29(prev[i * ss_prev + 1]));
-        val[i] = a + rr * (b - a);
-        final_vals[i] = val[i];
-      } else {
-        val[i] = Fr::zero();
-      }
-    }
-    *evaluation = sop_eval_final<K>(spg, h.nmono, val);
-  }
-  // absorb the last challenge bytes
-  if (pending && tid < 64) b3_hash_quad(pend, 80, ro.st->state, 8);
+  // the last round (one pair) is always a single block step: its two folded
+  // entries per slot are in prev
+  tail_final<K>(prev, ss_prev, spg, h, fs, pend, pending, ro.st, final_vals, evaluation);
 }
 
 // ---------------------------------------------------------------------------
@@ -1391,25 +1272,23 @@ __global__ void __launch_bounds__(TAIL_BLOCK)
 // j0) / G per slot).  The fold pairs adjacent entries, so block b's slice of
 // round j+1 is the fold of its own slice of round j: after the one HBM load
 // of the first round the tables never leave the block's LDS, and nothing but
-// the per-round sums crosses blocks (partial rows + grid barrier, then every
-// block runs the identical transcript step).  When a slice is down to one
-// pair, each block folds it to one entry per slot, writes it to HBM, and
-// after one more barrier block 0 gathers the G entries and finishes the last
-// log2(G) rounds alone (the table again in LDS).  The deferred absorb of the
-// previous challenge runs on the last wave beside the other waves' evaluation.
+// the per-round sums crosses blocks (limb accumulators + grid barrier, then
+// every block runs the identical transcript step).  When a slice is down to a
+// few pairs, each block publishes it to HBM (gat: 2^(nvars - j0) entries per
+// slot), and after the barrier fewer blocks regroup the slices, until block 0
+// finishes the last rounds alone (the table again in LDS).  The deferred
+// absorb of the previous challenge runs on the last wave beside the other
+// waves' evaluation.
 // ---------------------------------------------------------------------------
 #ifndef QG_SL_BLOCK
 #define QG_SL_BLOCK 256
 #endif
 static constexpr int SL_BLOCK = QG_SL_BLOCK;
-// entries per slot of a block's slice in the first tail round (LDS: K slots x
-// 1.5 x SL_SMAX entries of 36 B: the slice and its half-size fold)
-QG_HD constexpr uint32_t sl_smax(int K) { return K <= 4 ? 256u : 128u; }
 
 template <int K, int NP>
 __global__ void __launch_bounds__(SL_BLOCK)
-    k_sc_slice(TablePtrs tp0, TablePtrs gat, const SopDev* __restrict__ spg, SopHdr h,
-               uint32_t nvars, uint32_t j0, int fold0, int pending0, RoundOut ro,
+    k_sc_slice(RoundBufs tb, Fr* __restrict__ gat, const SopDev* __restrict__ spg, SopHdr h,
+               uint32_t nvars, uint32_t j0, int pending0, RoundOut ro,
                uint64_t* __restrict__ acc_j0, uint32_t* __restrict__ bar8,
                uint64_t* __restrict__ acc64, Fr* __restrict__ final_vals,
                Fr* __restrict__ evaluation) {
@@ -1437,27 +1316,19 @@ __global__ void __launch_bounds__(SL_BLOCK)
   uint32_t arrived = 0;                          // cumulative barrier arrivals
   uint32_t G = gridDim.x;                        // blocks holding a slice this round
   uint32_t S = (1u << (nvars - j0)) / G;         // entries per slot of this block's slice
-  sop_load<NP>(sp, spg, h, true);
-  if (tid < 8) st[tid] = ro.st->state[tid];
-  if (tid < 32) pend[tid] = (pending0 && tid < 20) ? ro.st->pend[tid] : 0u;
-  R29 r = R29::zero();
-  if (fold0) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = ro.st->r29[i];
-  }
-  R29* cur = Fbuf;                // slot stride S
+  R29 r = tail_prologue<NP>(sp, spg, h, ro.st, j0, pending0, st, pend);
+  R29* cur = Fbuf;               // slot stride S
   R29* nxt = Fbuf + K * SMAX;     // slot stride S / 2
   // the block's slice of the round-j0 table (folded from the source by r_{j0-1})
   for (uint32_t it = tid; it < nslots * S; it += SL_BLOCK) {
     const uint32_t s = it / S, e = it % S;
     const size_t idx = (size_t)blk * S + e;
     R29 v;
-    if (fold0) {
-      const Fr* src = tp0.src[s] + 2 * idx;
-      const R29 x0 = to29(src[0]), x1 = to29(src[1]);
-      v = red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
+    if (j0 > 0) {
+      const Fr* src = tb.src(j0, s) + 2 * idx;
+      v = fold29(to29(src[0]), to29(src[1]), r);
     } else {
-      v = to29(tp0.src[s][idx]);
+      v = to29(tb.src(0, s)[idx]);
     }
     cur[s * S + e] = v;
   }
@@ -1472,7 +1343,7 @@ __global__ void __launch_bounds__(SL_BLOCK)
     if (regroup)
       for (uint32_t it = tid; it < nslots * S; it += SL_BLOCK) {
         const uint32_t s = it / S, e = it % S;
-        st_sc1(gat.dst[s] + (size_t)blk * S + e, from29(cur[s * S + e]));
+        st_sc1(gat + ((size_t)s << (nvars - j0)) + (size_t)blk * S + e, from29(cur[s * S + e]));
       }
     const uint32_t ne = pending ? SL_BLOCK - 64 : SL_BLOCK;
     if (pending && last_wave) b3_hash_quad(pend, 80, st, 8);
@@ -1480,42 +1351,25 @@ __global__ void __launch_bounds__(SL_BLOCK)
     const uint32_t items = (S / 2) * NP;
     if (tid < ne)
       for (uint32_t it = tid; it < items; it += ne)
-        if (t < np) tail_eval<NP>(cur, S, sp, h, it / NP, t, acc);
+        if (t < np) eval_pair_point<NP>(cur, S, sp, h, it / NP, t, acc);
     if (blk == 0) SC_TR(16 * j + 1);
     tail_reduce<NP>(acc, std::min(items, ne), np, red, res);
     if (blk == 0) SC_TR(16 * j + 7);
     if (G > 1) {
-      // limbs of the block sums added into this round's accumulator shard
-      // (agent-scope u64 atomics at the memory side), one sharded barrier, then
-      // every block fetches the 8 shards with returning atomics and rebuilds
-      // the sums: no partial rows, one memory round trip.  Round j0 uses the
-      // big rounds' cleared slot (shard stride 16 x 9), later rounds acc64.
+      // the block sums through this round's limb accumulator and one sharded
+      // barrier: no partial rows, one memory round trip.  Round j0 uses the
+      // large rounds' cleared slot (shard stride 16 x 9), later rounds acc64.
       uint64_t* ar = j == j0 ? acc_j0 : acc64 + (size_t)(j - j0 - 1) * ACC_R;
       const uint32_t ss = j == j0 ? 16 * 9 : NP * 9;
-      if (tid < np * 9)
-        __hip_atomic_fetch_add((gu64*)(ar + (blk & 7) * ss + tid),
-                               (uint64_t)res[tid / 9].l[tid % 9], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+      acc_publish(ar, ss, np, res);
       arrived += G;
       grid_barrier8(bar8, arrived, &ro.st->err);
       if (blk == 0) SC_TR(16 * j + 8);
-      if (tid < np * 9) {
-        uint64_t v[8], a = 0;
-#pragma unroll
-        for (int x = 0; x < 8; x++)
-          v[x] = __hip_atomic_fetch_add((gu64*)(ar + x * ss + tid), (uint64_t)0,
-                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int x = 0; x < 8; x++) a += v[x];
-        lsum[tid] = a;
-      }
-      __syncthreads();
-      if (tid < np) res[tid] = limbsum29(lsum + 9 * tid);
+      acc_collect(ar, ss, np, lsum, res);
       __syncthreads();
     }
     if (blk == 0) SC_TR(16 * j + 2);
-    finish_core<NP>(sp, np, res, ro, j, fs, st, pend, nullptr, blk == 0 ? 16 * j : 4096, blk == 0,
-                    true);
+    finish_core<NP>(sp, np, res, ro, j, fs, st, pend, nullptr, blk == 0 ? 16 * j : 4096, blk == 0);
     __syncthreads();
     r = fs.r;
     pending = 1;
@@ -1523,16 +1377,15 @@ __global__ void __launch_bounds__(SL_BLOCK)
     if (regroup) {
       // f blocks' round-j slices (published before the barrier) become one
       // block's round-(j+1) slice, folded on the load; the other blocks retire.
-      // Fewer blocks: a cheaper barrier and fewer partial rows per round.
+      // Fewer blocks: a cheaper barrier and fewer sums per round.
       const uint32_t f = std::min<uint32_t>(G, 2 * SMAX / S);
       const uint32_t G2 = G / f;
       if (blk >= G2) return;
       const uint32_t S2 = f * S / 2;
       for (uint32_t it = tid; it < nslots * S2; it += SL_BLOCK) {
         const uint32_t s = it / S2, e = it % S2;
-        const Fr* src = gat.dst[s] + (size_t)blk * f * S + 2 * e;
-        const R29 x0 = to29(ld_sc1(src)), x1 = to29(ld_sc1(src + 1));
-        Fbuf[s * S2 + e] = red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
+        const Fr* src = gat + ((size_t)s << (nvars - j0)) + (size_t)blk * f * S + 2 * e;
+        Fbuf[s * S2 + e] = fold29(to29(ld_sc1(src)), to29(ld_sc1(src + 1)), r);
       }
       S = S2;
       G = G2;
@@ -1543,8 +1396,7 @@ __global__ void __launch_bounds__(SL_BLOCK)
       const uint32_t h2 = S / 2;
       for (uint32_t it = tid; it < nslots * h2; it += SL_BLOCK) {
         const uint32_t s = it / h2, e = it % h2;
-        const R29 x0 = cur[s * S + 2 * e], x1 = cur[s * S + 2 * e + 1];
-        nxt[s * h2 + e] = red2p29<FrP>(add29(x0, mul29(sub29(x1, x0), r)));
+        nxt[s * h2 + e] = fold29(cur[s * S + 2 * e], cur[s * S + 2 * e + 1], r);
       }
       S = h2;
     }
@@ -1553,24 +1405,8 @@ __global__ void __launch_bounds__(SL_BLOCK)
     nxt = tmp;
     __syncthreads();
   }
-  // final fold with r_{n-1} on the 32-bit path: one pair per slot left in cur (block 0)
-  if (tid == 0) {
-    const Fr rr = fs.r256;
-    Fr val[K];
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-      if ((uint32_t)i < nslots) {
-        const Fr a = lt_p(from29(cur[i * 2])), b = lt_p(from29(cur[i * 2 + 1]));
-        val[i] = a + rr * (b - a);
-        final_vals[i] = val[i];
-      } else {
-        val[i] = Fr::zero();
-      }
-    }
-    *evaluation = sop_eval_final<K>(spg, h.nmono, val);
-  }
-  // absorb the last challenge bytes
-  if (pending && tid < 64) b3_hash_quad(pend, 80, ro.st->state, 8);
+  // one pair per slot left in cur (block 0)
+  tail_final<K>(cur, 2, spg, h, fs, pend, pending, ro.st, final_vals, evaluation);
 }
 
 // ---------------------------------------------------------------------------
@@ -1670,9 +1506,7 @@ __global__ void k_gen_fold(const Fr* const* __restrict__ src, Fr* const* __restr
   if (i >= nq * nslots) return;
   const uint32_t s = (uint32_t)(i / nq);
   const size_t q = i % nq;
-  R29 r;
-#pragma unroll
-  for (int k = 0; k < 9; k++) r.l[k] = st->r29[k];
+  const R29 r = load_r29(st);
   const R29 x0 = to29(src[s][2 * q]), x1 = to29(src[s][2 * q + 1]);
   dst[s][q] = from29(red6p(add29(x0, mul29(sub29(x1, x0), r))));
 }
@@ -1745,31 +1579,29 @@ static L9 l9_of(const Fr& x) {
   return r;
 }
 
-// inverse Vandermonde on nodes 0..np-1: coefficient t of sum_u L_u(X) ev[u] is
-// sum_u V[t][u] ev[u]; out_m[t*16+u] = V (Montgomery), out_c = V (plain)
-static void build_vinv(uint32_t np, Fr* out_m, Fr* out_c) {
-  for (uint32_t i = 0; i < 16 * 16; i++) out_m[i] = out_c[i] = Fr::zero();
+// inverse Vandermonde on nodes 0..np-1 (the compiled and the generic path):
+// V[t * np + u] (Montgomery) with coefficient t of the interpolant =
+// sum_u V[t][u] ev[u]
+static std::vector<Fr> build_vinv(uint32_t np) {
+  std::vector<Fr> V((size_t)np * np, Fr::zero());
   for (uint32_t j = 0; j < np; j++) {
     std::vector<Fr> poly(1, Fr::one());
     Fr den = Fr::one();
     for (uint32_t m = 0; m < np; m++) {
       if (m == j) continue;
       std::vector<Fr> np2(poly.size() + 1, Fr::zero());
-      Fr negm = fneg(from_u64<FrP>(m));
+      const Fr negm = fneg(from_u64<FrP>(m));
       for (size_t k = 0; k < poly.size(); k++) {
         np2[k] = np2[k] + poly[k] * negm;
         np2[k + 1] = np2[k + 1] + poly[k];
       }
       poly = np2;
-      Fr diff = (j >= m) ? from_u64<FrP>(j - m) : fneg(from_u64<FrP>(m - j));
-      den = den * diff;
+      den = den * ((j >= m) ? from_u64<FrP>(j - m) : fneg(from_u64<FrP>(m - j)));
     }
-    Fr dinv = finv(den);
-    for (uint32_t i = 0; i < np; i++) {
-      out_m[i * 16 + j] = poly[i] * dinv;
-      out_c[i * 16 + j] = from_mont(out_m[i * 16 + j]);
-    }
+    const Fr dinv = finv(den);
+    for (uint32_t i = 0; i < np; i++) V[(size_t)i * np + j] = poly[i] * dinv;
   }
+  return V;
 }
 
 // Compiled programs are cached by their exact bytes (the device image carries
@@ -1829,13 +1661,13 @@ static std::shared_ptr<const ScProgram> get_program(const qg_expr_op* prog, size
   }
   for (size_t f = 0; f < sp.fac.size(); f++) d.fac[f] = (uint8_t)sp.fac[f];
   {
-    Fr vm[16 * 16], vc[16 * 16];
-    build_vinv(np, vm, vc);  // vc: plain inverse-Vandermonde entries
-    const Fr sm = pow2_mod_plain<FrP>((uint32_t)(261 + e)), sc = pow2_mod_plain<FrP>((uint32_t)(5 + e));
-    for (uint32_t i = 0; i < 16 * 16; i++) {
-      d.vm29[i] = l9_of(plain_mul(vc[i], sm));
-      d.vc29[i] = l9_of(plain_mul(vc[i], sc));
-    }
+    // the plain inverse-Vandermonde entries x 2^(5 + e): sums at scale S ->
+    // canonical coefficients (rows of 16; the memset left the rest zero)
+    const std::vector<Fr> V = build_vinv(np);
+    const Fr sc = pow2_mod_plain<FrP>((uint32_t)(5 + e));
+    for (uint32_t t = 0; t < np; t++)
+      for (uint32_t u = 0; u < np; u++)
+        d.vc29[t * 16 + u] = l9_of(plain_mul(from_mont(V[(size_t)t * np + u]), sc));
   }
   for (uint32_t t = 0; t < 16; t++)
     d.t29[t] = l9_of(plain_mul(from_u64_plain(t), pow2_mod_plain<FrP>(261)));
@@ -1857,12 +1689,11 @@ static std::shared_ptr<const ScProgram> get_program(const qg_expr_op* prog, size
 }
 
 
-// Co-residency guard of a grid-barrier launch: the grid must not exceed what
-// the device holds at once (occupancy API x CUs, one block per CU margin kept
-// for the gfx950 SGPR admission rule of MI355X_MICROARCH.md "Residency").
-// Queried once per context and kernel instantiation.
-template <int K, int NP, bool SLICE = false>
-static unsigned persist_grid_cap(qg_ctx* ctx, size_t cus) {
+// Resident blocks per CU of a tail kernel, for the co-residency guard of its
+// grid-barrier launch (tail_grid_cap): the occupancy API's answer, queried
+// once per context and kernel instantiation.
+template <int K, int NP, bool SLICE>
+static int tail_occupancy(qg_ctx* ctx) {
   const std::string key = std::string(SLICE ? "slice_occ_" : "persist_occ_") + std::to_string(K) +
                           "_" + std::to_string(NP);
   auto it = ctx->memo.find(key);
@@ -1876,245 +1707,66 @@ static unsigned persist_grid_cap(qg_ctx* ctx, size_t cus) {
     occ = std::stoi(it->second);
   }
   QG_CHECK(occ >= 1, QG_ERR_DEVICE, "persistent sumcheck kernel cannot be resident");
-  // bpc blocks per CU (QG_SC_TAIL_BPC, default 1), never more than the
-  // occupancy answer minus one: a spare block slot per CU keeps the barrier
-  // safe next to other kernels' blocks and under the gfx950 SGPR admission
-  // rule (MI355X_MICROARCH.md "Residency")
-  static const int bpc_env = [] {
-    const char* e = getenv("QG_SC_TAIL_BPC");
-    return e ? std::max(1, atoi(e)) : 1;
-  }();
-  const int bpc = std::max(1, std::min(bpc_env, occ - 1));
-  return (unsigned)std::max<size_t>(1, cus * (size_t)bpc);
+  return occ;
 }
 
-// io header: ScState | per-round barrier counters (nvars + 2) | 8 barrier
-// shards of the slice tail, one 128-B line each | challenges ...
-static size_t sumcheck_o_bar8(uint32_t nvars) {
-  return (sizeof(ScState) + sizeof(uint32_t) * (nvars + 2) + 127) & ~(size_t)127;
-}
-static uint32_t* sumcheck_bar8(uint32_t* bar, uint32_t nvars) {
-  uint8_t* io = reinterpret_cast<uint8_t*>(bar) - sizeof(ScState);
-  return reinterpret_cast<uint32_t*>(io + sumcheck_o_bar8(nvars));
-}
-// big-round limb accumulators (k_sc_big): [shard 8][16 points][9 limbs] u64;
-// round 0's in the io header after the barrier shards (zeroed per call),
-// round 1's in scratch; each round's last block clears the next round's
-static constexpr size_t SC_BACC_BYTES = 8 * 16 * 9 * sizeof(uint64_t);
-static size_t sumcheck_o_bacc0(uint32_t nvars) { return sumcheck_o_bar8(nvars) + 8 * 128; }
-static uint64_t* sumcheck_bacc0(uint32_t* bar, uint32_t nvars) {
-  uint8_t* io = reinterpret_cast<uint8_t*>(bar) - sizeof(ScState);
-  return reinterpret_cast<uint64_t*>(io + sumcheck_o_bacc0(nvars));
-}
+// the io region's pointers the round kernels share (ScIo: sumcheck_plan.h)
+struct ScIoPtrs {
+  uint32_t* bar;   // per-round barrier counters (k_sc_tail)
+  uint32_t* bar8;  // 8 barrier shards (large rounds' ticket, k_sc_slice's barrier)
+  uint64_t* acc0;  // accumulator slot 0
+};
 
-// The slice tail (k_sc_slice): G blocks, a power of two <= min(one per CU,
-// SMAX) so block 0 can gather one entry per block, each owning <= SMAX entries
-// per slot.  QG_SC_OLD_TAIL=1 keeps the streaming k_sc_tail (A/B runs).
+// one large round: the kernel of `form` (sc_big_form) on its grid
 template <int K, int NP>
-static size_t slice_gmax(qg_ctx* ctx, size_t cus) {
-  const char* off = getenv("QG_SC_OLD_TAIL");  // read per call: tests toggle it in-process
-  if (off && atoi(off) != 0) return 0;
-  const size_t gm = std::min<size_t>(persist_grid_cap<K, NP, true>(ctx, cus), sl_smax(K));
-  size_t G = 1;
-  while (G * 2 <= gm) G *= 2;
-  return G;
-}
-
-// largest round table (entries per slot) the slice tail can start from
-template <int K, int NP>
-static uint32_t slice_tail_log(qg_ctx* ctx, size_t cus) {
-  const size_t g = slice_gmax<K, NP>(ctx, cus);
-  if (!g) return 0;
-  uint32_t l = 0;
-  while (((size_t)1 << (l + 1)) <= g * sl_smax(K)) l++;
-  return l;
-}
-
-// launches k_sc_slice for rounds j0.. when a block's slice fits its LDS;
-// false: the caller launches k_sc_tail.
-template <int K, int NP>
-static bool launch_slice_tail(qg_ctx* ctx, size_t cus, TablePtrs t0, const SopDev* d_sp, SopHdr h,
-                              uint32_t nvars, uint32_t j0, int fold0, int pending0, RoundOut ro,
-                              uint32_t* bar, uint64_t* acc_j0, Fr* d_final, Fr* d_eval) {
-  const size_t gm = slice_gmax<K, NP>(ctx, cus);
-  if (!gm) return false;
-  const size_t n0 = (size_t)1 << (nvars - j0);
-  size_t G = 1;
-  while (G * 2 <= gm && G * 2 <= n0 / 2) G *= 2;
-  if (n0 / G > sl_smax(K)) return false;
-  uint64_t* acc64 = ctx->scratch_as<uint64_t>("sc_sacc", (size_t)std::max<uint32_t>(1, nvars - j0) * 8 * NP * 9);
-  // the 8 barrier shards follow the per-round counters (zeroed by the per-call
-  // header copy): sumcheck_bar8
-  uint32_t* bar8 = sumcheck_bar8(bar, nvars);
-  // regroup area: the round table published by the blocks (<= n0 entries per slot)
-  const uint32_t ns = std::max<uint32_t>(h.nslots, 1u);
-  Fr* sg = ctx->scratch_as<Fr>("sc_sgat", (size_t)ns * n0);
-  TablePtrs gat{};
-  for (uint32_t i = 0; i < 8; i++) gat.dst[i] = i < h.nslots ? sg + (size_t)i * n0 : nullptr;
-  hipLaunchKernelGGL((k_sc_slice<K, NP>), dim3((unsigned)G), dim3(SL_BLOCK), 0, ctx->stream, t0,
-                     gat, d_sp, h, nvars, j0, fold0, pending0, ro, acc_j0, bar8, acc64, d_final,
-                     d_eval);
-  QG_LAUNCH_CHECK();
-  ctx->sc_slice_tails++;
-  return true;
-}
-
-// thread-per-pair round kernel (k_sc_big) for product expressions and for
-// expressions of <= 4 slots at degree <= 3; false: use the staged k_sc_round
-static unsigned sc_big_blocks(qg_ctx* ctx, size_t npairs, int ov) {
-  size_t cap = ov > 0 ? (size_t)ov : (size_t)2 * ctx->num_cus();  // measured best (256 / 512 / 2048 blocks at 2^20: 0.289 / 0.264 / 0.333 ms)
-  cap = std::min<size_t>(cap, SC_MAX_BLOCKS);
-  return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, div_up(npairs, SC_BLOCK)));
-}
-
-// returns -1 when the staged k_sc_round must run instead, else the skip0 flag used
-template <int K, int NP>
-static int launch_big(qg_ctx* ctx, const std::vector<const Fr*>& src, Fr* X, Fr* Y, size_t N,
-                       uint32_t j, const SopDev* d_sp, SopHdr h, size_t npairs, RoundOut ro,
-                       int pending, Fr* loc, uint64_t* a0, uint64_t* a1, uint32_t* bar8,
-                       const ScSwitches& sw) {
-  // rounds j >= 1: h(0) = h_{j-1}(r_{j-1}) - h(1), exact by construction (the
-  // folded table's pair sums ARE the previous message at r); round 0 evaluates
-  // every point, so a wrong caller claim still yields the reference's bytes.
-  // QG_SC_NO_SKIP0=1 evaluates t = 0 in every round (A/B runs).
-  const int skip0 = (j >= 1 && h.np >= 2 && !sw.no_skip0) ? 1 : 0;
-  if (sw.staged || NP > 4) return -1;
-  const bool pure = (h.pad & SOP_PURE) != 0;
-  if (!pure && K > 4) return -1;
-  AllBufs tb{};
-  for (uint32_t i = 0; i < 8; i++) tb.in.src[i] = i < src.size() ? src[i] : nullptr;
-  tb.X = X;
-  tb.Y = Y;
-  tb.capX = N / 2;
-  tb.capY = std::max<size_t>(1, N / 4);
-  const unsigned blocks = sc_big_blocks(ctx, npairs, sw.big_blocks);
-  // QG_SC_WPE=4: the product sweep compiled for 4 waves per SIMD (<= 128 VGPRs,
+static void launch_big(qg_ctx* ctx, ScBig form, const RoundBufs& tb, uint32_t j, const SopDev* d_sp,
+                       SopHdr h, size_t npairs, RoundOut ro, int pending, Fr* loc, bool skip0,
+                       uint64_t* acc_j, uint64_t* acc_next, uint32_t* bar8, const ScSwitches& sw) {
+  // QG_SC_WPE: the product sweep compiled for 4 waves per SIMD (<= 128 VGPRs,
   // spills; tuning.  3 waves measured too: 0.214 -> 0.288 ms of big rounds,
   // profiles/r04_sumcheck_wpe_blocks_ab.txt)
-  static const bool wpe4 = getenv("QG_SC_WPE") != nullptr;
-  if (pure && wpe4)
-    hipLaunchKernelGGL((k_sc_big<K, 4, true, 4>), dim3(blocks), dim3(SC_BLOCK), 0,
-                       ctx->stream, tb, j, d_sp, h, npairs, ro, pending, loc, skip0, (j & 1) ? a1 : a0,
-                       (j & 1) ? a0 : a1, bar8);
-  else if (pure)
-    hipLaunchKernelGGL((k_sc_big<K, 4, true>), dim3(blocks), dim3(SC_BLOCK), 0, ctx->stream,
-                       tb, j, d_sp, h, npairs, ro, pending, loc, skip0, (j & 1) ? a1 : a0,
-                       (j & 1) ? a0 : a1, bar8);
-  else
-    hipLaunchKernelGGL((k_sc_big<4, 4, false>), dim3(blocks), dim3(SC_BLOCK), 0, ctx->stream,
-                       tb, j, d_sp, h, npairs, ro, pending, loc, skip0, (j & 1) ? a1 : a0,
-                       (j & 1) ? a0 : a1, bar8);
+  auto* fn = form == ScBig::staged ? &k_sc_round<K, NP>
+             : form == ScBig::sop  ? &k_sc_big<4, 4, false>
+             : sw.wpe4             ? &k_sc_big<K, 4, true, 4>
+                                   : &k_sc_big<K, 4, true>;
+  hipLaunchKernelGGL(fn, dim3(sc_round_grid(form, ctx->num_cus(), npairs, sw)), dim3(SC_BLOCK), 0,
+                     ctx->stream, tb, j, d_sp, h, npairs, ro, pending, loc, (int)skip0, acc_j,
+                     acc_next, bar8);
   QG_LAUNCH_CHECK();
-  (pure ? ctx->sc_big_pure_rounds : ctx->sc_big_sop_rounds)++;
-  return skip0;
+  (form == ScBig::staged ? ctx->sc_staged_rounds
+   : form == ScBig::sop  ? ctx->sc_big_sop_rounds
+                         : ctx->sc_big_pure_rounds)++;
 }
 
-// returns the first round of the persistent tail (its coefficient rows are
-// canonical words: k_sc_tail's finish_core canon_out)
+// rounds j0.. in one launch: k_sc_slice when a block's slice fits its LDS,
+// else the streaming k_sc_tail.  cus: the CUs the grid may count on.
 template <int K, int NP>
-static uint32_t run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
-                       const SopDev* d_sp, SopHdr h, RoundOut ro, uint32_t* bar, Fr* d_final,
-                       Fr* d_eval, const ScSwitches& sw) {
-
-  const uint32_t nslots = h.nslots;
-  const size_t N = (size_t)1 << nvars;
-  // ping-pong scratch: X holds N/2 per slot, Y holds N/4 per slot
-  Fr* X = ctx->scratch_as<Fr>("sc_x", std::max<size_t>(1, (N / 2) * nslots));
-  Fr* Y = ctx->scratch_as<Fr>("sc_y", std::max<size_t>(1, (N / 4) * nslots));
-  Fr* partial = ctx->scratch_as<Fr>("sc_partial", (size_t)SC_MAX_BLOCKS * NP);
-  uint64_t* a0 = sumcheck_bacc0(bar, nvars);
-  uint64_t* a1 = reinterpret_cast<uint64_t*>(ctx->scratch_as<uint8_t>("sc_bacc1", SC_BACC_BYTES));
-  uint32_t* bar8 = sumcheck_bar8(bar, nvars);
-  // the staged round kernel does not clear the next accumulator slot: the
-  // tail's first slot is then cleared here when it is the scratch one
-  bool staged = false;
-  auto clear_tail_slot = [&](uint32_t j0) {
-    if (staged && (j0 & 1)) QG_HIP(hipMemsetAsync(a1, 0, SC_BACC_BYTES, ctx->stream));
-  };
-  TablePtrs cur{};
-  for (uint32_t i = 0; i < 8; i++) cur.src[i] = i < src.size() ? src[i] : nullptr;
-  auto bufs = [&](Fr* base, size_t per) {
-    TablePtrs t{};
-    for (uint32_t i = 0; i < 8; i++) t.dst[i] = i < nslots ? base + per * i : nullptr;
-    return t;
-  };
-  TablePtrs tX = bufs(X, N / 2), tY = bufs(Y, std::max<size_t>(1, N / 4));
-  int fold = 0, pending = 0;
-  uint32_t j = 0;
-  int parity = 0;  // next destination: 0 -> X, 1 -> Y
-  // QG_SC_PERS_LOG overrides where the persistent tail takes over (tuning)
-  const int pers_log = sw.pers_log;
-  {
-    QgTimed tm(ctx, "sumcheck_round");
-    // the slice tail starts once a round's table fits the blocks' LDS slices
-    const uint32_t sl = slice_tail_log<K, NP>(ctx, ctx->num_cus());
-    const int plog = sl ? std::min<int>(pers_log, (int)sl) : pers_log;
-    for (; j < nvars; j++) {
-      const size_t table = N >> j;  // entries per table evaluated in round j
-      if (table <= ((size_t)1 << plog)) break;
-      const size_t npairs = table / 2;
-      TablePtrs tp = cur;
-      if (fold) {
-        const TablePtrs& d = parity ? tY : tX;
-        for (int i = 0; i < 8; i++) tp.dst[i] = d.dst[i];
-      }
-      if (launch_big<K, NP>(ctx, src, X, Y, N, j, d_sp, h, npairs, ro, pending, nullptr, a0, a1,
-                            bar8, sw) < 0) {
-        hipLaunchKernelGGL((k_sc_round<K, NP>),
-                           dim3(sc_round_blocks(ctx, npairs, sw.round_blocks)), dim3(SC_BLOCK), 0,
-                           ctx->stream, tp, d_sp, h, npairs, fold, ro, j, pending, partial,
-                           (Fr*)nullptr);
-        staged = true;
-        ctx->sc_staged_rounds++;
-      }
-      QG_LAUNCH_CHECK();
-      if (fold) {
-        for (int i = 0; i < 8; i++) cur.src[i] = tp.dst[i];
-        parity ^= 1;
-      }
-      fold = 1;
-      pending = 1;
-    }
+static void launch_tail(qg_ctx* ctx, size_t gmax, size_t cus, const RoundBufs& tb,
+                        const SopDev* d_sp, SopHdr h, uint32_t nvars, uint32_t j0, int pending,
+                        RoundOut ro, const ScIoPtrs& io, uint64_t* acc_j0, Fr* d_final, Fr* d_eval,
+                        const ScSwitches& sw) {
+  const size_t n0 = (size_t)1 << (nvars - j0);
+  ctx->sc_tail_first_round = j0;
+  if (const size_t G = slice_grid(K, gmax, n0)) {
+    uint64_t* acc64 = ctx->scratch_as<uint64_t>(
+        "sc_sacc", (size_t)std::max<uint32_t>(1, nvars - j0) * 8 * NP * 9);
+    // regroup area: the round table published by the blocks (n0 entries per slot)
+    Fr* gat = ctx->scratch_as<Fr>("sc_sgat", (size_t)std::max<uint32_t>(h.nslots, 1u) * n0);
+    hipLaunchKernelGGL((k_sc_slice<K, NP>), dim3((unsigned)G), dim3(SL_BLOCK), 0, ctx->stream, tb,
+                       gat, d_sp, h, nvars, j0, pending, ro, acc_j0, io.bar8, acc64, d_final,
+                       d_eval);
+    QG_LAUNCH_CHECK();
+    ctx->sc_slice_tails++;
+    return;
   }
-  {
-    QgTimed tm(ctx, "sumcheck_tail");
-    // Tail destinations.  k_sc_tail writes round j0's fold into t0.dst, then
-    // alternates bufA, bufB, bufA, ...  Capacities: X >= N/2, Y >= N/4.
-    //  j0 == 0: round 0 does not fold; round 1 writes N/2 -> X, round 2 -> Y, ...
-    //  j0 >= 1: round j0 writes N>>j0 into the buffer not holding cur.src
-    //           (X when parity == 0, j0 >= 1; Y when parity == 1, j0 >= 2).
-    TablePtrs t0 = cur, bufA, bufB;
-    if (j == 0) {
-      bufA = tX;
-      bufB = tY;
-    } else {
-      const TablePtrs& a = parity ? tY : tX;
-      const TablePtrs& b = parity ? tX : tY;
-      for (int i = 0; i < 8; i++) t0.dst[i] = a.dst[i];
-      bufA = b;
-      bufB = a;
-    }
-    // round j's accumulator slot was cleared by the last big round (or the
-    // per-call header when there is none)
-    clear_tail_slot(j);
-    ctx->sc_tail_first_round = j;
-    if (!launch_slice_tail<K, NP>(ctx, ctx->num_cus(), t0, d_sp, h, nvars, j, fold, pending, ro,
-                                  bar, (j & 1) ? a1 : a0, d_final, d_eval)) {
-      // persistent launch: one block per CU at most (co-residency for the grid
-      // barrier), fewer when the first persistent round has fewer pair groups
-      const size_t PB = tail_pb(h.nslots, NP);
-      const size_t pairs0 = (N >> j) / 2;
-      const unsigned grid = (unsigned)std::max<size_t>(
-          1, std::min<size_t>(persist_grid_cap<K, NP>(ctx, ctx->num_cus()), (pairs0 + PB - 1) / PB));
-      Fr* ppart = ctx->scratch_as<Fr>("sc_ppartial", (size_t)2 * grid * NP);
-      hipLaunchKernelGGL((k_sc_tail<K, NP>), dim3(grid), dim3(TAIL_BLOCK), 0, ctx->stream, t0,
-                         bufA, bufB, d_sp, h, nvars, j, fold, pending, ro, ppart, bar, d_final,
-                         d_eval);
-      QG_LAUNCH_CHECK();
-      ctx->sc_stream_tails++;
-    }
-  }
-  return j;
+  // fewer blocks than the cap when the first round has fewer pair groups
+  const unsigned grid = stream_grid(tail_grid_cap(tail_occupancy<K, NP, false>(ctx), cus, sw),
+                                    n0 / 2, tail_pb(h.nslots, NP));
+  Fr* ppart = ctx->scratch_as<Fr>("sc_ppartial", (size_t)2 * grid * NP);
+  hipLaunchKernelGGL((k_sc_tail<K, NP>), dim3(grid), dim3(TAIL_BLOCK), 0, ctx->stream, tb, d_sp, h,
+                     nvars, j0, pending, ro, ppart, io.bar, d_final, d_eval);
+  QG_LAUNCH_CHECK();
+  ctx->sc_stream_tails++;
 }
 
 // gathered [rank][slot][e] (S entries per rank and slot) -> per-slot tables
@@ -2128,98 +1780,70 @@ __global__ void k_sc_gather_tables(const Fr* __restrict__ in, uint32_t world, ui
   out[sl * world * S + rk * S + e] = in[idx];
 }
 
-// Sharded rounds: this rank holds the block of every table whose
-// high log2(world) index bits equal its rank.  The large rounds 0..js-1 pair
-// local entries only: one allgather of the (d+1) round sums per round, then
-// every rank runs the identical device transcript (k_sc_finish).  Once the
-// folded tables are small (global size <= 2^(SC_GATHER_LOG)) every rank
-// allgathers its block and runs the remaining rounds redundantly in the
-// single-GPU persistent kernel — no per-round collective on the
-// latency-bound tail (which does not shrink with more GPUs anyway).
-static constexpr uint32_t SC_GATHER_LOG = 16;
-
+// The rounds of one proof: large rounds 0..j0-1, one kernel each, then one
+// tail launch for rounds j0..nvars-1 (sumcheck_plan.h has every decision).
+// Sharded: this rank holds the block of every table whose high
+// log2(world) index bits equal its rank.  The large rounds pair local entries
+// only: one allgather of the (d+1) round sums per round, then every rank runs
+// the identical device transcript (k_sc_finish).  Once the folded tables are
+// small (sc_gather_round) every rank allgathers its block and runs the
+// remaining rounds redundantly in the single-GPU tail — no per-round
+// collective on the latency-bound tail (which does not shrink with more GPUs
+// anyway).
 template <int K, int NP>
-static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
-                            const SopDev* d_sp, SopHdr h, RoundOut ro, uint32_t* bar, Fr* d_final,
-                            Fr* d_eval, const ScSwitches& sw) {
-  const uint32_t nslots = h.nslots;
-  const uint32_t world = (uint32_t)ctx->world;
+static void run_rounds(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
+                       const SopDev* d_sp, SopHdr h, RoundOut ro, const ScIoPtrs& io, Fr* d_final,
+                       Fr* d_eval, const ScSwitches& sw) {
+  const bool sharded = ctx->sharded;
+  const uint32_t nslots = h.nslots, ns = std::max(nslots, 1u);
+  const uint32_t world = sharded ? (uint32_t)ctx->world : 1u;
   uint32_t lw = 0;
   while ((1u << lw) < world) lw++;
   QG_CHECK((1u << lw) == world, QG_ERR_INVALID, "sharded sumcheck needs a power-of-two world");
-  QG_CHECK(nvars > lw, QG_ERR_INVALID, "sharded sumcheck needs nvars > log2(world)");
-  const uint32_t m = nvars - lw;
-  const size_t NL = (size_t)1 << m;
-  // sharded rounds: until the source tables of round js (folded through
-  // r_{js-2}, global size 2^(nvars - js + 1)) fit the gather size; at most m
-  // (local tables of 2 entries)
-  uint32_t js = nvars + 1 > SC_GATHER_LOG ? nvars + 1 - SC_GATHER_LOG : 0;
-  if (js > m) js = m;
-  Fr* X = ctx->scratch_as<Fr>("sc_x", std::max<size_t>(1, (NL / 2) * std::max(nslots, 1u)));
-  Fr* Y = ctx->scratch_as<Fr>("sc_y", std::max<size_t>(1, (NL / 4) * std::max(nslots, 1u)));
-  Fr* partial = ctx->scratch_as<Fr>("sc_partial", (size_t)SC_MAX_BLOCKS * NP);
-  uint64_t* a0 = sumcheck_bacc0(bar, nvars);
-  uint64_t* a1 = reinterpret_cast<uint64_t*>(ctx->scratch_as<uint8_t>("sc_bacc1", SC_BACC_BYTES));
-  uint32_t* bar8 = sumcheck_bar8(bar, nvars);
-  // the staged round kernel does not clear the next accumulator slot: the
-  // tail's first slot is then cleared here when it is the scratch one
-  bool staged = false;
-  auto clear_tail_slot = [&](uint32_t j0) {
-    if (staged && (j0 & 1)) QG_HIP(hipMemsetAsync(a1, 0, SC_BACC_BYTES, ctx->stream));
-  };
-  Fr* loc = ctx->scratch_as<Fr>("sc_loc", NP);
-  Fr* all = ctx->scratch_as<Fr>("sc_all", (size_t)world * NP);
-  TablePtrs cur{};
-  for (uint32_t i = 0; i < 8; i++) cur.src[i] = i < src.size() ? src[i] : nullptr;
-  auto bufs = [&](Fr* base, size_t per) {
-    TablePtrs t{};
-    for (uint32_t i = 0; i < 8; i++) t.dst[i] = i < nslots ? base + per * i : nullptr;
-    return t;
-  };
-  TablePtrs tX = bufs(X, NL / 2), tY = bufs(Y, std::max<size_t>(1, NL / 4));
-  int fold = 0, parity = 0;
+  QG_CHECK(!sharded || nvars > lw, QG_ERR_INVALID, "sharded sumcheck needs nvars > log2(world)");
+  const size_t NL = (size_t)1 << (nvars - lw);  // this rank's entries per table
+  // co-residency of the tail's grid barrier: with the in-process loopback every
+  // rank shares one device, so each tail grid takes a 1/world share of the CUs
+  const size_t cus = sharded && comm_is_loopback(ctx) ? std::max<size_t>(1, ctx->num_cus() / world)
+                                                      : (size_t)ctx->num_cus();
+  const size_t gmax = slice_gmax(K, tail_grid_cap(tail_occupancy<K, NP, true>(ctx), cus, sw), sw);
+  const uint32_t j0 = sharded ? sc_gather_round(nvars, lw, sw)
+                              : sc_first_tail_round(nvars, sw, slice_tail_log(K, gmax));
+  Fr* X = ctx->scratch_as<Fr>("sc_x", std::max<size_t>(1, (NL / 2) * ns));
+  Fr* Y = ctx->scratch_as<Fr>("sc_y", std::max<size_t>(1, (NL / 4) * ns));
+  RoundBufs tb = round_bufs<Fr>(1, X, Y, NL);
+  for (uint32_t i = 0; i < 8; i++) tb.in[i] = i < src.size() ? src[i] : nullptr;
+  uint64_t* acc[2] = {io.acc0, reinterpret_cast<uint64_t*>(
+                                   ctx->scratch_as<uint8_t>("sc_bacc1", SC_BACC_BYTES))};
+  Fr* loc = sharded ? ctx->scratch_as<Fr>("sc_loc", NP) : nullptr;
+  Fr* all = sharded ? ctx->scratch_as<Fr>("sc_all", (size_t)world * NP) : nullptr;
   {
     QgTimed tm(ctx, "sumcheck_round");
-    for (uint32_t j = 0; j < js; j++) {
-      const size_t npairs = (NL >> j) / 2;
-      TablePtrs tp = cur;
-      if (fold) {
-        const TablePtrs& d = parity ? tY : tX;
-        for (int i = 0; i < 8; i++) tp.dst[i] = d.dst[i];
+    const ScBig form = sc_big_form({K, NP}, (h.pad & SOP_PURE) != 0, sw);
+    for (uint32_t j = 0; j < j0; j++) {
+      const bool skip0 = sc_skip0(form, h.np, j, sw);
+      // one GPU: round j - 1's challenge bytes are absorbed beside the sweep
+      launch_big<K, NP>(ctx, form, tb, j, d_sp, h, (NL >> j) / 2, ro, !sharded && j > 0, loc, skip0,
+                        acc[j & 1], acc[(j + 1) & 1], io.bar8, sw);
+      if (sharded) {
+        comm_allgather_bytes(ctx, loc, all, sizeof(Fr) * NP);
+        hipLaunchKernelGGL((k_sc_finish<NP>), dim3(1), dim3(SC_BLOCK), 0, ctx->stream, d_sp, h, all,
+                           world, ro, j, (int)skip0);
+        QG_LAUNCH_CHECK();
       }
-      int skip0 =
-          launch_big<K, NP>(ctx, src, X, Y, NL, j, d_sp, h, npairs, ro, 0, loc, a0, a1, bar8, sw);
-      if (skip0 < 0) {
-        skip0 = 0;
-        staged = true;
-        hipLaunchKernelGGL((k_sc_round<K, NP>),
-                           dim3(sc_round_blocks(ctx, npairs, sw.round_blocks)), dim3(SC_BLOCK), 0,
-                           ctx->stream, tp, d_sp, h, npairs, fold, ro, j, 0, partial, loc);
-        ctx->sc_staged_rounds++;
-      }
-      QG_LAUNCH_CHECK();
-      comm_allgather_bytes(ctx, loc, all, sizeof(Fr) * NP);
-      hipLaunchKernelGGL((k_sc_finish<NP>), dim3(1), dim3(SC_BLOCK), 0, ctx->stream, d_sp, h, all,
-                         world, ro, j, skip0);
-      QG_LAUNCH_CHECK();
-      if (fold) {
-        for (int i = 0; i < 8; i++) cur.src[i] = tp.dst[i];
-        parity ^= 1;
-      }
-      fold = 1;
     }
   }
-  {
-    QgTimed tm(ctx, "sumcheck_tail");
-    // this rank's source tables of round js: S entries per slot
-    const size_t S = js == 0 ? NL : NL >> (js - 1);
-    const size_t GN = (size_t)world * S;  // global size = 2^(nvars - js + 1) (js >= 1)
-    const uint32_t ns = std::max(nslots, 1u);
+  QgTimed tm(ctx, "sumcheck_tail");
+  if (sharded) {
+    // the tail's source: this rank's source tables of round j0 (S entries per
+    // slot), gathered to the global tables of 2^(nvars - j0 + 1) entries (j0 >= 1)
+    const size_t S = j0 == 0 ? NL : NL >> (j0 - 1);
+    const size_t GN = (size_t)world * S;
     Fr* pack = ctx->scratch_as<Fr>("scg_pack", ns * S);
     Fr* gat = ctx->scratch_as<Fr>("scg_all", (size_t)world * ns * S);
     Fr* G = ctx->scratch_as<Fr>("scg_src", ns * GN);
     for (uint32_t i = 0; i < nslots; i++)
-      QG_HIP(hipMemcpyAsync(pack + (size_t)i * S, cur.src[i], S * sizeof(Fr),
+      QG_HIP(hipMemcpyAsync(pack + (size_t)i * S, tb.src(j0, i), S * sizeof(Fr),
                             hipMemcpyDeviceToDevice, ctx->stream));
     if (nslots) {
       comm_allgather_bytes(ctx, pack, gat, (size_t)nslots * S * sizeof(Fr));
@@ -2227,80 +1851,17 @@ static uint32_t run_rounds_dist(qg_ctx* ctx, uint32_t nvars, const std::vector<c
                          dim3(256), 0, ctx->stream, gat, world, nslots, S, G);
       QG_LAUNCH_CHECK();
     }
-    // ping-pong buffers of the persistent rounds (run_rounds' capacities):
-    // js == 0: round 0 does not fold, a >= GN/2, b >= GN/4 alternate from round 1;
-    // js >= 1: round js folds into a (>= GN/2), then b (>= GN/4), a, ...
+    // the gathered tables are the inputs of round max(j0, 1)'s fold, which
+    // writes GN / 2 entries per slot, the next GN / 4
     Fr* A = ctx->scratch_as<Fr>("scg_a", ns * std::max<size_t>(1, GN / 2));
     Fr* B = ctx->scratch_as<Fr>("scg_b", ns * std::max<size_t>(1, GN / 4));
-    TablePtrs t0{}, bufA{}, bufB{};
-    for (uint32_t i = 0; i < 8; i++) {
-      const bool u = i < nslots;
-      t0.src[i] = u ? G + (size_t)i * GN : nullptr;
-      Fr* a = u ? A + (size_t)i * std::max<size_t>(1, GN / 2) : nullptr;
-      Fr* b = u ? B + (size_t)i * std::max<size_t>(1, GN / 4) : nullptr;
-      if (js == 0) {
-        bufA.dst[i] = a;
-        bufB.dst[i] = b;
-      } else {
-        t0.dst[i] = a;
-        bufA.dst[i] = b;
-        bufB.dst[i] = a;
-      }
-    }
-    const size_t PB = tail_pb(h.nslots, NP);
-    const size_t pairs0 = ((size_t)1 << nvars >> js) / 2;
-    // co-residency of the grid barrier: with the in-process loopback every rank
-    // shares one device, so each persistent grid takes a 1/world share of the CUs
-    const size_t cus = comm_is_loopback(ctx) ? std::max<size_t>(1, ctx->num_cus() / world)
-                                             : (size_t)ctx->num_cus();
-    clear_tail_slot(js);
-    ctx->sc_tail_first_round = js;
-    if (!launch_slice_tail<K, NP>(ctx, cus, t0, d_sp, h, nvars, js, js >= 1 ? 1 : 0, 0, ro, bar,
-                                  (js & 1) ? a1 : a0, d_final, d_eval)) {
-      const unsigned grid = (unsigned)std::max<size_t>(
-          1, std::min<size_t>(persist_grid_cap<K, NP>(ctx, cus), (pairs0 + PB - 1) / PB));
-      Fr* ppart = ctx->scratch_as<Fr>("sc_ppartial", (size_t)2 * grid * NP);
-      hipLaunchKernelGGL((k_sc_tail<K, NP>), dim3(grid), dim3(TAIL_BLOCK), 0, ctx->stream, t0,
-                         bufA, bufB, d_sp, h, nvars, js, js >= 1 ? 1 : 0, 0, ro, ppart, bar,
-                         d_final, d_eval);
-      QG_LAUNCH_CHECK();
-      ctx->sc_stream_tails++;
-    }
+    tb = round_bufs<Fr>(std::max(j0, 1u), A, B, GN);
+    for (uint32_t i = 0; i < 8; i++) tb.in[i] = i < nslots ? G + (size_t)i * GN : nullptr;
   }
-  return js;
-}
-
-template <int K, int NP>
-static uint32_t run_rounds_any(qg_ctx* ctx, uint32_t nvars, const std::vector<const Fr*>& src,
-                               const SopDev* d_sp, SopHdr h, RoundOut ro, uint32_t* bar,
-                               Fr* d_final, Fr* d_eval, const ScSwitches& sw) {
-  if (ctx->sharded)
-    return run_rounds_dist<K, NP>(ctx, nvars, src, d_sp, h, ro, bar, d_final, d_eval, sw);
-  return run_rounds<K, NP>(ctx, nvars, src, d_sp, h, ro, bar, d_final, d_eval, sw);
-}
-
-// inverse Vandermonde on nodes 0..np-1 for any np <= GEN_NPMAX: V[t][u]
-// (Montgomery) with coefficient t of the interpolant = sum_u V[t][u] ev[u]
-static std::vector<Fr> vinv_general(uint32_t np) {
-  std::vector<Fr> V((size_t)np * np, Fr::zero());
-  for (uint32_t j = 0; j < np; j++) {
-    std::vector<Fr> poly(1, Fr::one());
-    Fr den = Fr::one();
-    for (uint32_t m = 0; m < np; m++) {
-      if (m == j) continue;
-      std::vector<Fr> np2(poly.size() + 1, Fr::zero());
-      const Fr negm = fneg(from_u64<FrP>(m));
-      for (size_t k = 0; k < poly.size(); k++) {
-        np2[k] = np2[k] + poly[k] * negm;
-        np2[k + 1] = np2[k + 1] + poly[k];
-      }
-      poly = np2;
-      den = den * ((j >= m) ? from_u64<FrP>(j - m) : fneg(from_u64<FrP>(m - j)));
-    }
-    const Fr dinv = finv(den);
-    for (uint32_t i = 0; i < np; i++) V[(size_t)i * np + j] = poly[i] * dinv;
-  }
-  return V;
+  // round j0's accumulator slot was cleared by the last large round (or by the
+  // per-call header copy when there is none)
+  launch_tail<K, NP>(ctx, gmax, cus, tb, d_sp, h, nvars, j0, !sharded && j0 > 0, ro, io,
+                     acc[j0 & 1], d_final, d_eval, sw);
 }
 
 // value of the postfix program on host values (Montgomery), per input table
@@ -2454,7 +2015,7 @@ static void sumcheck_run_generic(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
   std::vector<L9> t29(GEN_NPMAX);
   for (uint32_t t = 0; t < (uint32_t)GEN_NPMAX; t++)
     t29[t] = l9_of(plain_mul(from_u64_plain(t), pow2_mod_plain<FrP>(261)));
-  const std::vector<Fr> V = vinv_general(np);
+  const std::vector<Fr> V = build_vinv(np);
   const auto dprog = gen_upload(ctx, g, "gen_prog");
   const GenOp* d_ops = dprog.first;
   const L9* d_c29 = dprog.second;
@@ -2664,15 +2225,10 @@ static void sumcheck_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
     memcpy(hs.state, st, 32);
   }
 
-  // one device region: ScState | barrier counters | chal | coeffs | final (8 slots +
-  // evaluation) | lens.  ScState and the counters are (re)initialised per call.
-  const size_t o_bar = sizeof(ScState);
-  const size_t o_chal = sumcheck_o_bacc0(nvars) + SC_BACC_BYTES;  // after the accumulator
-  const size_t o_coeffs = o_chal + sizeof(Fr) * nvars;
-  const size_t o_final = o_coeffs + sizeof(Fr) * (size_t)nvars * width;
-  const size_t o_lens = o_final + sizeof(Fr) * 9;
-  const size_t io_bytes = o_lens + sizeof(uint32_t) * nvars;
-  uint8_t* io = ctx->scratch_as<uint8_t>("sc_io", io_bytes);
+  // one device region (ScIo); everything before the challenges is
+  // (re)initialised per call
+  const ScIo o = sc_io(nvars, width);
+  uint8_t* io = ctx->scratch_as<uint8_t>("sc_io", o.bytes);
   SopDev* d_sp = ctx->scratch_as<SopDev>("sc_prog", 1);
   // the device copy holds program P->id while the slot's allocation generation
   // is unchanged (arena.h: never an address)
@@ -2682,49 +2238,42 @@ static void sumcheck_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
     QG_HIP(hipMemcpyAsync(d_sp, &P->img, sizeof(SopDev), hipMemcpyHostToDevice, ctx->stream));
     ctx->arena.commit("sc_prog", memo);
   }
-  uint8_t* hio = reinterpret_cast<uint8_t*>(ctx->pinned_get("sc_io", io_bytes));
-  memset(hio, 0, o_chal);
+  uint8_t* hio = reinterpret_cast<uint8_t*>(ctx->pinned_get("sc_io", o.bytes));
+  memset(hio, 0, o.chal);
   memcpy(hio, &hs, sizeof hs);
-  QG_HIP(hipMemcpyAsync(io, hio, o_chal, hipMemcpyHostToDevice, ctx->stream));
-  uint32_t* bar = reinterpret_cast<uint32_t*>(io + o_bar);
+  QG_HIP(hipMemcpyAsync(io, hio, o.chal, hipMemcpyHostToDevice, ctx->stream));
 
   std::vector<const Fr*> src;
   for (uint32_t u : P->used) src.push_back(d_tables[u]);
-  RoundOut ro{reinterpret_cast<ScState*>(io), reinterpret_cast<Fr*>(io + o_chal),
-              reinterpret_cast<Fr*>(io + o_coeffs), reinterpret_cast<uint32_t*>(io + o_lens),
-              width};
-  Fr* d_final = reinterpret_cast<Fr*>(io + o_final);
+  const RoundOut ro{reinterpret_cast<ScState*>(io), reinterpret_cast<Fr*>(io + o.chal),
+                    reinterpret_cast<Fr*>(io + o.coeffs), reinterpret_cast<uint32_t*>(io + o.lens),
+                    width};
+  const ScIoPtrs iop{reinterpret_cast<uint32_t*>(io + o.bar), reinterpret_cast<uint32_t*>(io + o.bar8),
+                     reinterpret_cast<uint64_t*>(io + o.acc0)};
+  Fr* d_final = reinterpret_cast<Fr*>(io + o.fin);
   Fr* d_eval = d_final + 8;
-  const uint32_t np = P->hdr.np;
-  const size_t nsrc = src.size();
   // (with no used slots, nslots = 0 and loads are skipped)
-  uint32_t tail0;
-  if (np <= 4) {
-    if (nsrc <= 4) tail0 = run_rounds_any<4, 4>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
-    else tail0 = run_rounds_any<8, 4>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
-  } else if (np <= 8) {
-    if (nsrc <= 4) tail0 = run_rounds_any<4, 8>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
-    else tail0 = run_rounds_any<8, 8>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
-  } else {
-    tail0 = run_rounds_any<8, 16>(ctx, nvars, src, d_sp, P->hdr, ro, bar, d_final, d_eval, sw);
-  }
+  const ScInstance in = sc_instance((uint32_t)src.size(), P->hdr.np);
+  auto* run = in.NP == 4   ? (in.K == 4 ? &run_rounds<4, 4> : &run_rounds<8, 4>)
+              : in.NP == 8 ? (in.K == 4 ? &run_rounds<4, 8> : &run_rounds<8, 8>)
+                           : &run_rounds<8, 16>;
+  run(ctx, nvars, src, d_sp, P->hdr, ro, iop, d_final, d_eval, sw);
 
-  QG_HIP(hipMemcpyAsync(hio, io, io_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  QG_HIP(hipMemcpyAsync(hio, io, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
   ctx->sync();
-  const std::vector<uint8_t> h(hio, hio + io_bytes);
+  const std::vector<uint8_t> h(hio, hio + o.bytes);
   QG_CHECK(reinterpret_cast<const ScState*>(h.data())->err == 0, QG_ERR_DEVICE,
            "sumcheck: grid barrier timed out (persistent blocks not co-resident)");
   memcpy(state, h.data(), 32);
-  memcpy(round_lens, h.data() + o_lens, sizeof(uint32_t) * nvars);
-  const Fr* hc = reinterpret_cast<const Fr*>(h.data() + o_coeffs);
-  // every round kernel writes canonical words (finish_core canon_out): the
-  // Montgomery pass after the challenge stays off the device's critical path
-  (void)tail0;
+  memcpy(round_lens, h.data() + o.lens, sizeof(uint32_t) * nvars);
+  // every round kernel writes its coefficient row as canonical words (finish_core)
+  const Fr* hc = reinterpret_cast<const Fr*>(h.data() + o.coeffs);
   for (size_t i = 0; i < (size_t)nvars * width; i++) fr_export(to_mont(hc[i]), round_coeffs + 4 * i);
-  const Fr* hp = reinterpret_cast<const Fr*>(h.data() + o_chal);
+  const Fr* hp = reinterpret_cast<const Fr*>(h.data() + o.chal);
   for (uint32_t i = 0; i < nvars; i++) fr_export(hp[i], point + 4 * i);
-  fr_export(reinterpret_cast<const Fr*>(h.data() + o_final)[8], evaluation);
+  fr_export(reinterpret_cast<const Fr*>(h.data() + o.fin)[8], evaluation);
 }
+
 
 // entries per table held by this rank: 2^nvars, or 2^(nvars - log2(world)) when
 // the tables are sharded over an attached communicator

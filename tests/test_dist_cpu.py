@@ -4,7 +4,7 @@ product code it mirrors:
 
 * MSM sharded by base index: each rank's partial sum, allgathered and added,
   equals the full MSM (msm_device_batch).
-* Sumcheck sharded by the high index bits (run_rounds_dist): per round every
+* Sumcheck sharded by the high index bits (the sharded run_rounds): per round every
   rank sums its local pairs, the (d+1) sums are allgathered, every rank runs
   the same transcript; once the global tables reach the gather size, every
   rank allgathers its block of that round's SOURCE tables and finishes
@@ -47,7 +47,7 @@ def _allgather_obj(x, world):
 
 
 def sharded_sumcheck(rank, world, nv, tabs, expr, claimed, domain, gather_log=16):
-    """The sharded protocol of run_rounds_dist (csrc/sumcheck.hip), step for step:
+    """The sharded protocol of run_rounds (csrc/sumcheck.hip), step for step:
 
     * rounds j < js (js = nv + 1 - gather_log, at most the local variable
       count m) pair local entries only; the fold by r_{j-1} is fused into round

@@ -61,7 +61,7 @@ def test_old_tail_matches_slice_tail(dev, nv, ntab):
 @pytest.mark.parametrize("world,nv", [(8, 17), (4, 16)])
 def test_sharded_k8_tail_matches_single(world, nv):
     """8 source tables: the gathered 2^15-entry tail exceeds what the slice tail
-    covers with 8 slots (and the loopback's 1/world CU share), so run_rounds_dist
+    covers with 8 slots (and the loopback's 1/world CU share), so run_rounds
     falls back to k_sc_tail; its proof equals the single-context proof."""
     import quill_amd as q
     from quill_amd.hyperplonk import VirtualPolyExpr as E, sumcheck_prove_tables

@@ -69,7 +69,7 @@ def test_rccl_msm_matches_single(rdev, dev, logn):
 
 @pytest.mark.parametrize("nv,ntab", [(9, 3), (18, 3), (20, 3), (17, 6)])
 def test_rccl_sumcheck_matches_single(rdev, dev, nv, ntab):
-    """run_rounds_dist at world 1: per-round ncclAllGather of the round sums,
+    """the sharded run_rounds at world 1: per-round ncclAllGather of the round sums,
     the gather of the folded tables, then the slice tail (or k_sc_tail)."""
     import quill_amd as q
     from quill_amd.hyperplonk import VirtualPolyExpr as E, sumcheck_prove_device

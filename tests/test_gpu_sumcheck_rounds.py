@@ -231,6 +231,71 @@ def test_call_sequence_leaves_no_state(dev):
         check_case(dev, name, nv, pers=pers, tail="stream" if "OLD_TAIL" in sw else "slice", **sw)
 
 
+# --- sharded large rounds ----------------------------------------------------------
+# On a sharded context QG_SC_PERS_LOG also lowers the gather point: the ranks
+# run js = min(nvars + 1 - PERS_LOG, nvars - log2(world)) large rounds on their
+# local blocks (k_sc_finish after each), gather, and run the tail from round js.
+def sharded_calls(world, pers, calls, **sw):
+    """`calls` = [(case name, nvars)] proved in order by every rank of one
+    loopback group, each rank in one context; per rank and call the proof, the
+    counter differences and the tail's first round"""
+    from test_gpu_multirank import run_ranks
+    refs = [reference(name, nv) for name, nv in calls]
+
+    def fn(dev, rank, world):
+        out = []
+        for (name, nv), (tabs, claimed, _) in zip(calls, refs):
+            nl = (1 << nv) // world
+            before = snapshot(dev)
+            got = prove(dev, nv, [tb[rank * nl:(rank + 1) * nl] for tb in tabs], sc.BY_NAME[name],
+                        claimed)
+            after = snapshot(dev)
+            out.append((got, {n: after[n] - before[n] for n in COUNTERS},
+                        dev.counter("sc_tail_first_round")))
+        return out
+    with switches(PERS_LOG=pers, **sw):
+        return run_ranks(world, fn), refs
+
+
+def check_sharded(world, pers, calls, js, tail=None, **sw):
+    outs, refs = sharded_calls(world, pers, calls, **sw)
+    assert len(outs) == world
+    for rank_out in outs:
+        for (name, nv), (_, _, want), (got, diff, first), j in zip(calls, refs, rank_out, js):
+            big = diff.pop(KERNEL_COUNTER[sc.BY_NAME[name].kernel])
+            tails = (diff.pop("sc_slice_tails"), diff.pop("sc_stream_tails"))
+            assert big == j and first == j
+            assert sum(tails) == 1 and (tail is None or tails == ((1, 0) if tail == "slice" else (0, 1)))
+            assert not any(diff.values())
+            assert got == want
+
+
+@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("name", ["prod3", "mixed", "k8d3", "k4d7"])
+def test_sharded_large_rounds_match_oracle(name, world):
+    """nvars 12 at PERS_LOG 6: 7 large rounds on local blocks of 2^11 / 2^10
+    entries (pure, sop, staged <8,4> and <4,8>), the tail from the odd round 7"""
+    check_sharded(world, 6, [(name, 12)], [7])
+
+
+def test_sharded_large_rounds_streaming_tail():
+    check_sharded(2, 6, [("prod3", 12)], [7], tail="stream", OLD_TAIL=1)
+
+
+@pytest.mark.parametrize("name", ["prod2", "mixed"])
+def test_sharded_gather_round_clamp(name):
+    """world 4, nvars 8, PERS_LOG 2: nvars + 1 - 2 = 7 exceeds the m = 6 local
+    rounds, so js = 6 and the last sharded round has one local pair"""
+    check_sharded(4, 2, [(name, 8)], [6])
+
+
+def test_sharded_staged_then_pure_in_one_context():
+    """staged large rounds, the tail from the odd round 7 (the scratch
+    accumulator slot), then a product in the same contexts: what the staged
+    rounds leave in the slot must not reach either tail"""
+    check_sharded(2, 6, [("k8d3", 12), ("prod3", 12), ("k4d7", 12), ("mixed", 12)], [7, 7, 7, 7])
+
+
 # --- switch values ---------------------------------------------------------------
 @pytest.mark.parametrize("var,value", [
     ("PERS_LOG", "0"), ("PERS_LOG", "31"), ("PERS_LOG", "-3"), ("PERS_LOG", "six"),
