@@ -30,6 +30,12 @@ namespace qg {
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// [a, a + na) and [b, b + nb) share an element (an output against its inputs)
+template <class T>
+inline bool ranges_overlap(const T* a, size_t na, const T* b, size_t nb) {
+  return a < b + nb && b < a + na;
+}
+
 // device-memory backend of the scratch arena (arena.h)
 struct HipAlloc {
   // a slot that grows is released while kernels queued on the context's

@@ -755,6 +755,27 @@ QG_DEV F29<C> shfl_xor29(const F29<C>& a, int m) {
   for (int i = 0; i < 9; i++) r.l[i] = __shfl_xor(a.l[i], m, 64);
   return r;
 }
+template <class C>
+QG_DEV F29<C> shfl_up29(const F29<C>& a, int d) {
+  F29<C> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = __shfl_up(a.l[i], d, 64);
+  return r;
+}
+template <class C>
+QG_DEV F29<C> shfl_down29(const F29<C>& a, int d) {
+  F29<C> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = __shfl_down(a.l[i], d, 64);
+  return r;
+}
+// the same for an Fr as 8 x 32 words
+QG_DEV Fr shfl_xor_fr(const Fr& a, int m) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = __shfl_xor(a.v[i], m, 64);
+  return r;
+}
 #endif
 
 // host: 2^k mod p as a plain integer (8 x 32 words)

@@ -3,7 +3,8 @@
 //   SetInclusionProof::prove      hyperplonk/src/piops/set_inclusion.rs:93-131
 // which evaluate h(x) through the expression tree for every row x, call
 // (beta + h(x)).inverse().unwrap() 2^n times, and multiply by m(x) in subset
-// mode.  Here: out[x] = m(x) / (beta + h(x)) in one HBM pass.
+// mode.  Here: out[x] = m(x) / (beta + h(x)) with ONE field inversion per
+// column, in three kernels around it (the only path).
 //
 //  * Both expressions are compiled on the host into sums of monomials
 //    (expr.h).  The coefficient of a monomial with f factors is pre-scaled by
@@ -11,22 +12,28 @@
 //    mul29 (x 2^-261) keeps both the denominator and the multiplier in
 //    arkworks form; a coefficient that comes out as 2^261 (a bare table
 //    entry) skips its multiply.
-//  * Batch inversion (Montgomery's trick) at four levels, ONE field inversion
-//    per column: phase 1 (k_logup_den) stores every row's beta + h(x) in the
-//    output buffer and multiplies each block's rows together; phase 2
-//    (k_logup_scan, one block) forms the exclusive prefix / suffix products of
-//    the block products and their total, which the host inverts (binary GCD,
-//    bingcd.h; on the device's scalar unit it took 50 us, more than the round
-//    trip); phase 3 (k_logup) gives each block 1/(its product) = 1/total x
-//    prefix x suffix, then within the block: each thread's running prefix of
-//    its LG_K rows in registers (row values in LDS), wave shuffle scans of the
-//    thread products, back-substitution.  mul29 drifts the power of two by -5
-//    per product; every output is a product tree over the inverse and all other
-//    rows, so one constant fixes all of them.
-//  * k_logup_fused (QG_LOGUP_FUSED=1) is the one-pass alternative: one
-//    binary-GCD inversion per 2048-row block, 128 instead of 192 B/row of HBM,
-//    but slower - the column is VALU-bound and the block idles while wave 0
-//    inverts (profiles/r03_logup_ab.txt).
+//  * Batch inversion (Montgomery's trick) at four levels: phase 1
+//    (k_logup_den) stores every row's beta + h(x) in the output buffer and
+//    multiplies each block's rows together; phase 2 (k_logup_scan, one block)
+//    forms the exclusive prefix / suffix products of the block products and
+//    their total, which the host inverts (binary GCD, bingcd.h; on the
+//    device's scalar unit it took 50 us, more than the round trip); phase 3
+//    (k_logup) gives each block 1/(its product) = 1/total x prefix x suffix,
+//    then within the block: each thread's running prefix of its LG_K rows in
+//    registers (row values in LDS), wave shuffle scans of the thread products,
+//    back-substitution.  96 B/row of tables read and 32 B/row written, plus
+//    the denominators' round trip through the output buffer (+64 B/row); the
+//    column is VALU-bound, not HBM-bound.
+//  * Domains: the denominators stay in arkworks' x 2^256 form (the raw table
+//    entries add in without a conversion multiply; beta + t0 + a t1 costs one
+//    multiply).  Every mul29 takes 2^261 off, so a product of j such values
+//    carries 2^(261 - 5j): with N rows the column total the host receives is
+//    tot = (prod v) 2^(261 - 5N) as a plain integer.  Each 1 / v_k of k_logup
+//    is a product tree over tinv and the column's other N - 1 rows, whatever
+//    its position, so ONE constant fixes every output: tinv = tot^-1 2^517
+//    gives every 1 / v_k as (1 / v_k) 2^261, and the multiplier's x 2^256
+//    domain then gives the output in arkworks form.  (A padding row is 2^261,
+//    mul29's identity: it is not one of the N.)
 //  * A zero denominator makes the block product zero: the kernel flags it and
 //    the call returns QG_ERR_ASSERT (the reference panics in unwrap()).
 //  * Per-block sums of the outputs feed SetInclusionProof's claimed sums
@@ -66,8 +73,14 @@ struct LgDev {
   L9 coef[2][LG_MAXM];
   uint32_t fac[LG_MAXF];
   const Fr* tab[LG_MAXT];
-  L9 kinv;    // k_logup_fused: 2^778 mod r, mul29(P^-1, kinv) = block inverse (see there)
-  L9 one256;  // 2^256 mod r: a padding row's denominator in the x 2^256 domain
+};
+
+// the scratch slot "lg_io": one call's image and its small result words
+struct LgIo {
+  LgDev img;
+  Fr res;                    // k_logup_sum: the column sum
+  uint32_t err;              // k_logup_den: some denominator was zero
+  unsigned long long first;  // k_expr_first_nonzero
 };
 
 // one expression at one row; < 2p, normalized
@@ -78,7 +91,7 @@ QG_DEV R29 lg_eval(const LgDev* __restrict__ g, int w, size_t row) {
     const uint32_t len = g->mlen[w][m], fs = g->fstart[w][m];
     uint32_t j = 0;
     R29 t;
-    if (g->unit[w][m]) {  // c 2^(base + 5f) = 2^261: the first factor as loaded (< p)
+    if (g->unit[w][m]) {  // c 2^(256 + 5f) = 2^261: the first factor as loaded (< p)
       t = to29(g->tab[g->fac[fs]][row]);
       j = 1;
     } else {
@@ -90,19 +103,21 @@ QG_DEV R29 lg_eval(const LgDev* __restrict__ g, int w, size_t row) {
   return acc;
 }
 
-QG_DEV R29 shfl_up29(const R29& a, int d) {
-  R29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = __shfl_up(a.l[i], d, 64);
-  return r;
-}
-QG_DEV R29 shfl_down29(const R29& a, int d) {
-  R29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = __shfl_down(a.l[i], d, 64);
-  return r;
-}
+// ---- block primitives: 256 threads = LG_WAVES waves -------------------------
+static constexpr int LG_WAVES = LG_BLOCK / 64;
 
+// nine limbs to / from one LDS row (a wave's total or partial sum)
+QG_DEV R29 lds_get9(const uint32_t* row) {
+  R29 v;
+#pragma unroll
+  for (int i = 0; i < 9; i++) v.l[i] = row[i];
+  return v;
+}
+QG_DEV void lds_put9(uint32_t* row, const R29& v) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) row[i] = v.l[i];
+}
+// the same in the [k][limb][thread] layout of a block's LG_K x LG_BLOCK rows
 QG_DEV R29 lds_row(const uint32_t* vs, int k, int tid) {
   R29 v;
 #pragma unroll
@@ -112,6 +127,61 @@ QG_DEV R29 lds_row(const uint32_t* vs, int k, int tid) {
 QG_DEV void lds_put(uint32_t* vs, int k, int tid, const R29& v) {
 #pragma unroll
   for (int i = 0; i < 9; i++) vs[(k * 9 + i) * LG_BLOCK + tid] = v.l[i];
+}
+
+// Sum over the block of one value < 2p per thread: a wave xor-tree, then the
+// LG_WAVES wave partials through LDS.  Thread 0 returns the sum (< 2p).
+QG_DEV R29 block_sum29(R29 acc, uint32_t (*wsum)[9]) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int d = 32; d >= 1; d >>= 1) acc = red2p29(add29(acc, shfl_xor29(acc, d)));
+  if (lane == 0) lds_put9(wsum[wv], acc);
+  __syncthreads();
+  R29 s = R29::zero();
+  if (tid == 0)
+#pragma unroll
+    for (int w = 0; w < LG_WAVES; w++) s = red2p29(add29(s, lds_get9(wsum[w])));
+  return s;
+}
+
+// Exclusive prefix (ep) and suffix (es) products over the block of one value T
+// per thread: inclusive wave shuffle scans in both directions, then the fix-up
+// from the wave totals, which stay in wtot.  PAIR: the two scans' products as
+// one interleaved pair (field29.h mul29tn), which is k_logup's form, instead
+// of two mul29; the same arithmetic.  k_logup_scan, a single block at one wave
+// per SIMD, is slower with the pair (40.6 against 31.2 us at 2^22 rows,
+// profiles/r13_logup_one_path.txt), so each kernel keeps the form it had.
+// tot given: thread 0 multiplies the wave totals into it as well, in the
+// fix-up loop (a loop of its own after it the compiler moves to the scalar
+// unit, which is several times slower at these products).
+template <bool PAIR>
+QG_DEV void block_scan_prod29(const R29& T, uint32_t (*wtot)[9], R29& ep, R29& es,
+                              R29* tot = nullptr) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const R29 one = R29::from_l9(F29P<FrP>::ONE);
+  R29 ip = T, is = T;  // inclusive in-wave prefix / suffix
+  for (int d = 1; d < 64; d <<= 1) {
+    R29 x2[2] = {shfl_up29(ip, d), is}, y2[2] = {ip, shfl_down29(is, d)};
+    if constexpr (PAIR) {
+      mul29tn<FrP, 2>(x2, y2, x2);
+    } else {
+      x2[0] = mul29(x2[0], y2[0]);
+      x2[1] = mul29(x2[1], y2[1]);
+    }
+    if (lane >= d) ip = x2[0];
+    if (lane + d < 64) is = x2[1];
+  }
+  if (lane == 63) lds_put9(wtot[wv], ip);
+  ep = shfl_up29(ip, 1);
+  es = shfl_down29(is, 1);
+  if (lane == 0) ep = one;
+  if (lane == 63) es = one;
+  __syncthreads();
+  for (int w = 0; w < LG_WAVES; w++) {  // wave products straight from LDS (uniform loop)
+    const R29 t = lds_get9(wtot[w]);
+    if (w < wv) ep = mul29(ep, t);
+    if (w > wv) es = mul29(es, t);
+    if (tot && tid == 0) *tot = mul29(*tot, t);
+  }
 }
 
 // Phase 1: per row v = beta + h(row) (x 2^256), stored (< p) into the output
@@ -144,18 +214,11 @@ __global__ __launch_bounds__(LG_DEN_BLOCK) void k_logup_den(const LgDev* __restr
     const R29 o = shfl_down29(T, d);
     if (lane + d < 64) T = mul29(T, o);
   }
-  if (lane == 0)
-#pragma unroll
-    for (int i = 0; i < 9; i++) wtot[wv][i] = T.l[i];
+  if (lane == 0) lds_put9(wtot[wv], T);
   __syncthreads();
   if (tid == 0) {
     R29 p = one;
-    for (int w = 0; w < LG_DEN_BLOCK / 64; w++) {
-      R29 t;
-#pragma unroll
-      for (int i = 0; i < 9; i++) t.l[i] = wtot[w][i];
-      p = mul29(p, t);
-    }
+    for (int w = 0; w < LG_DEN_BLOCK / 64; w++) p = mul29(p, lds_get9(wtot[w]));
     bprod[blockIdx.x] = from29(canon29(p));
   }
 }
@@ -166,41 +229,19 @@ __global__ __launch_bounds__(LG_DEN_BLOCK) void k_logup_den(const LgDev* __restr
 // segment products and the four wave totals: ~20 dependent products per
 // thread at one wave per SIMD (a 1024-thread Hillis-Steele scan through LDS
 // took 49 us at 2^22 rows).
-static constexpr int LG_SCAN = 256;
-__global__ __launch_bounds__(LG_SCAN) void k_logup_scan(const Fr* __restrict__ bprod, uint32_t nb,
-                                                        Fr* __restrict__ pre, Fr* __restrict__ suf,
-                                                        Fr* __restrict__ total) {
-  __shared__ uint32_t wtot[LG_SCAN / 64][9];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const uint32_t per = (nb + LG_SCAN - 1) / LG_SCAN;
+__global__ __launch_bounds__(LG_BLOCK) void k_logup_scan(const Fr* __restrict__ bprod, uint32_t nb,
+                                                         Fr* __restrict__ pre, Fr* __restrict__ suf,
+                                                         Fr* __restrict__ total) {
+  __shared__ uint32_t wtot[LG_WAVES][9];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t per = (nb + LG_BLOCK - 1) / LG_BLOCK;
   const uint32_t lo = tid * per < nb ? tid * per : nb, hi = lo + per < nb ? lo + per : nb;
   const R29 one = R29::from_l9(F29P<FrP>::ONE);
   R29 tp = one;  // product of this thread's segment
   for (uint32_t i = lo; i < hi; i++) tp = mul29(tp, to29(bprod[i]));
-  R29 ip = tp, is = tp;  // inclusive in-wave prefix / suffix
-  for (int d = 1; d < 64; d <<= 1) {
-    const R29 a = shfl_up29(ip, d), b = shfl_down29(is, d);
-    if (lane >= (uint32_t)d) ip = mul29(a, ip);
-    if (lane + d < 64) is = mul29(is, b);
-  }
-  if (lane == 63)
-#pragma unroll
-    for (int i = 0; i < 9; i++) wtot[wv][i] = ip.l[i];
-  R29 ep = shfl_up29(ip, 1), es = shfl_down29(is, 1);
-  if (lane == 0) ep = one;
-  if (lane == 63) es = one;
-  __syncthreads();
-  R29 tot = one;
-  for (uint32_t w = 0; w < LG_SCAN / 64; w++) {
-    R29 t;
-#pragma unroll
-    for (int i = 0; i < 9; i++) t.l[i] = wtot[w][i];
-    if (w < wv) ep = mul29(ep, t);
-    if (w > wv) es = mul29(es, t);
-    if (tid == 0) tot = mul29(tot, t);
-  }
+  R29 rp, rs, tot = one;
+  block_scan_prod29<false>(tp, wtot, rp, rs, &tot);
   if (tid == 0) *total = from29(canon29(tot));
-  R29 rp = ep, rs = es;
   for (uint32_t k = 0; k < hi - lo; k++) {  // prefix up, suffix down, interleaved
     const uint32_t i = lo + k, j = hi - 1 - k;
     pre[i] = from29(canon29(rp));
@@ -211,8 +252,8 @@ __global__ __launch_bounds__(LG_SCAN) void k_logup_scan(const Fr* __restrict__ b
 }
 
 // Phase 3: 1/v for every row of the block from inv(total) x prefix x suffix of
-// the block products (block inverse), then the thread-level Montgomery trick
-// as in one pass: the rows' v values come back from the output buffer.
+// the block products (block inverse), then the thread-level Montgomery trick;
+// the rows' v values come back from the output buffer.
 __global__ __launch_bounds__(LG_BLOCK) void k_logup(const LgDev* __restrict__ g, size_t n,
                                                     Fr* __restrict__ out,
                                                     const Fr* __restrict__ pre,
@@ -220,18 +261,16 @@ __global__ __launch_bounds__(LG_BLOCK) void k_logup(const LgDev* __restrict__ g,
                                                     const Fr* __restrict__ tinv,
                                                     Fr* __restrict__ bsum) {
   __shared__ uint32_t vs[LG_K * 9 * LG_BLOCK];  // row denominators, [k][limb][thread]
-  __shared__ uint32_t wtot[LG_BLOCK / 64][9];
-  __shared__ uint32_t wsum[LG_BLOCK / 64][9];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ uint32_t wtot[LG_WAVES][9];
+  __shared__ uint32_t wsum[LG_WAVES][9];
+  const int tid = threadIdx.x;
   const size_t base = (size_t)blockIdx.x * LG_ROWS + tid;
-  const R29 one = R29::from_l9(F29P<FrP>::ONE);
 
-  // 1. denominators back from HBM to LDS, then the running prefix of this thread's rows
+  // 1. denominators back from HBM to LDS (a padding row is mul29's identity),
+  // then the running prefix of this thread's rows
   for (int k = 0; k < LG_K; k++) {
     const size_t row = base + (size_t)k * LG_BLOCK;
-    const R29 v = row < n ? to29(out[row]) : one;
-#pragma unroll
-    for (int i = 0; i < 9; i++) vs[(k * 9 + i) * LG_BLOCK + tid] = v.l[i];
+    lds_put(vs, k, tid, row < n ? to29(out[row]) : R29::from_l9(F29P<FrP>::ONE));
   }
   static_assert(LG_K == 8, "prefix chain is written out for 8 rows");
   R29 pre_r[LG_K];
@@ -243,34 +282,13 @@ __global__ __launch_bounds__(LG_BLOCK) void k_logup(const LgDev* __restrict__ g,
   pre_r[5] = mul29(pre_r[4], lds_row(vs, 5, tid));
   pre_r[6] = mul29(pre_r[5], lds_row(vs, 6, tid));
   pre_r[7] = mul29(pre_r[6], lds_row(vs, 7, tid));
-  const R29 T = pre_r[LG_K - 1];
 
-  // 2. exclusive prefix / suffix products of T across the block (the two
-  // scans' products as one interleaved pair, field29.h mul29tn)
-  R29 ip = T, is = T;  // inclusive in-wave prefix / suffix
-  for (int d = 1; d < 64; d <<= 1) {
-    R29 x2[2] = {shfl_up29(ip, d), is}, y2[2] = {ip, shfl_down29(is, d)};
-    mul29tn<FrP, 2>(x2, y2, x2);
-    if (lane >= d) ip = x2[0];
-    if (lane + d < 64) is = x2[1];
-  }
-  if (lane == 63)
-#pragma unroll
-    for (int i = 0; i < 9; i++) wtot[wv][i] = ip.l[i];
-  R29 ep = shfl_up29(ip, 1), es = shfl_down29(is, 1);
-  if (lane == 0) ep = one;
-  if (lane == 63) es = one;
-  __syncthreads();
-  for (int w = 0; w < LG_BLOCK / 64; w++) {  // wave products straight from LDS (uniform loop)
-    R29 t;
-#pragma unroll
-    for (int i = 0; i < 9; i++) t.l[i] = wtot[w][i];
-    if (w < wv) ep = mul29(ep, t);
-    if (w > wv) es = mul29(es, t);
-  }
+  // 2. exclusive prefix / suffix products of the thread products across the block
+  R29 ep, es;
+  block_scan_prod29<true>(pre_r[LG_K - 1], wtot, ep, es);
   // 1 / (block product) = 1 / total x (other blocks' products)
   const R29 binv = mul29(mul29(to29(*tinv), to29(pre[blockIdx.x])), to29(suf[blockIdx.x]));
-  R29 inv_run = mul29(mul29(binv, ep), es);  // 1 / T
+  R29 inv_run = mul29(mul29(binv, ep), es);  // 1 / (this thread's product)
 
   // 3. back-substitution: 1 / v_k overwrites v_k in LDS (own slots only);
   // the output product and the next running inverse as one interleaved pair
@@ -305,232 +323,18 @@ __global__ __launch_bounds__(LG_BLOCK) void k_logup(const LgDev* __restrict__ g,
       acc = red2p29(add29(acc, y));
     }
   }
-  // block sum (values < 2p; a wave tree then 4 wave partials)
-  for (int d = 32; d >= 1; d >>= 1) {
-    R29 o;
-#pragma unroll
-    for (int i = 0; i < 9; i++) o.l[i] = __shfl_xor(acc.l[i], d, 64);
-    acc = red2p29(add29(acc, o));
-  }
-  if (lane == 0)
-#pragma unroll
-    for (int i = 0; i < 9; i++) wsum[wv][i] = acc.l[i];
-  __syncthreads();
-  if (tid == 0) {
-    R29 s = R29::zero();
-#pragma unroll
-    for (int w = 0; w < LG_BLOCK / 64; w++) {
-      R29 t;
-#pragma unroll
-      for (int i = 0; i < 9; i++) t.l[i] = wsum[w][i];
-      s = red2p29(add29(s, t));
-    }
-    bsum[blockIdx.x] = from29(canon29(s));
-  }
-}
-
-// One pass (default): k_logup with the denominators evaluated from the tables
-// instead of re-read, and 1 / (block product) from ONE binary-GCD inversion
-// per 2048-row block (csrc/bingcd.h, wave 0 on the scalar unit) instead of a
-// column-wide product inverted on the host: 96 B/row read + 32 B/row written,
-// no scan kernel, no host round trip.
-// Domains: the denominators stay in arkworks' x 2^256 form (the raw table
-// entries add in without a conversion multiply; beta + t0 + a t1 costs one
-// multiply).  Every mul29 takes 2^261 off, so a product of m such values
-// carries 2^(261 - 5m); each 1 / v_k below is a product tree over binv and the
-// block's other N - 1 rows, whatever its position, so with the block product P
-// = (prod v) 2^(261 - 5N) inverted as a plain integer and binv = mul29(P^-1,
-// 2^778) every 1 / v_k comes out as (1 / v_k) 2^261 - the multiplier's domain
-// then gives the output in arkworks form.  (Padding rows are 2^256, i.e. 1.)
-__global__ __launch_bounds__(LG_BLOCK) void k_logup_fused(const LgDev* __restrict__ g, size_t n,
-                                                          Fr* __restrict__ out, Fr* __restrict__ bsum,
-                                                          uint32_t* __restrict__ err) {
-  __shared__ uint32_t vs[LG_K * 9 * LG_BLOCK];  // row denominators, [k][limb][thread]
-  __shared__ uint32_t wtot[LG_BLOCK / 64][9];
-  __shared__ uint32_t wsum[LG_BLOCK / 64][9];
-  __shared__ uint32_t binv_sh[9];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const size_t base = (size_t)blockIdx.x * LG_ROWS + tid;
-  const R29 one = R29::from_l9(F29P<FrP>::ONE);
-
-  // 1. denominators (x 2^261) into LDS, the running prefix of this thread's rows
-  bool zero = false;
-  for (int k = 0; k < LG_K; k++) {
-    const size_t row = base + (size_t)k * LG_BLOCK;
-    R29 v = R29::from_l9(g->one256);
-    if (row < n) {
-      v = canon29(lg_eval(g, 0, row));
-      zero |= is_zero29(v);
-    }
-    lds_put(vs, k, tid, v);
-  }
-  if (zero) atomicOr(err, 1u);
-  static_assert(LG_K == 8, "prefix chain is written out for 8 rows");
-  R29 pre_r[LG_K];
-  pre_r[0] = lds_row(vs, 0, tid);
-  pre_r[1] = mul29(pre_r[0], lds_row(vs, 1, tid));
-  pre_r[2] = mul29(pre_r[1], lds_row(vs, 2, tid));
-  pre_r[3] = mul29(pre_r[2], lds_row(vs, 3, tid));
-  pre_r[4] = mul29(pre_r[3], lds_row(vs, 4, tid));
-  pre_r[5] = mul29(pre_r[4], lds_row(vs, 5, tid));
-  pre_r[6] = mul29(pre_r[5], lds_row(vs, 6, tid));
-  pre_r[7] = mul29(pre_r[6], lds_row(vs, 7, tid));
-  const R29 T = pre_r[LG_K - 1];
-
-  // 2. exclusive prefix / suffix products of T across the block
-  R29 ip = T, is = T;
-  for (int d = 1; d < 64; d <<= 1) {
-    const R29 a = shfl_up29(ip, d), b = shfl_down29(is, d);
-    if (lane >= d) ip = mul29(a, ip);
-    if (lane + d < 64) is = mul29(is, b);
-  }
-  if (lane == 63)
-#pragma unroll
-    for (int i = 0; i < 9; i++) wtot[wv][i] = ip.l[i];
-  R29 ep = shfl_up29(ip, 1), es = shfl_down29(is, 1);
-  if (lane == 0) ep = one;
-  if (lane == 63) es = one;
-  __syncthreads();
-  if (wv == 0) {  // block inverse: one binary-GCD inversion, wave-uniform (scalar unit)
-    R29 P = one;
-    for (int w = 0; w < LG_BLOCK / 64; w++) {
-      R29 t;
-#pragma unroll
-      for (int i = 0; i < 9; i++) t.l[i] = wtot[w][i];
-      P = mul29(P, t);
-    }
-    Fr pc = from29(canon29(P));
-#pragma unroll
-    for (int i = 0; i < 8; i++) pc.v[i] = __builtin_amdgcn_readfirstlane(pc.v[i]);
-    const Fr ipl = inv_bingcd<FrP>(pc);  // 0 if some denominator was 0
-    const R29 b = mul29(to29(ipl), R29::from_l9(g->kinv));
-    if (lane == 0)
-#pragma unroll
-      for (int i = 0; i < 9; i++) binv_sh[i] = b.l[i];
-  }
-  for (int w = 0; w < LG_BLOCK / 64; w++) {  // wave products straight from LDS (uniform loop)
-    R29 t;
-#pragma unroll
-    for (int i = 0; i < 9; i++) t.l[i] = wtot[w][i];
-    if (w < wv) ep = mul29(ep, t);
-    if (w > wv) es = mul29(es, t);
-  }
-  __syncthreads();
-  R29 binv;
-#pragma unroll
-  for (int i = 0; i < 9; i++) binv.l[i] = binv_sh[i];
-  R29 inv_run = mul29(mul29(binv, ep), es);  // 1 / T
-
-  // 3. back-substitution: 1 / v_k overwrites v_k in LDS (own slots only)
-#define LG_BACK(k)                                        \
-  {                                                       \
-    const R29 x = mul29(inv_run, pre_r[k - 1]);           \
-    inv_run = mul29(inv_run, lds_row(vs, k, tid));        \
-    lds_put(vs, k, tid, x);                               \
-  }
-  LG_BACK(7) LG_BACK(6) LG_BACK(5) LG_BACK(4) LG_BACK(3) LG_BACK(2) LG_BACK(1)
-#undef LG_BACK
-  lds_put(vs, 0, tid, inv_run);
-
-  // 4. multiplier, store, block sum
-  R29 acc = R29::zero();
-  for (int k = 0; k < LG_K; k++) {
-    const size_t row = base + (size_t)k * LG_BLOCK;
-    if (row >= n) break;
-    const R29 x = lds_row(vs, k, tid);
-    const R29 m = lg_eval(g, 1, row);  // M x 2^256
-    const R29 y = canon29(mul29(x, m));
-    out[row] = from29(y);
-    acc = red2p29(add29(acc, y));
-  }
-  for (int d = 32; d >= 1; d >>= 1) {
-    R29 o;
-#pragma unroll
-    for (int i = 0; i < 9; i++) o.l[i] = __shfl_xor(acc.l[i], d, 64);
-    acc = red2p29(add29(acc, o));
-  }
-  if (lane == 0)
-#pragma unroll
-    for (int i = 0; i < 9; i++) wsum[wv][i] = acc.l[i];
-  __syncthreads();
-  if (tid == 0) {
-    R29 s = R29::zero();
-#pragma unroll
-    for (int w = 0; w < LG_BLOCK / 64; w++) {
-      R29 t;
-#pragma unroll
-      for (int i = 0; i < 9; i++) t.l[i] = wsum[w][i];
-      s = red2p29(add29(s, t));
-    }
-    bsum[blockIdx.x] = from29(canon29(s));
-  }
+  const R29 s = block_sum29(acc, wsum);
+  if (tid == 0) bsum[blockIdx.x] = from29(canon29(s));
 }
 
 // sum of the per-block sums (one block)
-__global__ __launch_bounds__(256) void k_logup_sum(const Fr* __restrict__ bsum, uint32_t nb,
-                                                   Fr* __restrict__ res) {
-  __shared__ uint32_t ws[4][9];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(LG_BLOCK) void k_logup_sum(const Fr* __restrict__ bsum, uint32_t nb,
+                                                        Fr* __restrict__ res) {
+  __shared__ uint32_t wsum[LG_WAVES][9];
   R29 acc = R29::zero();
-  for (uint32_t i = tid; i < nb; i += 256) acc = red2p29(add29(acc, to29(bsum[i])));
-  for (int d = 32; d >= 1; d >>= 1) {
-    R29 o;
-#pragma unroll
-    for (int i = 0; i < 9; i++) o.l[i] = __shfl_xor(acc.l[i], d, 64);
-    acc = red2p29(add29(acc, o));
-  }
-  if (lane == 0)
-#pragma unroll
-    for (int i = 0; i < 9; i++) ws[wv][i] = acc.l[i];
-  __syncthreads();
-  if (tid == 0) {
-    R29 s = R29::zero();
-    for (int w = 0; w < 4; w++) {
-      R29 t;
-#pragma unroll
-      for (int i = 0; i < 9; i++) t.l[i] = ws[w][i];
-      s = red2p29(add29(s, t));
-    }
-    *res = from29(canon29(s));
-  }
-}
-
-// qg_selftest_inverse's device path: one inversion per thread
-template <class C>
-__global__ void k_inv_selftest(const Fp<C>* __restrict__ in, Fp<C>* __restrict__ out, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = inv_bingcd<C>(in[i]);
-}
-
-template <class C>
-static void inv_selftest(qg_ctx* ctx, bool dev, const uint64_t* in, uint64_t* out, size_t n) {
-  std::vector<Fp<C>> h(n);
-  for (size_t i = 0; i < n; i++)
-    for (int l = 0; l < 4; l++) {
-      h[i].v[2 * l] = (uint32_t)in[4 * i + l];
-      h[i].v[2 * l + 1] = (uint32_t)(in[4 * i + l] >> 32);
-    }
-  for (size_t i = 0; i < n; i++) {
-    Fp<C> t = h[i];
-    reduce_full<C>(t.v);
-    QG_CHECK(t == h[i], QG_ERR_INVALID, "inverse self-test input not canonical");
-  }
-  if (dev) {
-    QG_CHECK(ctx, QG_ERR_INVALID, "device self-test needs a context");
-    QG_HIP(hipSetDevice(ctx->device));
-    Fp<C>* d = ctx->scratch_as<Fp<C>>("inv_selftest", 2 * n + 2);
-    QG_HIP(hipMemcpyAsync(d, h.data(), n * sizeof(Fp<C>), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_inv_selftest<C>, dim3(div_up(n ? n : 1, 64)), dim3(64), 0, ctx->stream, d, d + n,
-                       n);
-    QG_LAUNCH_CHECK();
-    QG_HIP(hipMemcpyAsync(h.data(), d + n, n * sizeof(Fp<C>), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-  } else {
-    for (size_t i = 0; i < n; i++) h[i] = inv_bingcd<C>(h[i]);
-  }
-  for (size_t i = 0; i < n; i++)
-    for (int l = 0; l < 4; l++)
-      out[4 * i + l] = (uint64_t)h[i].v[2 * l] | ((uint64_t)h[i].v[2 * l + 1] << 32);
+  for (uint32_t i = threadIdx.x; i < nb; i += LG_BLOCK) acc = red2p29(add29(acc, to29(bsum[i])));
+  const R29 s = block_sum29(acc, wsum);
+  if (threadIdx.x == 0) *res = from29(canon29(s));
 }
 
 // first row whose expression value (slot 0, no beta) is nonzero; atomicMin
@@ -561,10 +365,11 @@ static L9 lg_l9(const Fr& plain) {
   return r;
 }
 
-// compile one expression into slot w of the image; `add_const` (Montgomery)
-// is added to the constant monomial; `base` = 261 or 256 (output scale)
+// compile one expression into slot w of the image at scale 256 + 5f (the value
+// comes out in arkworks form, x 2^256); `add_const` (Montgomery) is added to
+// the constant monomial when `with_const`
 static void lg_compile(LgDev& d, int w, const SopProgram& sp, const Fr& add_const, bool with_const,
-                       uint32_t base, std::vector<uint32_t>& tables_used, uint32_t& nfac) {
+                       std::vector<uint32_t>& tables_used, uint32_t& nfac) {
   std::vector<uint32_t> mlen = sp.mono_len;
   std::vector<Fr> coeff = sp.coeff;
   std::vector<std::vector<uint32_t>> facs;
@@ -603,10 +408,72 @@ static void lg_compile(LgDev& d, int w, const SopProgram& sp, const Fr& add_cons
       }
       d.fac[nfac++] = slot;
     }
-    const Fr cf = lg_plain_mul(from_mont(coeff[m]), pow2_mod_plain<FrP>(base + 5 * mlen[m]));
+    const Fr cf = lg_plain_mul(from_mont(coeff[m]), pow2_mod_plain<FrP>(256 + 5 * mlen[m]));
     d.coef[w][m] = lg_l9(cf);
     d.unit[w][m] = mlen[m] >= 1 && cf == pow2_mod_plain<FrP>(261) ? 1u : 0u;
   }
+}
+
+// an expression as the C-ABI passes it; empty: none given
+struct LgExpr {
+  const qg_expr_op* prog = nullptr;
+  size_t len = 0;
+  const uint64_t* consts = nullptr;
+  size_t nconsts = 0;
+  explicit operator bool() const { return prog && len; }
+};
+
+// The one setup of every kernel here: compile into `img` (the caller's, alive
+// until the call's sync), bind the tables the expressions use, upload into the
+// "lg_io" slot.  beta == nullptr: slot 0 = h alone (k_expr_column,
+// k_expr_first_nonzero).  Otherwise the Logup pair: slot 0 = beta + h and slot
+// 1 = m, or the constant 1 when m is empty.  Only a table that is used has to
+// be there.  QG_ERR_UNSUPPORTED: outside the compiled envelope (128 monomials,
+// 512 factors, 64 tables).
+static LgIo* lg_setup(qg_ctx* ctx, LgDev& img, uint32_t ntables, const std::vector<const Fr*>& tabs,
+                      const LgExpr& h, const uint64_t* beta, const LgExpr& m) {
+  memset(&img, 0, sizeof(img));
+  std::vector<uint32_t> used;
+  uint32_t nfac = 0;
+  lg_compile(img, 0, compile_program(h.prog, h.len, h.consts, h.nconsts, ntables),
+             beta ? fr_import(beta) : Fr::zero(), beta != nullptr, used, nfac);
+  if (beta && m)
+    lg_compile(img, 1, compile_program(m.prog, m.len, m.consts, m.nconsts, ntables), Fr::zero(),
+               false, used, nfac);
+  else if (beta)
+    lg_compile(img, 1, SopProgram{}, Fr::one(), true, used, nfac);
+  for (size_t s = 0; s < used.size(); s++) {
+    QG_CHECK(tabs[used[s]], QG_ERR_INVALID, "table buffer missing or too short");
+    img.tab[s] = tabs[used[s]];
+  }
+  QG_HIP(hipSetDevice(ctx->device));
+  LgIo* io = ctx->scratch_as<LgIo>("lg_io", 1);
+  QG_HIP(hipMemcpyAsync(&io->img, &img, sizeof(img), hipMemcpyHostToDevice, ctx->stream));
+  return io;
+}
+
+// lg_setup, and for expressions outside the compiled envelope (it answered
+// QG_ERR_UNSUPPORTED) the generic interpreter: h (and m) are materialised with
+// expr_table_device, and the image runs over those columns with h = Input(0),
+// m = Input(1).  Every table has to be there then.
+static LgIo* lg_setup_any(qg_ctx* ctx, LgDev& img, size_t n, uint32_t ntables,
+                          const std::vector<const Fr*>& tabs, const LgExpr& h, const uint64_t* beta,
+                          const LgExpr& m) {
+  try {
+    return lg_setup(ctx, img, ntables, tabs, h, beta, m);
+  } catch (const Error& e) {
+    if (e.code != QG_ERR_UNSUPPORTED) throw;
+  }
+  for (const Fr* t : tabs) QG_CHECK(t, QG_ERR_INVALID, "table buffer missing or too short");
+  const bool has_m = beta && m;
+  Fr* ev = ctx->scratch_as<Fr>("lg_gen_tabs", n * (has_m ? 2 : 1));
+  expr_table_device(ctx, n, ntables, tabs, h.prog, h.len, h.consts, h.nconsts, ev);
+  if (has_m) expr_table_device(ctx, n, ntables, tabs, m.prog, m.len, m.consts, m.nconsts, ev + n);
+  static const qg_expr_op in0[1] = {{QG_OP_INPUT, 0}}, in1[1] = {{QG_OP_INPUT, 1}};
+  std::vector<const Fr*> cols{ev};
+  if (has_m) cols.push_back(ev + n);
+  return lg_setup(ctx, img, (uint32_t)cols.size(), cols, LgExpr{in0, 1}, beta,
+                  has_m ? LgExpr{in1, 1} : LgExpr{});
 }
 
 static size_t lg_local_size(const qg_ctx* ctx, uint32_t nvars) {
@@ -616,15 +483,6 @@ static size_t lg_local_size(const qg_ctx* ctx, uint32_t nvars) {
   QG_CHECK(nvars >= lw, QG_ERR_INVALID, "nvars must be at least log2(world)");
   QG_CHECK(nvars < 40, QG_ERR_INVALID, "nvars too large");
   return (size_t)1 << (nvars - lw);
-}
-
-// the 3-kernel path (default) or the one-pass kernel (QG_LOGUP_FUSED=1): one
-// pass moves 128 instead of 192 B/row but idles the block during its
-// inversion; the column is VALU-bound, so the 3 kernels are faster
-// (profiles/r03_logup_ab.txt)
-static bool logup_fused() {
-  const char* ov = getenv("QG_LOGUP_FUSED");
-  return ov && atoi(ov) != 0;
 }
 
 // the column sum (d_res) and the zero-denominator flag (d_err) of this rank,
@@ -668,49 +526,13 @@ static Fr logup_total(qg_ctx* ctx, const Fr* d_res, const uint32_t* d_err) {
 // out[x] = m(x) / (beta + h(x)) over this rank's rows; returns sum_x out[x]
 // over all ranks (Fr, i.e. arkworks Montgomery words)
 static Fr logup_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const std::vector<const Fr*>& tabs,
-                    const qg_expr_op* hp, size_t hl, const uint64_t* hc, size_t hn,
-                    const qg_expr_op* mp, size_t ml, const uint64_t* mc, size_t mn,
-                    const uint64_t beta[4], Fr* d_out) {
-  QG_CHECK(hp && hl, QG_ERR_INVALID, "missing h expression");
+                    const LgExpr& h, const LgExpr& m, const uint64_t beta[4], Fr* d_out) {
+  QG_CHECK(h, QG_ERR_INVALID, "missing h expression");
   const size_t n = lg_local_size(ctx, nvars);
   LgDev img;
-  memset(&img, 0, sizeof(img));
-  std::vector<uint32_t> used;
-  uint32_t nfac = 0;
-  try {
-    const SopProgram sh = compile_program(hp, hl, hc, hn, ntables);
-    // denominators in arkworks' x 2^256 form (raw t0 adds without a multiply;
-    // the mul29 drift is one fixed power of two per output, see k_logup_fused)
-    lg_compile(img, 0, sh, fr_import(beta), true, 256, used, nfac);
-    if (mp && ml) {
-      const SopProgram sm = compile_program(mp, ml, mc, mn, ntables);
-      lg_compile(img, 1, sm, Fr::zero(), false, 256, used, nfac);
-    } else {
-      SopProgram one;
-      lg_compile(img, 1, one, Fr::one(), true, 256, used, nfac);
-    }
-  } catch (const Error& e) {
-    if (e.code != QG_ERR_UNSUPPORTED) throw;
-    // outside the compiled envelope (more than 128 monomials, 512 factors or
-    // 64 tables): materialise h (and m) with the generic interpreter, then run
-    // the column over those tables with h = Input(0), m = Input(1)
-    const bool has_m = mp && ml;
-    Fr* ev = ctx->scratch_as<Fr>("lg_gen_tabs", n * (has_m ? 2 : 1));
-    expr_table_device(ctx, n, ntables, tabs, hp, hl, hc, hn, ev);
-    if (has_m) expr_table_device(ctx, n, ntables, tabs, mp, ml, mc, mn, ev + n);
-    const qg_expr_op h0[1] = {{QG_OP_INPUT, 0}}, m1[1] = {{QG_OP_INPUT, 1}};
-    std::vector<const Fr*> t2{ev};
-    if (has_m) t2.push_back(ev + n);
-    return logup_run(ctx, nvars, (uint32_t)t2.size(), t2, h0, 1, nullptr, 0, has_m ? m1 : nullptr,
-                     has_m ? 1 : 0, nullptr, 0, beta, d_out);
-  }
-  for (size_t s = 0; s < used.size(); s++) img.tab[s] = tabs[used[s]];
+  LgIo* io = lg_setup_any(ctx, img, n, ntables, tabs, h, beta, m);
 
   const uint32_t nb = div_up(n, LG_ROWS);
-  uint8_t* io = ctx->scratch_as<uint8_t>("lg_io", sizeof(LgDev) + 64);
-  LgDev* d_img = reinterpret_cast<LgDev*>(io);
-  Fr* d_res = reinterpret_cast<Fr*>(io + sizeof(LgDev));
-  uint32_t* d_err = reinterpret_cast<uint32_t*>(io + sizeof(LgDev) + 32);
   Fr* d_bsum = ctx->scratch_as<Fr>("lg_bsum", nb);
   // block products, their exclusive prefix / suffix products, total, 1/total
   Fr* d_bp = ctx->scratch_as<Fr>("lg_bprod", 3 * (size_t)nb + 2);
@@ -718,21 +540,7 @@ static Fr logup_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const std::ve
   Fr* d_suf = d_pre + nb;
   Fr* d_tot = d_suf + nb;
   Fr* d_tinv = d_tot + 1;
-  img.kinv = lg_l9(pow2_mod_plain<FrP>(778));
-  img.one256 = lg_l9(pow2_mod_plain<FrP>(256));
-  QG_HIP(hipMemcpyAsync(d_img, &img, sizeof(img), hipMemcpyHostToDevice, ctx->stream));
-  QG_HIP(hipMemsetAsync(d_err, 0, 4, ctx->stream));
-  if (logup_fused()) {
-    {
-      QgTimed tm(ctx, "logup_column");
-      hipLaunchKernelGGL(k_logup_fused, dim3(nb), dim3(LG_BLOCK), 0, ctx->stream, d_img, n, d_out,
-                         d_bsum, d_err);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_logup_sum, dim3(1), dim3(256), 0, ctx->stream, d_bsum, nb, d_res);
-      QG_LAUNCH_CHECK();
-    }
-    return logup_total(ctx, d_res, d_err);
-  }
+  QG_HIP(hipMemsetAsync(&io->err, 0, 4, ctx->stream));
   struct {
     Fr tot;
     uint32_t err;
@@ -740,20 +548,18 @@ static Fr logup_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const std::ve
   {
     // kernel time only: the timed region closes before the D2H copies and the sync
     QgTimed tm(ctx, "logup_column");
-    hipLaunchKernelGGL(k_logup_den, dim3(nb), dim3(LG_DEN_BLOCK), 0, ctx->stream, d_img, n, d_out,
-                       d_bp, d_err);
+    hipLaunchKernelGGL(k_logup_den, dim3(nb), dim3(LG_DEN_BLOCK), 0, ctx->stream, &io->img, n, d_out,
+                       d_bp, &io->err);
     QG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_logup_scan, dim3(1), dim3(LG_SCAN), 0, ctx->stream, d_bp, nb, d_pre,
+    hipLaunchKernelGGL(k_logup_scan, dim3(1), dim3(LG_BLOCK), 0, ctx->stream, d_bp, nb, d_pre,
                        d_suf, d_tot);
     QG_LAUNCH_CHECK();
   }
   QG_HIP(hipMemcpyAsync(&ht.tot, d_tot, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  QG_HIP(hipMemcpyAsync(&ht.err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+  QG_HIP(hipMemcpyAsync(&ht.err, &io->err, 4, hipMemcpyDeviceToHost, ctx->stream));
   ctx->sync();
   // one inversion for the whole column, of the product of every denominator:
-  // with N rows in the x 2^256 domain, tot = P 2^(261 - 5N) (plain); each
-  // 1 / v_k of k_logup is a product tree over tinv and the other N - 1 rows,
-  // so tinv = tot^-1 2^517 gives every 1 / v_k as (1 / v_k) 2^261
+  // tinv = tot^-1 2^517 (the domains: top of the file)
   Fr tinv = Fr::zero();
   if (!ht.err) {
     const Fr tot_plain = ht.tot;  // nonzero: no denominator was zero
@@ -763,50 +569,64 @@ static Fr logup_run(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const std::ve
     if (!(lg_plain_mul(tot_plain, inv_plain) == from_mont(Fr::one())))
       inv_plain = from_mont(finv(to_mont(tot_plain)));
     tinv = lg_plain_mul(inv_plain, pow2_mod_plain<FrP>(517));
-  }
-  if (!ht.err) {
     QG_HIP(hipMemcpyAsync(d_tinv, &tinv, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     QgTimed tm(ctx, "logup_column");
-    hipLaunchKernelGGL(k_logup, dim3(nb), dim3(LG_BLOCK), 0, ctx->stream, d_img, n, d_out, d_pre,
+    hipLaunchKernelGGL(k_logup, dim3(nb), dim3(LG_BLOCK), 0, ctx->stream, &io->img, n, d_out, d_pre,
                        d_suf, d_tinv, d_bsum);
     QG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_logup_sum, dim3(1), dim3(256), 0, ctx->stream, d_bsum, nb, d_res);
+    hipLaunchKernelGGL(k_logup_sum, dim3(1), dim3(LG_BLOCK), 0, ctx->stream, d_bsum, nb, &io->res);
     QG_LAUNCH_CHECK();
   }
-  return logup_total(ctx, d_res, d_err);
-}
-
-// [a, a + na) and [b, b + nb) share an element
-template <class T>
-static bool lg_overlap(const T* a, size_t na, const T* b, size_t nb) {
-  return a < b + nb && b < a + na;
+  return logup_total(ctx, &io->res, &io->err);
 }
 
 // d_out[x] = h(tabs[.][x]) over this rank's n rows, canonical Montgomery words.
 // Only the compiled image: an expression beyond lg_compile's limits (128
 // monomials, 512 factors, 64 tables) is QG_ERR_UNSUPPORTED, not interpreted.
 static void expr_column_run(qg_ctx* ctx, size_t n, uint32_t ntables,
-                            const std::vector<const Fr*>& tabs, const qg_expr_op* prog, size_t len,
-                            const uint64_t* consts, size_t nconsts, Fr* d_out) {
+                            const std::vector<const Fr*>& tabs, const LgExpr& h, Fr* d_out) {
   LgDev img;
-  memset(&img, 0, sizeof(img));
-  std::vector<uint32_t> used;
-  uint32_t nfac = 0;
-  // scale 256 + 5f: the value comes out in arkworks form (x 2^256)
-  lg_compile(img, 0, compile_program(prog, len, consts, nconsts, ntables), Fr::zero(), false, 256,
-             used, nfac);
-  for (size_t s = 0; s < used.size(); s++) img.tab[s] = tabs[used[s]];
-  QG_HIP(hipSetDevice(ctx->device));
-  uint8_t* io = ctx->scratch_as<uint8_t>("lg_io", sizeof(LgDev) + 64);
-  LgDev* d_img = reinterpret_cast<LgDev*>(io);
-  QG_HIP(hipMemcpyAsync(d_img, &img, sizeof(img), hipMemcpyHostToDevice, ctx->stream));
+  LgIo* io = lg_setup(ctx, img, ntables, tabs, h, nullptr, LgExpr{});
   {
     QgTimed tm(ctx, "expr_column");
-    hipLaunchKernelGGL(k_expr_column, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_img, n,
+    hipLaunchKernelGGL(k_expr_column, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, &io->img, n,
                        d_out);
     QG_LAUNCH_CHECK();
   }
   ctx->sync();
+}
+
+// ---- the column entries' table arguments ------------------------------------
+// the _dev entries: the output and every table present and at least n long, no
+// table sharing an entry with the output's n (k_logup_den writes out[row] while
+// other blocks still read the tables, and k_logup reads them again for m)
+static std::vector<const Fr*> lg_dev_tables(uint32_t ntables, const qg_buf* const* tables, size_t n,
+                                            const qg_buf* out) {
+  QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
+  QG_CHECK(out->n >= n, QG_ERR_INVALID, "output buffer too short");
+  std::vector<const Fr*> tabs;
+  for (uint32_t i = 0; i < ntables; i++) {
+    QG_CHECK(tables[i] && tables[i]->n >= n, QG_ERR_INVALID, "table buffer missing or too short");
+    QG_CHECK(!ranges_overlap(out->d, n, tables[i]->d, n), QG_ERR_INVALID,
+             "output aliases an input table");
+    tabs.push_back(tables[i]->d);
+  }
+  return tabs;
+}
+
+// the host entries: every table present, uploaded into "lg_in"; returns the
+// output column, which follows the tables there
+static Fr* lg_upload_tables(qg_ctx* ctx, uint32_t ntables, const uint64_t* const* tables, size_t n,
+                            std::vector<const Fr*>& tabs) {
+  QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
+  for (uint32_t i = 0; i < ntables; i++) QG_CHECK(tables[i] != nullptr, QG_ERR_INVALID, "null table");
+  QG_HIP(hipSetDevice(ctx->device));
+  Fr* d = ctx->scratch_as<Fr>("lg_in", n * ((size_t)ntables + 1));
+  for (uint32_t i = 0; i < ntables; i++) {
+    fr_upload(ctx, d + n * i, tables[i], n);
+    tabs.push_back(d + n * i);
+  }
+  return d + n * ntables;
 }
 
 }  // namespace qg
@@ -819,23 +639,14 @@ int qg_expr_column(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const uint64_t
                    uint64_t* out) {
   return qg_guard(ctx, [&] {
     QG_CHECK(ctx && prog && len && out, QG_ERR_INVALID, "null argument");
-    QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
     QG_CHECK(nconsts == 0 || consts, QG_ERR_INVALID, "null constants");
     const size_t n = lg_local_size(ctx, nvars);
-    for (uint32_t i = 0; i < ntables; i++) {
-      QG_CHECK(tables[i] != nullptr, QG_ERR_INVALID, "null table");
-      QG_CHECK(!lg_overlap(out, 4 * n, tables[i], 4 * n), QG_ERR_INVALID,
+    for (uint32_t i = 0; tables && i < ntables; i++)
+      QG_CHECK(!tables[i] || !ranges_overlap(out, 4 * n, tables[i], 4 * n), QG_ERR_INVALID,
                "output aliases an input table");
-    }
-    QG_HIP(hipSetDevice(ctx->device));
-    Fr* d = ctx->scratch_as<Fr>("lg_in", n * ((size_t)ntables + 1));
     std::vector<const Fr*> tabs;
-    for (uint32_t i = 0; i < ntables; i++) {
-      fr_upload(ctx, d + n * i, tables[i], n);
-      tabs.push_back(d + n * i);
-    }
-    Fr* d_out = d + n * ntables;
-    expr_column_run(ctx, n, ntables, tabs, prog, len, consts, nconsts, d_out);
+    Fr* d_out = lg_upload_tables(ctx, ntables, tables, n, tabs);
+    expr_column_run(ctx, n, ntables, tabs, LgExpr{prog, len, consts, nconsts}, d_out);
     fr_download(ctx, out, d_out, n);
     ctx->sync();
   });
@@ -846,18 +657,10 @@ int qg_expr_column_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const qg_b
                        qg_buf* out) {
   return qg_guard(ctx, [&] {
     QG_CHECK(ctx && prog && len && out, QG_ERR_INVALID, "null argument");
-    QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
     QG_CHECK(nconsts == 0 || consts, QG_ERR_INVALID, "null constants");
     const size_t n = lg_local_size(ctx, nvars);
-    QG_CHECK(out->n >= n, QG_ERR_INVALID, "output buffer too short");
-    std::vector<const Fr*> tabs;
-    for (uint32_t i = 0; i < ntables; i++) {
-      QG_CHECK(tables[i] && tables[i]->n >= n, QG_ERR_INVALID, "table buffer missing or too short");
-      QG_CHECK(!lg_overlap(out->d, n, tables[i]->d, n), QG_ERR_INVALID,
-               "output aliases an input table");
-      tabs.push_back(tables[i]->d);
-    }
-    expr_column_run(ctx, n, ntables, tabs, prog, len, consts, nconsts, out->d);
+    const std::vector<const Fr*> tabs = lg_dev_tables(ntables, tables, n, out);
+    expr_column_run(ctx, n, ntables, tabs, LgExpr{prog, len, consts, nconsts}, out->d);
   });
 }
 
@@ -868,18 +671,11 @@ int qg_logup_column(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const uint64_
                     uint64_t* out, uint64_t out_sum[4]) {
   return qg_guard(ctx, [&] {
     QG_CHECK(ctx && beta && out, QG_ERR_INVALID, "null argument");
-    QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
     const size_t n = lg_local_size(ctx, nvars);
-    Fr* d = ctx->scratch_as<Fr>("lg_in", std::max<size_t>(1, n * (ntables + 1)));
     std::vector<const Fr*> tabs;
-    for (uint32_t i = 0; i < ntables; i++) {
-      QG_CHECK(tables[i] != nullptr, QG_ERR_INVALID, "null table");
-      fr_upload(ctx, d + n * i, tables[i], n);
-      tabs.push_back(d + n * i);
-    }
-    Fr* d_out = d + n * ntables;
-    const Fr s = logup_run(ctx, nvars, ntables, tabs, h_prog, h_len, h_consts, h_nconsts, m_prog,
-                           m_len, m_consts, m_nconsts, beta, d_out);
+    Fr* d_out = lg_upload_tables(ctx, ntables, tables, n, tabs);
+    const Fr s = logup_run(ctx, nvars, ntables, tabs, LgExpr{h_prog, h_len, h_consts, h_nconsts},
+                           LgExpr{m_prog, m_len, m_consts, m_nconsts}, beta, d_out);
     fr_download(ctx, out, d_out, n);
     if (out_sum) fr_export(s, out_sum);
   });
@@ -892,28 +688,11 @@ int qg_logup_column_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables, const qg_
                         qg_buf* out, uint64_t out_sum[4]) {
   return qg_guard(ctx, [&] {
     QG_CHECK(ctx && beta && out, QG_ERR_INVALID, "null argument");
-    QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
     const size_t n = lg_local_size(ctx, nvars);
-    QG_CHECK(out->n >= n, QG_ERR_INVALID, "output buffer too short");
-    std::vector<const Fr*> tabs;
-    for (uint32_t i = 0; i < ntables; i++) {
-      QG_CHECK(tables[i] && tables[i]->n >= n, QG_ERR_INVALID, "table buffer missing or too short");
-      QG_CHECK(tables[i]->d != out->d, QG_ERR_INVALID, "output aliases an input table");
-      tabs.push_back(tables[i]->d);
-    }
-    const Fr s = logup_run(ctx, nvars, ntables, tabs, h_prog, h_len, h_consts, h_nconsts, m_prog,
-                           m_len, m_consts, m_nconsts, beta, out->d);
+    const std::vector<const Fr*> tabs = lg_dev_tables(ntables, tables, n, out);
+    const Fr s = logup_run(ctx, nvars, ntables, tabs, LgExpr{h_prog, h_len, h_consts, h_nconsts},
+                           LgExpr{m_prog, m_len, m_consts, m_nconsts}, beta, out->d);
     if (out_sum) fr_export(s, out_sum);
-  });
-}
-
-int qg_selftest_inverse(qg_ctx* ctx, int field, int on_device, const uint64_t* in, uint64_t* out,
-                        size_t n) {
-  if ((!in || !out) && n) return QG_ERR_INVALID;
-  if (field != 0 && field != 1) return QG_ERR_INVALID;
-  return qg_guard(ctx, [&] {
-    if (field == 0) inv_selftest<FrP>(ctx, on_device != 0, in, out, n);
-    else inv_selftest<FqP>(ctx, on_device != 0, in, out, n);
   });
 }
 
@@ -927,53 +706,21 @@ int qg_expr_first_nonzero_dev(qg_ctx* ctx, uint32_t nvars, uint32_t ntables,
     QG_CHECK(ntables == 0 || tables, QG_ERR_INVALID, "null tables");
     const size_t n = lg_local_size(ctx, nvars);
     *first_row = -1;
+    // a table that is missing or too short counts only where it is used
+    std::vector<const Fr*> tabs(ntables, nullptr);
+    for (uint32_t i = 0; i < ntables; i++)
+      if (tables[i] && tables[i]->n >= n) tabs[i] = tables[i]->d;
+    // slot 0 alone, no beta: the value in arkworks form (x 2^256); zero test only
     LgDev img;
-    memset(&img, 0, sizeof(img));
-    std::vector<uint32_t> used;
-    uint32_t nfac = 0;
-    bool generic = false;
-    try {
-      const SopProgram sp = compile_program(prog, len, consts, nconsts, ntables);
-      if (sp.mono_len.empty()) return;  // identically zero
-      // scale 256 + 5f: values come out in arkworks form (x 2^256); zero test only
-      lg_compile(img, 0, sp, Fr::zero(), false, 256, used, nfac);
-    } catch (const Error& e) {
-      if (e.code != QG_ERR_UNSUPPORTED) throw;
-      generic = true;
-    }
-    if (generic) {
-      // h(x) materialised by the generic interpreter, then tested as Input(0)
-      std::vector<const Fr*> tabs(ntables, nullptr);
-      for (uint32_t i = 0; i < ntables; i++) {
-        QG_CHECK(tables[i] && tables[i]->n >= n, QG_ERR_INVALID, "table buffer missing or too short");
-        tabs[i] = tables[i]->d;
-      }
-      Fr* ev = ctx->scratch_as<Fr>("fnz_gen_tab", n);
-      expr_table_device(ctx, n, ntables, tabs, prog, len, consts, nconsts, ev);
-      memset(&img, 0, sizeof(img));
-      used.clear();
-      nfac = 0;
-      const qg_expr_op h0[1] = {{QG_OP_INPUT, 0}};
-      lg_compile(img, 0, compile_program(h0, 1, nullptr, 0, 1), Fr::zero(), false, 256, used, nfac);
-      img.tab[0] = ev;
-    } else {
-      for (size_t s = 0; s < used.size(); s++) {
-        QG_CHECK(tables[used[s]] && tables[used[s]]->n >= n, QG_ERR_INVALID,
-                 "table buffer missing or too short");
-        img.tab[s] = tables[used[s]]->d;
-      }
-    }
-    uint8_t* io = ctx->scratch_as<uint8_t>("lg_io", sizeof(LgDev) + 64);
-    LgDev* d_img = reinterpret_cast<LgDev*>(io);
-    unsigned long long* d_first = reinterpret_cast<unsigned long long*>(io + sizeof(LgDev));
+    LgIo* io = lg_setup_any(ctx, img, n, ntables, tabs, LgExpr{prog, len, consts, nconsts}, nullptr,
+                            LgExpr{});
     const unsigned long long init = n;
-    QG_HIP(hipMemcpyAsync(d_img, &img, sizeof(img), hipMemcpyHostToDevice, ctx->stream));
-    QG_HIP(hipMemcpyAsync(d_first, &init, 8, hipMemcpyHostToDevice, ctx->stream));
+    QG_HIP(hipMemcpyAsync(&io->first, &init, 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_expr_first_nonzero, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,
-                       d_img, n, d_first);
+                       &io->img, n, &io->first);
     QG_LAUNCH_CHECK();
     unsigned long long f = 0;
-    QG_HIP(hipMemcpyAsync(&f, d_first, 8, hipMemcpyDeviceToHost, ctx->stream));
+    QG_HIP(hipMemcpyAsync(&f, &io->first, 8, hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
     *first_row = f >= n ? -1 : (int64_t)f;
   });

@@ -435,12 +435,6 @@ static void lookup_report(int64_t miss, int64_t* first_missing) {
            "lookup source row " + std::to_string(miss) + " is in no table row");
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-template <class T>
-static bool lk_overlap(const T* a, size_t na, const T* b, size_t nb) {
-  return a < b + nb && b < a + na;
-}
-
 // the _dev entry's checks of this rank's own arguments; `check_buffers` is
 // false when the lengths are over a cap (no buffer of such a length exists)
 static void lookup_check_dev_args(uint32_t ncols, const qg_buf* const* src_cols, size_t src_len,
@@ -457,8 +451,8 @@ static void lookup_check_dev_args(uint32_t ncols, const qg_buf* const* src_cols,
              "source column buffer missing or too short");
     QG_CHECK(tab_cols[c] && tab_cols[c]->n >= tab_len, QG_ERR_INVALID,
              "table column buffer missing or too short");
-    QG_CHECK(!lk_overlap(out_m->d, tab_len, src_cols[c]->d, src_len) &&
-                 !lk_overlap(out_m->d, tab_len, tab_cols[c]->d, tab_len),
+    QG_CHECK(!ranges_overlap(out_m->d, tab_len, src_cols[c]->d, src_len) &&
+                 !ranges_overlap(out_m->d, tab_len, tab_cols[c]->d, tab_len),
              QG_ERR_INVALID, "output aliases an input column");
     src.c[c] = src_cols[c]->d;
     tab.c[c] = tab_cols[c]->d;
@@ -483,8 +477,8 @@ int qg_lookup_multiplicities(qg_ctx* ctx, uint32_t ncols, const uint64_t* const*
              "(communicator attached): use qg_lookup_multiplicities_dev");
     for (uint32_t c = 0; c < ncols; c++) {
       QG_CHECK(src_cols[c] && tab_cols[c], QG_ERR_INVALID, "null column");
-      QG_CHECK(!lk_overlap(out_m, 4 * tab_len, src_cols[c], 4 * src_len) &&
-                   !lk_overlap(out_m, 4 * tab_len, tab_cols[c], 4 * tab_len),
+      QG_CHECK(!ranges_overlap(out_m, 4 * tab_len, src_cols[c], 4 * src_len) &&
+                   !ranges_overlap(out_m, 4 * tab_len, tab_cols[c], 4 * tab_len),
                QG_ERR_INVALID, "output aliases an input column");
     }
     QG_HIP(hipSetDevice(ctx->device));

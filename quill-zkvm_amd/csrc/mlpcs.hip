@@ -31,15 +31,8 @@ static constexpr int ML_BLOCK = 256;
 static constexpr int SH_B = 32;  // suffix-Horner chunk length
 
 // ---------------------------------------------------------------- reductions
-QG_DEV Fr shfl_xor_fr2(const Fr& a, int m) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = __shfl_xor(a.v[i], m, 64);
-  return r;
-}
-
 QG_DEV Fr block_sum_fr(Fr v, Fr* lds) {
-  for (int m = 32; m > 0; m >>= 1) v = v + shfl_xor_fr2(v, m);
+  for (int m = 32; m > 0; m >>= 1) v = v + shfl_xor_fr(v, m);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
   if (lane == 0) lds[wid] = v;
   __syncthreads();
@@ -344,13 +337,6 @@ struct EvJob {
 struct EvJobs {
   EvJob j[EV_MAXJ];
 };
-
-QG_DEV F29<FrP> shfl_down29(const F29<FrP>& a, int d) {
-  F29<FrP> r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = __shfl_down(a.l[i], d, 64);
-  return r;
-}
 
 __global__ void __launch_bounds__(EV_T) k_poly_eval(EvJobs jb) {
   const EvJob& J = jb.j[blockIdx.y];

@@ -6,7 +6,11 @@
 // the host; on_device = 1 runs them as compiled for gfx950, plus the
 // device-only throughput forms (mul29t ...).  One thread per case, no
 // data-dependent addressing.  qg_selftest_curve29 (below) does the same for
-// the XYZZ primitives of curve29.h.
+// the XYZZ primitives of curve29.h, qg_selftest_inverse for the binary-GCD
+// inversion of bingcd.h.
+#include <vector>
+
+#include "bingcd.h"
 #include "common.h"
 #include "curve29.h"
 #include "field29.h"
@@ -252,6 +256,47 @@ static void x29_selftest(qg_ctx* ctx, int op, bool dev, const uint32_t* in, size
   ctx->sync();
 }
 
+// ---- qg_selftest_inverse ----------------------------------------------------
+// The binary-GCD inversion of bingcd.h (the Logup column's single inversion runs
+// it on the host).
+// qg_selftest_inverse's device path: one inversion per thread
+template <class C>
+__global__ void k_inv_selftest(const Fp<C>* __restrict__ in, Fp<C>* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = inv_bingcd<C>(in[i]);
+}
+
+template <class C>
+static void inv_selftest(qg_ctx* ctx, bool dev, const uint64_t* in, uint64_t* out, size_t n) {
+  std::vector<Fp<C>> h(n);
+  for (size_t i = 0; i < n; i++)
+    for (int l = 0; l < 4; l++) {
+      h[i].v[2 * l] = (uint32_t)in[4 * i + l];
+      h[i].v[2 * l + 1] = (uint32_t)(in[4 * i + l] >> 32);
+    }
+  for (size_t i = 0; i < n; i++) {
+    Fp<C> t = h[i];
+    reduce_full<C>(t.v);
+    QG_CHECK(t == h[i], QG_ERR_INVALID, "inverse self-test input not canonical");
+  }
+  if (dev) {
+    QG_CHECK(ctx, QG_ERR_INVALID, "device self-test needs a context");
+    QG_HIP(hipSetDevice(ctx->device));
+    Fp<C>* d = ctx->scratch_as<Fp<C>>("inv_selftest", 2 * n + 2);
+    QG_HIP(hipMemcpyAsync(d, h.data(), n * sizeof(Fp<C>), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_inv_selftest<C>, dim3(div_up(n ? n : 1, 64)), dim3(64), 0, ctx->stream, d, d + n,
+                       n);
+    QG_LAUNCH_CHECK();
+    QG_HIP(hipMemcpyAsync(h.data(), d + n, n * sizeof(Fp<C>), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+  } else {
+    for (size_t i = 0; i < n; i++) h[i] = inv_bingcd<C>(h[i]);
+  }
+  for (size_t i = 0; i < n; i++)
+    for (int l = 0; l < 4; l++)
+      out[4 * i + l] = (uint64_t)h[i].v[2 * l] | ((uint64_t)h[i].v[2 * l + 1] << 32);
+}
+
 }  // namespace qg
 
 extern "C" {
@@ -276,6 +321,16 @@ int qg_selftest_curve29(qg_ctx* ctx, int op, int on_device, const uint32_t* in, 
   if (n > X29_MAX_CASES) return QG_ERR_INVALID;
   if (on_device && !ctx) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] { x29_selftest(ctx, op, on_device != 0, in, n, out, flags); });
+}
+
+int qg_selftest_inverse(qg_ctx* ctx, int field, int on_device, const uint64_t* in, uint64_t* out,
+                        size_t n) {
+  if ((!in || !out) && n) return QG_ERR_INVALID;
+  if (field != 0 && field != 1) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    if (field == 0) inv_selftest<FrP>(ctx, on_device != 0, in, out, n);
+    else inv_selftest<FqP>(ctx, on_device != 0, in, out, n);
+  });
 }
 
 }  // extern "C"

@@ -243,13 +243,6 @@ QG_DEV void st_sc1_u32(uint32_t* p, uint32_t v) {
 // every storing wave drains its sc1 stores (inline asm: the compiler cannot drop it)
 QG_DEV void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-QG_DEV Fr shfl_xor_fr(const Fr& a, int m) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = __shfl_xor(a.v[i], m, 64);
-  return r;
-}
-
 // lazy value < 6p -> normalized, < 2p
 QG_DEV R29 red6p(const R29& a) {
   return condsub29<FrP>(condsub29<FrP>(normfull29<FrP>(a), l9_mul_small(F29P<FrP>::P, 4)),

@@ -12,5 +12,3 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/lg_$tag -o run 
   python3 -u bench.py --full --log-msm 16 --no-sumcheck --log-mle 0 --log-hp-rows 0 --no-cpu-baseline --no-traffic \
   --no-scaling-modes --steps 10 --detail-out '' > gpurun_out/lg_${tag}_prof.out 2>&1 || exit 1
 python3 profiles/kstats.py gpurun_out/lg_$tag logup > gpurun_out/lg_$tag.txt || exit 1
-QG_LOGUP_FUSED=1 timeout -k 10 300 python -u bench.py --full --log-msm 16 --no-sumcheck --log-mle 0 --log-hp-rows 0 --no-cpu-baseline \
-  --no-scaling-modes --steps 10 --detail-out gpurun_out/lg_${tag}_1p.json > gpurun_out/lg_${tag}_1p.out 2>&1 || exit 1

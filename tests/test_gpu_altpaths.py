@@ -3,11 +3,12 @@ for bit against the default path on the same inputs:
   * k_sc_tail, the streaming sumcheck tail: QG_SC_OLD_TAIL=1 on one context, and
     the sharded prover whose gathered tail does not fit the slice tail (8 source
     tables at nvars >= 15 over 8 loopback ranks, ADVICE r3 medium);
-  * k_logup_fused, the one-pass Logup column (QG_LOGUP_FUSED=1);
   * the replicated S polynomial in the sharded ML opening (QG_S_REPLICATED=1).
   * an MSM batch in stream order (QG_MSM_PIPE=0) instead of on the two side
     streams.
-The switches are read per call, so the tests toggle them in-process."""
+The switches are read per call, so the tests toggle them in-process.
+(The Logup column has one path: its one-pass kernel and QG_LOGUP_FUSED are gone;
+tests/test_gpu_logup.py checks the column against the oracle at the same sizes.)"""
 import contextlib
 import os
 import random
@@ -84,25 +85,6 @@ def test_sharded_k8_tail_matches_single(world, nv):
                                      claimed, q.Transcript(b"k8"))
     for got in run_ranks(world, fn):
         assert got == ref
-
-
-@pytest.mark.parametrize("nv", [11, 13, 16])
-def test_logup_fused_matches_default(dev, nv):
-    import quill_amd as q
-    from quill_amd import VirtualPolyExpr as E
-    from quill_amd.logup import logup_column_device
-    tabs = [q.DeviceVec(dev, 1 << nv).fill_random(88 + 5 * i + nv) for i in range(3)]
-    res = []
-    for fused in ("0", "1"):
-        out = q.DeviceVec(dev, 1 << nv)
-        with env("QG_LOGUP_FUSED", fused):
-            s = logup_column_device(dev, nv, tabs, E.Input(0) + E.Const(0xA1FA) * E.Input(1),
-                                    0xBE7A, out, E.Input(2))
-        res.append((s, out.to_numpy().tobytes()))
-        out.close()
-    for t in tabs:
-        t.close()
-    assert res[0] == res[1]
 
 
 @pytest.mark.parametrize("world", [2, 4])

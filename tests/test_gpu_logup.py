@@ -115,6 +115,69 @@ def test_logup_column_large_property(dev, nv):
         v.close()
 
 
+@pytest.mark.parametrize("nv", [11, 13, 16])
+def test_logup_column_device_matches_c_oracle(dev, nv):
+    """Exactly 1, 4 and 32 blocks of 2048 rows on device-resident tables,
+    m / (beta + t0 + a t1): the column's bytes equal the C restatement of the
+    reference's per-row loop (pinned on the CPU by tests/test_oracle_logup.py)
+    on the downloaded tables, and the returned sum is the sum of the column."""
+    import numpy as np
+    import oracle_c as oc
+    from quill_amd import DeviceVec, VirtualPolyExpr as E
+    from quill_amd.logup import logup_column_device
+    a, beta = 0xA1FA, 0xBE7A
+    tabs = [DeviceVec(dev, 1 << nv).fill_random(88 + 5 * i + nv) for i in range(3)]
+    out = DeviceVec(dev, 1 << nv)
+    s = logup_column_device(dev, nv, tabs, E.Input(0) + E.Const(a) * E.Input(1), beta, out,
+                            E.Input(2))
+    got = out.to_numpy()
+    want, _ = oc.logup_column_arrays(*[t.to_numpy() for t in tabs], o.fr_to_limbs_mont(a),
+                                     o.fr_to_limbs_mont(beta))
+    for v in tabs + [out]:
+        v.close()
+    assert got.tobytes() == np.ascontiguousarray(want, dtype=np.uint64).tobytes()
+    assert s == oc.fr_sum_prod([got])
+
+
+def test_logup_column_dev_statuses(dev):
+    """qg_logup_column_dev's argument checks: the output may share no entry with
+    a table (the same buffer, or a view of one buffer shifted by one entry), and
+    every buffer is there and long enough."""
+    import ctypes as C
+    import quill_amd as q
+    from quill_amd import VirtualPolyExpr as E, lib
+    from quill_amd.field import fr_c
+    from quill_amd.hyperplonk import _program_c
+    L = lib()
+    nv, n = 3, 8
+    U64P = C.POINTER(C.c_uint64)
+    vecs = [q.DeviceVec(dev, n).fill_random(40 + i) for i in range(3)]
+    out = q.DeviceVec(dev, n)
+    hp, hl, hc, hn = _program_c(E.Input(0) + E.Const(0xA1FA) * E.Input(1))
+    mp, ml, mc, mn = _program_c(E.Input(2))
+    beta, s = fr_c(0xBE7A), (C.c_uint64 * 4)()
+
+    def call(tables, o_):
+        ptrs = (C.c_void_p * 3)(*[t.h.value if t is not None else None for t in tables])
+        return L.qg_logup_column_dev(dev.h, nv, 3, ptrs, hp, hl, hc.ctypes.data_as(U64P), hn, mp, ml,
+                                     mc.ctypes.data_as(U64P), mn, beta, o_.h, s)
+
+    assert call(vecs, out) == 0
+    # out is one of the tables; out and a table are overlapping views of one buffer
+    assert call(vecs, vecs[1]) == -1
+    big = q.DeviceVec(dev, 2 * n).fill_random(50)
+    view_t, view_o = big.view(0, n), big.view(n - 1, n)
+    assert call([vecs[0], vecs[1], view_t], view_o) == -1
+    assert "aliases" in L.qg_last_error(dev.h).decode()
+    # short buffers: the output, a table; a null table
+    short = q.DeviceVec(dev, n - 1)
+    assert call(vecs, short) == -1
+    assert call([vecs[0], vecs[1], short], out) == -1
+    assert call([vecs[0], None, vecs[2]], out) == -1
+    for v in [view_t, view_o, big, short, out] + vecs:
+        v.close()
+
+
 def _cmp_mle(gp, op):
     assert gp.evaluation_point == op.evaluation_point
     assert gp.evaluation == op.evaluation and gp.s_comm == op.s_comm
