@@ -300,9 +300,10 @@ typedef struct qg_ipa_proof {
  * than the SRS ("Polynomial degree exceeds max degree").  QG_ERR_ASSERT: r == 0,
  * a failed quotient check ("Polynomial division failed", naming which of
  * "f at r", "f at 1/r", "g at r", "g at 1/r", "S at r", "S at 1/r"), or
- * "Inner product verification equation failed".  QG_ERR_UNSUPPORTED: a context
- * with a communicator attached (the sharded S polynomial takes an eq-table g
- * only).
+ * "Inner product verification equation failed".  QG_ERR_UNSUPPORTED: this
+ * host-pointer entry on a context with a communicator attached ("sharded" in
+ * qg_last_error, returned before any collective): a sharded caller holds device
+ * blocks and calls qg_ipa_prove_dev, as for qg_lookup_multiplicities.
  * The call transforms f in the scratch the ML opening keeps its transform in:
  * a QG_OPEN_UNCHANGED opening after it recomputes its transform.
  * QG_IPA_PAIRED=1 (read per call) runs the six quotients as three paired
@@ -310,7 +311,28 @@ typedef struct qg_ipa_proof {
  * six single ones; the proof is identical. */
 int qg_ipa_prove(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf, const uint64_t* g,
                  size_t ng, uint8_t state[32], qg_ipa_proof* out);
-/* Same, on device-resident vectors (the first nf / ng entries). */
+/* Same, on device-resident vectors (the first nf / ng entries).
+ * With a communicator attached, rank c of W passes its blocks f[cL, (c+1)L) and
+ * g[cL, (c+1)L) of the two global coefficient vectors (nf == ng == L) and the
+ * SRS shard at offset cL, as qg_mle_open_dev takes it.  W L must be a power of
+ * two (at most 2^27) and W a power of two <= 64; a shorter operand is
+ * zero-padded by the caller, and zero tails are trimmed globally, as
+ * DensePolynomial trims them.  The proof and the final transcript state on every
+ * rank equal what the single-context call returns for the concatenated vectors,
+ * bit for bit (zero-padding changes neither the inner product nor the trimmed
+ * polynomials; it only appends zero coefficients to S).  Any other local
+ * geometry is QG_ERR_UNSUPPORTED ("sharded inner-product argument needs nf ==
+ * ng == L with world * L a power of two ..."), decided from the rank's own
+ * arguments before the first collective, so a rank that fails it leaves no peer
+ * waiting; so are nf == 0 && ng == 0, null handles and a length beyond the
+ * buffer (QG_ERR_INVALID).  "Polynomial degree exceeds max degree" is judged
+ * against every rank's shard (the shard sizes travel with the local lengths) and
+ * returned by all ranks together, like r == 0, a failed quotient check and the
+ * final equation.  Ranks that pass different L cannot be detected by any rank:
+ * a caller error, and the call may then hang or return a wrong proof.
+ * QG_S_PRESUM_FUSED=0 (read per call and per rank) runs the S
+ * polynomial's pre-sums as one launch per operand and residue instead of the
+ * fused one; the proof is identical. */
 int qg_ipa_prove_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf, const qg_buf* g,
                      size_t ng, uint8_t state[32], qg_ipa_proof* out);
 

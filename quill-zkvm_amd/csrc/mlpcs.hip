@@ -1500,6 +1500,48 @@ __global__ void k_s_presum(const Fr* __restrict__ f, size_t M, size_t B, uint32_
   u[i2] = from29(canon29(mul29(acc, to29(pw[i2]))));
 }
 
+// The same pre-sum for two operands f and g (a general g instead of an eq
+// table: the inner-product argument) at NRES residues in one pass: residue q
+// has the constants cw.v[q] and the powers pw + q B, and u + (2 op + q) B
+// receives operand op (0: f, 1: g) at residue q.  Each gathered entry is read
+// and converted to limbs once instead of once per (operand, residue) launch of
+// k_s_presum; every output runs k_s_presum's steps on its own accumulator, so
+// the words are the ones four launches write.  The constants are wave-uniform
+// (scalar loads from the kernel arguments); h <= SP_MAXW / 2.
+struct SpConsts2 {
+  L9 v[2][SP_MAXW / 2];
+};
+template <int NRES>
+__global__ void __launch_bounds__(256)
+    k_s_presum_fg(const Fr* __restrict__ f, const Fr* __restrict__ g, size_t M, size_t B,
+                  uint32_t h, SpConsts2 cw, const Fr* __restrict__ pw, Fr* __restrict__ u) {
+  const size_t i2 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i2 >= B) return;
+  R29 acc[2][NRES];
+#pragma unroll
+  for (int op = 0; op < 2; op++)
+#pragma unroll
+    for (int q = 0; q < NRES; q++) acc[op][q] = R29::zero();
+  for (uint32_t i1 = 0; i1 < h; i1++) {
+    const size_t e = (size_t)i1 * B + i2;
+    if (e >= M) break;  // (only at W = 1: the upper half of the one block is padding)
+    const R29 x[2] = {to29(f[e]), to29(g[e])};
+#pragma unroll
+    for (int q = 0; q < NRES; q++) {
+      const R29 k = R29::from_l9(cw.v[q][i1]);
+#pragma unroll
+      for (int op = 0; op < 2; op++) acc[op][q] = red2p29(add29(acc[op][q], mul29(x[op], k)));
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NRES; q++) {
+    const R29 p = to29(pw[(size_t)q * B + i2]);
+#pragma unroll
+    for (int op = 0; op < 2; op++)
+      u[(size_t)(2 * op + q) * B + i2] = from29(canon29(mul29(acc[op][q], p)));
+  }
+}
+
 // G at residue c, bit-reversed within the block, one product-formula level per
 // launch (k_eqdft_level restricted to k = c mod W): level t has 2^(lb - t)
 // entries e (lb = log2 B), k2 = bitrev(e), factor a_t + z_t w^{(k2 W + c) 2^t}
@@ -1583,8 +1625,15 @@ static L9 l9_x261(const Fr& mont) {  // Montgomery field element -> (value x 2^2
 // this rank's slice S[rank L, rank L + L) (L = M / W; the last entry of the last
 // slice is h[2M - 1] = 0, past S's M - 1 coefficients).  f: the gathered
 // evaluations (M entries, every rank), point: the eq variables (nvars).
+// With `g` (M gathered entries, M = 2^nvars; `point` unused) the second operand
+// is that general vector instead of the eq table: its side at both residues is
+// what f's is, a pre-sum and the B-point DIF, in the same bit-reversed order,
+// so everything from the combine on is shared.  The four pre-sums (two when the
+// residue is its own mirror) run as one k_s_presum_fg launch;
+// QG_S_PRESUM_FUSED=0 (read per call) runs k_s_presum per operand and residue
+// instead, with the same words out (A/B runs, tests).
 static void s_poly_sharded(qg_ctx* ctx, const Fr* f, size_t M, const uint64_t* point,
-                           size_t nvars, Fr* S_local) {
+                           size_t nvars, Fr* S_local, const Fr* g = nullptr) {
   QgTimed tm(ctx, "s_polynomial");
   const uint32_t W = (uint32_t)ctx->world, c = (uint32_t)ctx->rank;
   QG_CHECK(W <= SP_MAXW && (W & (W - 1)) == 0 && M == ((size_t)1 << nvars) && M >= W,
@@ -1607,7 +1656,55 @@ static void s_poly_sharded(qg_ctx* ctx, const Fr* f, size_t M, const uint64_t* p
   Fr* Gb = ctx->scratch_as<Fr>("sp_G", 2 * B);
   Fr* tmp = ctx->scratch_as<Fr>("sp_tmp", 2 * B);  // u / pw scratch, then G level ping-pong
   const int K = 64;
-  for (int q = 0; q < nres; q++) {
+  if (g) {
+    // both operands by pre-sum + DIF: u[(2 op + q) B ..), the powers of residue q at pw + q B
+    Fr* ub = ctx->scratch_as<Fr>("sp_u", 4 * B);
+    Fr* pw = tmp;
+    const uint32_t hb = std::max<uint32_t>(1, W / 2);  // input blocks (partial at W = 1)
+    SpConsts2 cw2{};
+    SpConsts cw1[2] = {};
+    for (int q = 0; q < nres; q++) {
+      hipLaunchKernelGGL(k_powers_ml, dim3(div_up(div_up(B, (size_t)K), ML_BLOCK)), dim3(ML_BLOCK),
+                         0, ctx->stream, fpow_small(w, res[q]), B, K, pw + (size_t)q * B);
+      QG_LAUNCH_CHECK();
+      Fr wk = Fr::one();
+      const Fr wWc = fpow_small(wW, res[q]);
+      for (uint32_t i1 = 0; i1 < hb; i1++) {
+        cw2.v[q][i1] = cw1[q].v[i1] = l9_x261(wk);
+        wk = wk * wWc;
+      }
+    }
+    hipLaunchKernelGGL(k_fr_to261, dim3(div_up((size_t)nres * B, ML_BLOCK)), dim3(ML_BLOCK), 0,
+                       ctx->stream, pw, (size_t)nres * B, F29P<FrP>::TO261);
+    QG_LAUNCH_CHECK();
+    const char* fe = getenv("QG_S_PRESUM_FUSED");
+    {
+      QgTimed tp(ctx, "s_presum");  // (inside "s_polynomial": micro/ipa_sharded_cost.py)
+      if (!(fe && atoi(fe) == 0)) {
+        const dim3 grid(div_up(B, ML_BLOCK)), blk(ML_BLOCK);
+        if (nres == 2)
+          hipLaunchKernelGGL(k_s_presum_fg<2>, grid, blk, 0, ctx->stream, f, g, M, B, hb, cw2, pw,
+                             ub);
+        else
+          hipLaunchKernelGGL(k_s_presum_fg<1>, grid, blk, 0, ctx->stream, f, g, M, B, hb, cw2, pw,
+                             ub);
+        QG_LAUNCH_CHECK();
+      } else {
+        for (int op = 0; op < 2; op++)
+          for (int q = 0; q < nres; q++) {
+            hipLaunchKernelGGL(k_s_presum, dim3(div_up(B, ML_BLOCK)), dim3(ML_BLOCK), 0, ctx->stream,
+                               op ? g : f, M, B, hb, cw1[q], pw + (size_t)q * B,
+                               ub + (size_t)(2 * op + q) * B);
+            QG_LAUNCH_CHECK();
+          }
+      }
+    }
+    for (int op = 0; op < 2; op++)
+      for (int q = 0; q < nres; q++)
+        ntt_run(ctx, true, ub + (size_t)(2 * op + q) * B, B, (op ? Gb : Fb) + (size_t)q * B, twB,
+                "sp_tw", lb, 0, 0, nullptr);
+  }
+  for (int q = 0; !g && q < nres; q++) {
     const uint32_t cc = res[q];
     Fr* Fq = Fb + (size_t)q * B;
     Fr* Gq = Gb + (size_t)q * B;
@@ -2316,6 +2413,221 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
            QG_ERR_ASSERT, "Inner product verification equation failed");
 }
 
+// The local geometry of a sharded inner-product argument, decided from this
+// rank's arguments alone (before the first collective): equal local lengths L,
+// world a power of two <= SP_MAXW, world * L a power of two within the NTT's
+// 2-adicity.  Returns log2(world * L).
+static size_t ipa_sharded_geometry(qg_ctx* ctx, size_t nf, size_t ng) {
+  const size_t W = (size_t)ctx->world;
+  const size_t M = W * nf;
+  size_t nvars = 0;
+  while (((size_t)1 << nvars) < M && nvars < 27) nvars++;
+  QG_CHECK(nf == ng && nf > 0 && W <= (size_t)SP_MAXW && (W & (W - 1)) == 0 &&
+               M == ((size_t)1 << nvars),
+           QG_ERR_UNSUPPORTED,
+           "sharded inner-product argument needs nf == ng == L with world * L a power of two "
+           "(at most 2^27) and world a power of two <= " + std::to_string(SP_MAXW));
+  return nvars;
+}
+
+// InnerProductProof::prove with a communicator: this rank holds f[rank L,
+// (rank+1) L) and g[rank L, (rank+1) L) of two global vectors of M = world L
+// coefficients and the matching SRS shard.  The flow is
+// mle_open_batch_sharded's with three polynomials and six quotients:
+//   1. the local dot part and local trimmed lengths of f and g (queued);
+//   2. f and g gathered (two allgathers), this rank's slice of S by
+//      s_poly_sharded's general-g form (one all-to-all), its local length;
+//   3. ONE allgather of every rank's dot part, three local lengths and shard
+//      size: the inner product, the global trimmed lengths and - because every
+//      rank then knows every rank's part lengths and bases - the "Polynomial
+//      degree exceeds max degree" decision, the same on all ranks;
+//   4. the S commitment (sharded MSM), the transcript step on every rank;
+//   5. six local suffix-Horner scans (QG_IPA_PAIRED=1: three paired ones),
+//      ONE allgather of their slice-end values T, the carries;
+//   6. the quotient check on the ranks' summed parts (ONE allgather) and the
+//      six commitments as ONE sharded MSM batch; ipa.rs:94-100.
+// Every decision that ends the call is taken on gathered values, which all
+// ranks hold alike, so no rank leaves between two collectives its peers enter.
+// The scratch is the flow's own and s_poly_sharded's (sp_*): no transform the
+// "ntt_F_src" memo describes is touched, so the memo stays.
+// An all-zero operand needs no special case: its transform is exact zeros (the
+// single path also skips only a stated length of 0, which has no sharded form).
+static void ipa_prove_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* df, const Fr* dg, size_t L,
+                              size_t nvars, uint8_t state[32], qg_ipa_proof* out) {
+  const size_t W = (size_t)ctx->world, rank = (size_t)ctx->rank;
+  const size_t M = W * L, off = rank * L;
+  struct Small {
+    Fr part;
+    unsigned long long len[3], srs_n;
+  };
+  Small* d_sm = ctx->scratch_as<Small>("ipas_small", 1);
+  QG_HIP(hipMemsetAsync(d_sm, 0, sizeof(Small), ctx->stream));
+  const unsigned long long my_n = srs->n;
+  QG_HIP(hipMemcpyAsync(&d_sm->srs_n, &my_n, sizeof my_n, hipMemcpyHostToDevice, ctx->stream));
+  dot_to_device(ctx, df, dg, L, &d_sm->part);
+  trim_launch(ctx, df, L, &d_sm->len[0]);
+  trim_launch(ctx, dg, L, &d_sm->len[1]);
+  Fr* Sl = ctx->scratch_as<Fr>("ipas_Sl", L);
+  if (M > 1) {
+    Fr* ffull = ctx->scratch_as<Fr>("ipas_f", M);
+    Fr* gfull = ctx->scratch_as<Fr>("ipas_g", M);
+    comm_allgather_bytes(ctx, df, ffull, L * sizeof(Fr));
+    comm_allgather_bytes(ctx, dg, gfull, L * sizeof(Fr));
+    s_poly_sharded(ctx, ffull, M, nullptr, nvars, Sl, gfull);
+  } else {
+    QG_HIP(hipMemsetAsync(Sl, 0, L * sizeof(Fr), ctx->stream));  // M == 1: S is empty
+  }
+  trim_launch(ctx, Sl, L, &d_sm->len[2]);
+  if (ctx->open_fault_live == 1) {  // test-only: this rank's first nonzero local length
+    ctx->open_fault_live = 0;
+    hipLaunchKernelGGL(k_fault_short_len, dim3(1), dim3(64), 0, ctx->stream, d_sm->len, (size_t)3,
+                       (unsigned long long)ctx->open_fault_value);
+    QG_LAUNCH_CHECK();
+  }
+  // exchange 1: dot parts, local lengths and shard sizes of every rank
+  Small* d_all = ctx->scratch_as<Small>("ipas_small_all", W);
+  comm_allgather_bytes(ctx, d_sm, d_all, sizeof(Small));
+  std::vector<Small> all(W);
+  QG_HIP(hipMemcpyAsync(all.data(), d_all, W * sizeof(Small), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  Fr ip = Fr::zero();
+  size_t glt[3] = {0, 0, 0};  // global trimmed lengths of f, g, S
+  for (size_t r = 0; r < W; r++) {
+    ip = ip + all[r].part;
+    // the largest (rank offset + local length) of a nonzero slice
+    for (int p = 0; p < 3; p++)
+      if (all[r].len[p]) glt[p] = std::max(glt[p], r * L + (size_t)all[r].len[p]);
+  }
+  // rank r's live part of a polynomial of global length n, and of its quotient
+  auto live = [&](size_t n, size_t r) { return n > r * L ? std::min(L, n - r * L) : (size_t)0; };
+  auto qlive = [&](size_t n, size_t r) { return n ? live(n - 1, r) : (size_t)0; };
+  for (size_t r = 0; r < W; r++) {
+    bool fits = live(glt[2], r) <= all[r].srs_n;
+    for (int p = 0; p < 3; p++) fits = fits && qlive(glt[p], r) <= all[r].srs_n;
+    QG_CHECK(fits, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+  }
+  const G1Affine s_comm = msm_device_batch(ctx, srs, {Sl}, {live(glt[2], rank)})[0];
+  // transcript: inner_product, s_comm; draw r (ipa.rs:76-83), on every rank alike
+  uint8_t b32[32], b64[64];
+  fr_to_bytes(ip, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr r = transcript_draw_fr(state);
+  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  const Fr r_inv = finv(r);
+  fr_export(ip, out->inner_product);
+  g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
+  // the six quotients' local scans: job i = 2 p + (point), this rank's le[p]
+  // live coefficients of polynomial p into sq[i][0 .. le); T_i = sq[i][0]
+  qg_kzg_opening* outs[6] = {&out->f_opening, &out->f_opening_inv, &out->g_opening,
+                             &out->g_opening_inv, &out->s_opening, &out->s_opening_inv};
+  const Fr* polys[3] = {df, dg, Sl};
+  const Fr xs[2] = {r, r_inv};
+  size_t le[3];
+  Fr* sq[6];
+  for (int i = 0; i < 6; i++) {
+    le[i >> 1] = live(glt[i >> 1], rank);
+    sq[i] = ctx->scratch_as<Fr>("ipas_s#" + std::to_string(i), le[i >> 1] + 1);
+  }
+  const char* pe = getenv("QG_IPA_PAIRED");
+  const bool paired = pe && atoi(pe) != 0;
+  {
+    QgTimed tm(ctx, "kzg_division");
+    if (paired) {
+      std::vector<ShIn<2>> jobs;
+      for (int p = 0; p < 3; p++)
+        if (le[p]) jobs.push_back({polys[p], le[p], {r, r_inv}, {sq[2 * p], sq[2 * p + 1]}});
+      suffix_horner<2>(ctx, jobs);
+    } else {
+      std::vector<ShIn<1>> jobs;
+      for (int i = 0; i < 6; i++)
+        if (le[i >> 1]) jobs.push_back({polys[i >> 1], le[i >> 1], {xs[i & 1]}, {sq[i]}});
+      suffix_horner_many(ctx, jobs);
+    }
+  }
+  Fr* d_T = ctx->scratch_as<Fr>("ipas_T", 6);
+  QG_HIP(hipMemsetAsync(d_T, 0, 6 * sizeof(Fr), ctx->stream));
+  for (int i = 0; i < 6; i++)
+    if (le[i >> 1])
+      QG_HIP(hipMemcpyAsync(d_T + i, sq[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+  // exchange 2: every rank's T values
+  Fr* d_Tall = ctx->scratch_as<Fr>("ipas_T_all", 6 * W);
+  comm_allgather_bytes(ctx, d_T, d_Tall, 6 * sizeof(Fr));
+  std::vector<Fr> Tall(6 * W);
+  QG_HIP(hipMemcpyAsync(Tall.data(), d_Tall, 6 * W * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  // C_rank = sum_{r' > rank} T_r' x^((r' - rank - 1) L);  y = sum_r' T_r' x^(r' L)
+  Fr y[6];
+  Fr* pw = ctx->scratch_as<Fr>("open_pw", L + 1);
+  std::vector<const Fr*> qs(6);
+  std::vector<size_t> qn(6);
+  for (int i = 0; i < 6; i++) {
+    const size_t n = le[i >> 1];
+    const Fr x = xs[i & 1], xL = fpow_small(x, L);
+    Fr Cc = Fr::zero(), yy = Fr::zero();
+    for (size_t rr = W; rr-- > 0;) {
+      if (rr == rank) Cc = yy;
+      yy = Tall[rr * 6 + i] + xL * yy;
+    }
+    y[i] = yy;
+    if (n > 0) {
+      QgTimed tm(ctx, "kzg_division");
+      const int KP = 64;
+      hipLaunchKernelGGL(k_powers_ml, dim3(div_up(div_up(n + 1, (size_t)KP), ML_BLOCK)),
+                         dim3(ML_BLOCK), 0, ctx->stream, x, n + 1, KP, pw);
+      QG_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_sh_carry, dim3(div_up(n + 1, ML_BLOCK)), dim3(ML_BLOCK), 0, ctx->stream,
+                         sq[i], n, pw, Cc);
+      QG_LAUNCH_CHECK();
+    }
+    // q_k = s_{k+1} for global k < glt - 1; this rank's part starts at s + 1
+    qn[i] = qlive(glt[i >> 1], rank);
+    qs[i] = sq[i] + 1;
+    fault_quotient(ctx, sq[i] + 1, qn[i]);
+  }
+  // kzg.rs:85 on the ranks' summed parts: f(sigma), g(sigma), S(sigma) over the
+  // untrimmed local blocks and the six q(sigma)
+  const bool check = open_check_on();
+  Fr* d_ev = check ? ctx->scratch_as<Fr>("ipas_ck_ev", 9) : nullptr;
+  if (check) {
+    QgTimed tm(ctx, "kzg_open_check");
+    std::vector<EvIn> in;
+    for (int p = 0; p < 3; p++) in.push_back({polys[p], L, (uint64_t)off});
+    for (int i = 0; i < 6; i++) in.push_back({qs[i], qn[i], (uint64_t)off});
+    poly_eval_queue(ctx, in, ctx->open_sigma, d_ev);
+  }
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qn);
+  if (check) {
+    Fr* d_evall = ctx->scratch_as<Fr>("ipas_ck_ev_all", 9 * W);
+    comm_allgather_bytes(ctx, d_ev, d_evall, 9 * sizeof(Fr));
+    std::vector<Fr> ev(9 * W);
+    QG_HIP(hipMemcpyAsync(ev.data(), d_evall, ev.size() * sizeof(Fr), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    ctx->sync();
+    std::vector<uint32_t> bad(6, 0);
+    std::vector<uint8_t> checked(6, 0);
+    for (int i = 0; i < 6; i++) {
+      Fr P = Fr::zero(), Q = Fr::zero();
+      for (size_t rr = 0; rr < W; rr++) {
+        P = P + ev[9 * rr + (i >> 1)];
+        Q = Q + ev[9 * rr + 3 + i];
+      }
+      checked[i] = glt[i >> 1] ? CK_QUOT : CK_ZERO;
+      bad[i] = open_check_host(P, y[i], Q, ctx->open_sigma, xs[i & 1]);
+    }
+    open_check_settle(ctx, bad, checked, 6, IPA_QNAME);
+  }
+  for (int i = 0; i < 6; i++) {
+    fr_export(xs[i & 1], outs[i]->x);
+    fr_export(y[i], outs[i]->y);
+    g1_export(pis[i], outs[i]->proof_xy, &outs[i]->proof_inf);
+  }
+  // ipa.rs:94-100
+  QG_CHECK(y[0] * y[3] + y[1] * y[2] == r * y[4] + r_inv * y[5] + from_u64<FrP>(2) * ip,
+           QG_ERR_ASSERT, "Inner product verification equation failed");
+}
+
 }  // namespace qg
 
 extern "C" {
@@ -2453,21 +2765,27 @@ int qg_mle_open_dev_ex(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_
   });
 }
 
-// a general sharded g has no S polynomial here (s_poly_sharded builds its g
-// operand from the eq-table product formula only); checked before OpenCall,
-// whose constructor is collective on a sharded context
-static void ipa_entry_checks(qg_ctx* ctx, size_t nf, size_t ng) {
+// The entry checks run before OpenCall, whose constructor is collective on a
+// sharded context: a rank that fails one leaves no peer waiting.
+// The host-pointer entry stays single-context: a sharded caller holds device
+// blocks and calls qg_ipa_prove_dev.
+static void ipa_host_entry_checks(qg_ctx* ctx, size_t nf, size_t ng) {
   QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
-           "the inner-product argument is not supported on a sharded context (communicator "
-           "attached)");
+           "the host-pointer inner-product argument is not supported on a sharded context "
+           "(communicator attached): pass device blocks to qg_ipa_prove_dev");
   QG_CHECK(nf || ng, QG_ERR_INVALID, "inner-product argument of two empty polynomials");
+}
+// the device entry: returns log2(world * L) on a sharded context (0 otherwise)
+static size_t ipa_dev_entry_checks(qg_ctx* ctx, size_t nf, size_t ng) {
+  QG_CHECK(nf || ng, QG_ERR_INVALID, "inner-product argument of two empty polynomials");
+  return ctx->sharded ? ipa_sharded_geometry(ctx, nf, ng) : 0;
 }
 
 int qg_ipa_prove(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf, const uint64_t* g,
                  size_t ng, uint8_t state[32], qg_ipa_proof* out) {
   if (!ctx || !srs || (!f && nf) || (!g && ng) || !state || !out) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] {
-    ipa_entry_checks(ctx, nf, ng);
+    ipa_host_entry_checks(ctx, nf, ng);
     QG_HIP(hipSetDevice(ctx->device));
     OpenCall call(ctx);
     Fr* df = ctx->scratch_as<Fr>("ipa_f", nf ? nf : 1);
@@ -2482,10 +2800,11 @@ int qg_ipa_prove_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf,
                      size_t ng, uint8_t state[32], qg_ipa_proof* out) {
   if (!ctx || !srs || !f || !g || nf > f->n || ng > g->n || !state || !out) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] {
-    ipa_entry_checks(ctx, nf, ng);
+    const size_t nvars = ipa_dev_entry_checks(ctx, nf, ng);
     QG_HIP(hipSetDevice(ctx->device));
     OpenCall call(ctx);
-    ipa_prove_device(ctx, srs, f->d, nf, g->d, ng, state, out);
+    if (ctx->sharded) ipa_prove_sharded(ctx, srs, f->d, g->d, nf, nvars, state, out);
+    else ipa_prove_device(ctx, srs, f->d, nf, g->d, ng, state, out);
   });
 }
 

@@ -144,7 +144,12 @@ class InnerProductProof:
     def prove(cls, poly1, poly2, kzg: "KZG", transcript: Transcript) -> "InnerProductProof":
         """ipa.rs:59-112 (qg_ipa_prove; qg_ipa_prove_dev when both operands are
         DeviceVecs).  Like the reference, the commitments to poly1 and poly2
-        are the caller's to absorb into the transcript beforehand."""
+        are the caller's to absorb into the transcript beforehand.
+        On a Device with a communicator the operands are this rank's DeviceVec
+        blocks of equal length L (world * L a power of two) and `kzg` wraps the
+        SRS shard at offset rank * L, as for KZG.open_dev; every rank gets the
+        single-context proof.  Host or mixed operands there raise the
+        library's error (the host-pointer entry stays single-context)."""
         out = IpaProof()
         dev = kzg.dev
         if isinstance(poly1, DeviceVec) and isinstance(poly2, DeviceVec):
