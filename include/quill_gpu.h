@@ -558,6 +558,34 @@ int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols,
                                  const qg_buf* const* src_cols, size_t src_len,
                                  const qg_buf* const* tab_cols, size_t tab_len,
                                  qg_buf* out_m, int64_t* first_missing);
+/* The same call with the sharded flow chosen by `table_mode`; the entry above
+ * is this one with QG_LOOKUP_TABLE_REPLICATED.  Both modes return the same
+ * out_m, first_missing and errors, bit for bit; the mode is never chosen for
+ * the caller.  On a context with no communicator either mode is the
+ * one-context flow (0 collectives).  An unknown mode is QG_ERR_INVALID; ranks
+ * that pass different modes all return QG_ERR_INVALID together (the mode
+ * travels in the first exchange).
+ * QG_LOOKUP_TABLE_PARTITIONED: every tuple has one owner rank, chosen by a hash
+ * of the tuple.  Each rank sends the owner one record per distinct tuple of its
+ * table block and of its source block (with the local count), the owner matches
+ * them, and the counts travel back to the rank that holds the winning table
+ * row: 6 collectives per call whatever ncols, all of agreed fixed sizes (the
+ * most records any rank sends any rank, rounded up to even).  No rank holds
+ * more than its own blocks, its share of the distinct tuples and padding; at
+ * most 1024 ranks (QG_ERR_UNSUPPORTED above).  For a table as large as the
+ * source (memory or bus consistency, a range check over a committed column);
+ * the replicated mode suits a small table under a large source.
+ * QG_LOOKUP_OWNER_BITS=<b> (read per call) keeps only the low b bits of the
+ * owner hash (b = 0: rank 0 owns every tuple; a test switch, the result does
+ * not change).  Counters of qg_ctx_counter: "lookup_routed_tab" and
+ * "lookup_routed_src" (records this rank sent), "lookup_exchange_bytes". */
+#define QG_LOOKUP_TABLE_REPLICATED  0u   /* the table gathered on every rank */
+#define QG_LOOKUP_TABLE_PARTITIONED 1u   /* every tuple matched on its owner rank */
+int qg_lookup_multiplicities_dev_ex(qg_ctx* ctx, uint32_t ncols,
+                                    const qg_buf* const* src_cols, size_t src_len,
+                                    const qg_buf* const* tab_cols, size_t tab_len,
+                                    qg_buf* out_m, int64_t* first_missing,
+                                    uint32_t table_mode);
 
 /* Column materialiser: out[x] = h(tables[.][x]) for every row x of the
  * hypercube, h a postfix expression over `tables` (the encoding of the sumcheck
@@ -630,7 +658,15 @@ int qg_trace_marker(qg_ctx* ctx, uint32_t tag);
  * number in use, which a call leaves as it found it (an event that a failed
  * call did not hand back shows here, long before the pool runs dry).
  * "lookup_collectives": collectives issued by qg_lookup_multiplicities_dev on
- * this (sharded) context, at most ncols + 3 per call.
+ * this (sharded) context, at most ncols + 3 per call with a replicated table
+ * and 6 with a partitioned one.
+ * "lookup_routed_tab" / "lookup_routed_src": table / source records this rank
+ * sent to owner ranks in the partitioned mode (one per distinct tuple of its
+ * block).  "lookup_exchange_bytes": bytes this rank received in the payload
+ * collectives of either sharded mode (replicated: W*tab_len*(32*ncols + 4) per
+ * call; partitioned: the two record exchanges and the counters' way back).
+ * "lookup_scratch_bytes": bytes of scratch the context holds now for the lookup
+ * multiplicities (grow-only: the largest call so far, all modes together).
  * The sumcheck prover's paths, counted on the host where each kernel is
  * launched (cumulative over the context's calls):
  * "sc_big_pure_rounds": large rounds run by the thread-per-pair kernel on a

@@ -283,6 +283,13 @@ int qg_ctx_kernel_time(const qg_ctx* ctx, const char* name, double* total_ms, ui
 int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value) {
   if (!ctx || !name || !value) return QG_ERR_INVALID;
   const std::string n(name);
+  if (n == "lookup_scratch_bytes") {  // the arena slots of lookup.hip: "lk_*", "lkp_*"
+    uint64_t b = 0;
+    for (const auto& kv : ctx->arena.slots)
+      if (kv.first.compare(0, 2, "lk") == 0) b += kv.second.bytes;
+    *value = b;
+    return QG_OK;
+  }
   *value = n == "msm_plan_refetch"         ? ctx->msm_plan_refetch
            : n == "msm_handover_violation" ? ctx->msm_handover_violation
            : n == "open_checks"            ? ctx->open_checks
@@ -290,6 +297,9 @@ int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value) {
            : n == "events_created"         ? ctx->events_created
            : n == "events_pooled"          ? ctx->event_pool.size()
            : n == "lookup_collectives"     ? ctx->lookup_collectives
+           : n == "lookup_routed_tab"      ? ctx->lookup_routed_tab
+           : n == "lookup_routed_src"      ? ctx->lookup_routed_src
+           : n == "lookup_exchange_bytes"  ? ctx->lookup_exchange_bytes
            : n == "sc_big_pure_rounds"     ? ctx->sc_big_pure_rounds
            : n == "sc_big_sop_rounds"      ? ctx->sc_big_sop_rounds
            : n == "sc_staged_rounds"       ? ctx->sc_staged_rounds

@@ -126,8 +126,11 @@ struct qg_ctx {
   uint32_t open_fault_armed = 0, open_fault_live = 0;
   uint64_t open_fault_value = 0;
   // collectives issued by the sharded lookup multiplicities (lookup.hip): at
-  // most ncols + 3 per call
+  // most ncols + 3 per call with a replicated table, 6 with a partitioned one
   uint64_t lookup_collectives = 0;
+  // partitioned table: records this rank sent; both sharded modes: bytes this
+  // rank received in the payload collectives (running totals)
+  uint64_t lookup_routed_tab = 0, lookup_routed_src = 0, lookup_exchange_bytes = 0;
   // which sumcheck kernels ran (sumcheck.hip, counted on the host at the launch
   // sites): large rounds by kernel, tails by kind, calls of the interpreted
   // path, and the first round of the last call's tail

@@ -35,13 +35,16 @@
 //    hash: b = 0 sends every row down one probe chain (tests).
 //    QG_LOOKUP_BLOCKS=<k> caps the count kernel's grid.
 //
-// Sharded contexts (qg_lookup_multiplicities_dev only; world W, rank r): every
-// rank holds one block of each column, global row = rank x block length + local
-// row, and receives its block of the global m.  The table is replicated, the
-// source stays where it is (lookup_run_sharded):
+// Sharded contexts (the _dev entries only; world W, rank r): every rank holds
+// one block of each column, global row = rank x block length + local row, and
+// receives its block of the global m.  Two explicit modes compute the same m
+// (qg_lookup_multiplicities_dev_ex; the host decisions are in lookup_plan.h).
+//
+// QG_LOOKUP_TABLE_REPLICATED: the table is replicated, the source stays where
+// it is (lookup_run_sharded):
 //   1. header allgather (32 B per rank: status of the local argument checks,
-//      ncols, src_len, tab_len) - a rank whose checks failed still joins, so all
-//      ranks leave together and none waits in a later collective;
+//      ncols, src_len, tab_len, table mode) - a rank whose checks failed still
+//      joins, so all ranks leave together and none waits in a later collective;
 //   2. one allgather per table column into one global column (rank-major order
 //      is global row order);
 //   3. k_lookup_build over the gathered table (global length), k_lookup_count
@@ -52,21 +55,58 @@
 //   5. one allgather of (lowest missing global row, error word): min and OR.
 // ncols + 3 collectives per call ("lookup_collectives" of qg_ctx_counter).
 // What bounds it: W x tab_len < 2^31 rows of table on every rank (32 x ncols
-// bytes each, plus 12 bytes of slots and counters); a table as large as the
-// source would want a hash-partitioned table instead.
+// bytes each, plus 12 bytes of slots and counters), received and built again
+// by every rank: right for a small table under a big trace.
+//
+// QG_LOOKUP_TABLE_PARTITIONED: every tuple has one owner rank, chosen by a
+// hash of the tuple; no rank holds more than its blocks, its share of the
+// distinct tuples and padding (lookup_run_partitioned):
+//   1. the header allgather, as above;
+//   2. local dedup with the kernels above: k_lookup_build + k_lookup_count of
+//      the source block against itself leave a counter > 0 exactly at the
+//      lowest local row of each distinct tuple (its local count); the same for
+//      the table block.  Only these representatives travel;
+//   3. k_lookup_route_count: owner = (fmix(row hash) x W) >> 32 per
+//      representative, counted per destination (LDS, then one global atomic
+//      per block and destination).  QG_LOOKUP_OWNER_BITS=<b> (read per call)
+//      keeps the low b bits of the finalised hash first: b = 0 makes rank 0
+//      the owner of everything (tests);
+//   4. one allgather of every rank's 2 W counts; all ranks take the maxima
+//      over all pairs, rounded up to even: the fixed chunk lengths of 6.;
+//   5. k_lookup_route_scatter: the representatives into W chunks
+//      [meta: max x 8 B][col 0: max x 32 B]...; meta (filled with ones every
+//      call) = (global row, EMPTY) or (global source row, local count);
+//   6. two all-to-alls: table records, source records;
+//   7. k_lookup_owner_build over the received table records: 64-bit slots
+//      (global row << 32 | record index), atomicCAS to claim, atomicMin on an
+//      equal tuple - the slot names the record with the lowest global row;
+//   8. k_lookup_owner_count over the received source records: the local count
+//      onto the winning record's counter; an empty slot first lowers
+//      first_missing to the record's global row (a representative is its
+//      tuple's lowest row on its rank, so the minimum over all is the lowest
+//      missing global row);
+//   9. one all-to-all takes the counters back in arrival positions;
+//      k_lookup_finish_routed writes m through the meta the sender kept;
+//  10. the allgather of (lowest missing global row, error word).
+// 6 collectives per call whatever ncols.  What bounds it: the most records any
+// rank sends any rank (a send and a receive buffer of W x max x (8 + 32 x
+// ncols) bytes each for the table and for the source, plus 24 bytes of slots
+// and counters per received table record); with distinct rows and an even
+// hash W x max is about the rank's own block, whatever W.  Kernels of both
+// flows: no thread waits on another, every loop has a bound, nothing depends
+// on block order or placement.
 #include <stdlib.h>
 
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "lookup_plan.h"
 
 using namespace qg;
 
 namespace qg {
 
-static constexpr uint32_t LK_MAXCOLS = 16;
-static constexpr uint32_t LK_EMPTY = 0xffffffffu;
 static constexpr int LK_BLOCK = 256;        // build / finish
 static constexpr int LK_CBLOCK = 1024;      // count: two blocks fill a CU's 32 wave slots
 static constexpr uint32_t LK_LDS_ROWS = 16384;  // 64 KB of uint32 counters per block
@@ -104,26 +144,23 @@ QG_DEV uint32_t lk_mix(uint32_t h, uint32_t k) {  // murmur3 body
   return h * 5u + 0xe6546b64u;
 }
 
+static constexpr uint32_t LK_SEED = 0x9747b28cu;
+QG_DEV uint32_t lk_mix_word(uint32_t h, const LkWord& w) {
+  h = lk_mix(h, w.lo.x);
+  h = lk_mix(h, w.lo.y);
+  h = lk_mix(h, w.lo.z);
+  h = lk_mix(h, w.lo.w);
+  h = lk_mix(h, w.hi.x);
+  h = lk_mix(h, w.hi.y);
+  h = lk_mix(h, w.hi.z);
+  return lk_mix(h, w.hi.w);
+}
+
 // hash of row `row` of `cols` (all 8 limbs of every column), cut to hash_mask
 QG_DEV uint32_t lk_hash(const LkCols& cols, uint32_t ncols, size_t row, uint32_t hash_mask) {
-  uint32_t h = 0x9747b28cu;
-  for (uint32_t c = 0; c < ncols; c++) {
-    const LkWord w = lk_load(cols.c[c] + row);
-    h = lk_mix(h, w.lo.x);
-    h = lk_mix(h, w.lo.y);
-    h = lk_mix(h, w.lo.z);
-    h = lk_mix(h, w.lo.w);
-    h = lk_mix(h, w.hi.x);
-    h = lk_mix(h, w.hi.y);
-    h = lk_mix(h, w.hi.z);
-    h = lk_mix(h, w.hi.w);
-  }
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h & hash_mask;
+  uint32_t h = LK_SEED;
+  for (uint32_t c = 0; c < ncols; c++) h = lk_mix_word(h, lk_load(cols.c[c] + row));
+  return lk_fmix(h) & hash_mask;
 }
 
 // row a of A == row b of B, column by column
@@ -250,15 +287,6 @@ __global__ __launch_bounds__(LK_BLOCK) void k_lookup_finish_parts(
   out[j] = to_mont(x);
 }
 
-// QG_LOOKUP_HASH_BITS=<b>, read per call: keep the low b bits of the hash
-static uint32_t lookup_hash_mask() {
-  const char* hb = getenv("QG_LOOKUP_HASH_BITS");
-  if (!hb || !hb[0]) return 0xffffffffu;
-  const int b = atoi(hb);
-  if (b <= 0) return 0u;
-  return b >= 32 ? 0xffffffffu : (1u << b) - 1u;
-}
-
 // QG_LOOKUP_BLOCKS=<k>, read per call: caps the count kernel's grid (default two
 // blocks per CU), so a small input runs several grid-stride rounds
 static size_t lookup_count_blocks(qg_ctx* ctx) {
@@ -284,17 +312,23 @@ struct LkWork {
   uint32_t* d_count;
   LkState* d_st;
 };
+// the scratch a build-and-count keeps its slots, counters and state words in,
+// and the timing groups its two launches are booked under
+struct LkNames {
+  const char *slots, *count, *state, *build_group, *count_group;
+};
+static constexpr LkNames LK_MAIN = {"lk_slots", "lk_count", "lk_state", "lookup_build",
+                                    "lookup_count"};
 static LkWork lookup_build_count(qg_ctx* ctx, uint32_t ncols, const LkCols& src, size_t src_len,
-                                 const LkCols& tab, size_t tab_len) {
-  uint64_t cap = 2;
-  while (cap < 2 * (uint64_t)tab_len) cap <<= 1;
-  const uint32_t hash_mask = lookup_hash_mask();
-  uint32_t* d_slots = ctx->scratch_as<uint32_t>("lk_slots", cap);
-  uint32_t* d_count = ctx->scratch_as<uint32_t>("lk_count", tab_len);
-  LkState* d_st = ctx->scratch_as<LkState>("lk_state", 1);
+                                 const LkCols& tab, size_t tab_len, const LkNames& nm = LK_MAIN) {
+  const uint64_t cap = lk_slot_cap(tab_len);
+  const uint32_t hash_mask = lk_hash_mask_env();
+  uint32_t* d_slots = ctx->scratch_as<uint32_t>(nm.slots, cap);
+  uint32_t* d_count = ctx->scratch_as<uint32_t>(nm.count, tab_len);
+  LkState* d_st = ctx->scratch_as<LkState>(nm.state, 1);
   const uint32_t tl = (uint32_t)tab_len;
   {
-    QgTimed tm(ctx, "lookup_build");
+    QgTimed tm(ctx, nm.build_group);
     // nothing of an earlier call survives: slots, counters and the state words
     QG_HIP(hipMemsetAsync(d_slots, 0xff, cap * sizeof(uint32_t), ctx->stream));
     QG_HIP(hipMemsetAsync(&d_st->first_missing, 0xff, sizeof(unsigned long long), ctx->stream));
@@ -304,7 +338,7 @@ static LkWork lookup_build_count(qg_ctx* ctx, uint32_t ncols, const LkCols& src,
     QG_LAUNCH_CHECK();
   }
   {
-    QgTimed tm(ctx, "lookup_count");
+    QgTimed tm(ctx, nm.count_group);
     QG_HIP(hipMemsetAsync(d_count, 0, tab_len * sizeof(uint32_t), ctx->stream));
     const size_t want = div_up(src_len, LK_CBLOCK);
     const unsigned grid = (unsigned)std::min<size_t>(want, lookup_count_blocks(ctx));
@@ -343,7 +377,7 @@ struct LkHeader {
   int32_t status;  // of this rank's local argument checks
   uint32_t ncols;
   uint64_t src_len, tab_len;
-  uint64_t pad;
+  uint64_t mode;  // QG_LOOKUP_TABLE_*: 0 in the replicated mode
 };
 static_assert(sizeof(LkHeader) == 32, "lookup header is 32 bytes per rank");
 // ... and after the count
@@ -351,22 +385,6 @@ struct LkResult {
   unsigned long long first_missing;  // global source row, ~0 when none
   uint32_t err, pad;
 };
-
-// world x len >= limit, without overflow
-static bool lk_global_over(uint64_t world, uint64_t len, uint64_t limit) {
-  return len >= (limit + world - 1) / world;
-}
-
-// the caps, on the global lengths; every rank evaluates them on the agreed
-// header values, so all ranks take the same branch
-static void lookup_check_global(const qg_ctx* ctx, uint32_t ncols, size_t src_len, size_t tab_len) {
-  QG_CHECK(ncols <= LK_MAXCOLS, QG_ERR_UNSUPPORTED, "lookup multiplicities: more than 16 columns");
-  QG_CHECK(!lk_global_over(ctx->world, tab_len, 1ull << 31), QG_ERR_UNSUPPORTED,
-           "lookup multiplicities: global table of 2^31 rows or more");
-  // also what keeps a row's count inside 32 bits (k_lookup_finish_parts)
-  QG_CHECK(!lk_global_over(ctx->world, src_len, 1ull << 32), QG_ERR_UNSUPPORTED,
-           "lookup multiplicities: 2^32 global source rows or more");
-}
 
 // every rank's `mine`, in rank order; one collective
 template <class T>
@@ -407,6 +425,7 @@ static int64_t lookup_run_sharded(qg_ctx* ctx, uint32_t ncols, const LkCols& src
     comm_alltoall_bytes(ctx, w.d_count, d_recv, tab_len * sizeof(uint32_t));
     ctx->lookup_collectives++;
   }
+  ctx->lookup_exchange_bytes += lk_replicated_exchange_bytes(W, ncols, tab_len);
   {
     QgTimed tm(ctx, "lookup_finish");
     hipLaunchKernelGGL(k_lookup_finish_parts, dim3(div_up(tab_len, LK_BLOCK)), dim3(LK_BLOCK), 0,
@@ -419,6 +438,311 @@ static int64_t lookup_run_sharded(qg_ctx* ctx, uint32_t ncols, const LkCols& src
   LkResult mine{~0ull, h.err, 0};
   if (h.first_missing < (unsigned long long)src_len)
     mine.first_missing = (unsigned long long)ctx->rank * src_len + h.first_missing;
+  unsigned long long first = ~0ull;
+  uint32_t err = 0;
+  for (const LkResult& r : lookup_exchange(ctx, mine)) {
+    first = std::min(first, r.first_missing);
+    err |= r.err;
+  }
+  QG_CHECK(!err, QG_ERR_DEVICE, "lookup multiplicities: probe sequence exhausted");
+  return first == ~0ull ? -1 : (int64_t)first;
+}
+
+// ---- sharded flow, hash-partitioned table -----------------------------------
+// A payload buffer is W chunks of the LkChunk layout (lookup_plan.h); record
+// `idx` of a buffer is slot idx % max of chunk idx / max.
+struct LkRecs {
+  const uint8_t* base;
+  LkChunk ch;
+  uint64_t chunk_bytes;
+};
+QG_DEV uint2 lk_rec_meta(const LkRecs& r, uint32_t idx) {
+  const uint64_t s = idx / r.ch.max, k = idx % r.ch.max;
+  return reinterpret_cast<const uint2*>(r.base + s * r.chunk_bytes)[k];
+}
+QG_DEV LkWord lk_rec_word(const LkRecs& r, uint32_t idx, uint32_t c) {
+  const uint64_t s = idx / r.ch.max, k = idx % r.ch.max;
+  return lk_load(reinterpret_cast<const Fr*>(r.base + s * r.chunk_bytes + r.ch.col_off(c)) + k);
+}
+// the unmasked row hash of a record: lk_hash of the row it was copied from
+QG_DEV uint32_t lk_rec_hash(const LkRecs& r, uint32_t idx) {
+  uint32_t h = LK_SEED;
+  for (uint32_t c = 0; c < r.ch.ncols; c++) h = lk_mix_word(h, lk_rec_word(r, idx, c));
+  return lk_fmix(h);
+}
+QG_DEV bool lk_recs_equal(const LkRecs& A, uint32_t a, const LkRecs& B, uint32_t b) {
+  for (uint32_t c = 0; c < A.ch.ncols; c++)
+    if (!lk_same(lk_rec_word(A, a, c), lk_rec_word(B, b, c))) return false;
+  return true;
+}
+
+// Route, pass 1: one thread per row of a block of columns.  A row whose dedup
+// counter is nonzero is its tuple's representative (the lowest local row); its
+// owner goes to dest[row] (EMPTY for the other rows) and is counted, per block
+// in LDS, then with one global atomic per block and destination.
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_route_count(
+    LkCols cols, uint32_t ncols, uint64_t len, const uint32_t* __restrict__ dedup, uint32_t world,
+    uint32_t owner_mask, uint32_t* __restrict__ dest, uint32_t* __restrict__ totals) {
+  __shared__ uint32_t lc[LK_MAX_WORLD];
+  for (uint32_t d = threadIdx.x; d < world; d += LK_BLOCK) lc[d] = 0;
+  __syncthreads();
+  const uint64_t i = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (i < len) {
+    uint32_t d = LK_EMPTY;
+    if (dedup[i]) {
+      d = lk_owner(lk_hash(cols, ncols, i, 0xffffffffu), owner_mask, world);
+      atomicAdd(&lc[d], 1u);
+    }
+    dest[i] = d;
+  }
+  __syncthreads();
+  for (uint32_t d = threadIdx.x; d < world; d += LK_BLOCK)
+    if (lc[d]) atomicAdd(&totals[d], lc[d]);
+}
+
+// Route, pass 2: the representatives into the W chunks of `send` (`max` slots
+// each, meta pre-filled with ones).  A block reserves its slots of a chunk with
+// one atomicAdd on that chunk's cursor; a row's place inside the reservation is
+// its LDS ticket.  Which slot a record lands in depends on the order the blocks
+// ran in; nothing downstream does.  A slot index is checked against `max`
+// before the store (it cannot pass it: pass 1 counted the same rows).
+// SRC: meta = (global source row, local count); else (global table row, EMPTY).
+template <bool SRC>
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_route_scatter(
+    LkCols cols, uint32_t ncols, uint64_t len, const uint32_t* __restrict__ dedup,
+    const uint32_t* __restrict__ dest, uint32_t world, uint64_t row_base,
+    uint32_t* __restrict__ cursors, uint8_t* __restrict__ send, LkChunk ch,
+    LkState* __restrict__ st) {
+  __shared__ uint32_t lc[LK_MAX_WORLD];
+  for (uint32_t d = threadIdx.x; d < world; d += LK_BLOCK) lc[d] = 0;
+  __syncthreads();
+  const uint64_t i = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  const uint32_t d = i < len ? dest[i] : LK_EMPTY;
+  uint32_t ticket = 0;
+  if (d < world) ticket = atomicAdd(&lc[d], 1u);
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < world; k += LK_BLOCK)
+    if (lc[k]) lc[k] = atomicAdd(&cursors[k], lc[k]);  // count -> base of the reservation
+  __syncthreads();
+  if (d >= world) return;
+  const uint64_t slot = (uint64_t)lc[d] + ticket;
+  if (slot >= ch.max) {
+    atomicOr(&st->err, 1u);
+    return;
+  }
+  uint8_t* chunk = send + (uint64_t)d * ch.bytes();
+  reinterpret_cast<uint2*>(chunk)[slot] =
+      make_uint2((uint32_t)(row_base + i), SRC ? dedup[i] : LK_EMPTY);
+  for (uint32_t c = 0; c < ncols; c++) {
+    const LkWord w = lk_load(cols.c[c] + i);
+    uint4* q = reinterpret_cast<uint4*>(chunk + ch.col_off(c)) + 2 * slot;
+    q[0] = w.lo;
+    q[1] = w.hi;
+  }
+}
+
+// Owner build: one thread per received table record (padding slots leave at
+// once).  Open addressing over 64-bit slots (global row << 32 | record index),
+// filled with ones every call.  A claimed slot's tuple never changes; an equal
+// tuple lowers the slot with atomicMin, so the slot names the record with the
+// lowest global row whatever the thread order and the arrival order.
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_owner_build(
+    LkRecs tab, uint32_t nrec, unsigned long long* __restrict__ slots, uint64_t cap,
+    uint32_t hash_mask, LkState* __restrict__ st) {
+  const uint64_t i64 = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (i64 >= nrec) return;
+  const uint32_t idx = (uint32_t)i64;
+  const uint2 meta = lk_rec_meta(tab, idx);
+  if (meta.x == LK_EMPTY) return;
+  const unsigned long long mine = ((unsigned long long)meta.x << 32) | idx;
+  const uint64_t mask = cap - 1;
+  uint64_t s = (lk_rec_hash(tab, idx) & hash_mask) & mask;
+  for (uint64_t it = 0; it < cap; it++, s = (s + 1) & mask) {
+    const unsigned long long prev = atomicCAS(&slots[s], LK_EMPTY64, mine);
+    if (prev == LK_EMPTY64) return;
+    const uint32_t pidx = (uint32_t)prev;  // only build threads write slots
+    if (pidx < nrec && lk_recs_equal(tab, pidx, tab, idx)) {
+      atomicMin(&slots[s], mine);
+      return;
+    }
+  }
+  atomicOr(&st->err, 1u);
+}
+
+// Owner count: one thread per received source record (a separate launch: the
+// slots are complete).  The record's local count is added to the counter of
+// the winning table record; an empty slot first means the tuple is in no table
+// row, and the record's global row (the lowest of its tuple on its rank) goes
+// into first_missing.  Equal hits in a wave are NOT merged: the records were
+// deduplicated per rank, so a tuple arrives at most W times in all, spread
+// over W chunks, and a ballot round would cost more than the adds it saves.
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_owner_count(
+    LkRecs src, uint32_t nsrc, LkRecs tab, uint32_t nrec,
+    const unsigned long long* __restrict__ slots, uint64_t cap, uint32_t hash_mask,
+    uint32_t* __restrict__ count, LkState* __restrict__ st) {
+  const uint64_t i64 = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (i64 >= nsrc) return;
+  const uint32_t idx = (uint32_t)i64;
+  const uint2 meta = lk_rec_meta(src, idx);
+  if (meta.x == LK_EMPTY) return;
+  const uint64_t mask = cap - 1;
+  uint64_t s = (lk_rec_hash(src, idx) & hash_mask) & mask;
+  for (uint64_t it = 0; it < cap; it++, s = (s + 1) & mask) {
+    const unsigned long long k = slots[s];
+    if (k == LK_EMPTY64) {
+      if (meta.x < __hip_atomic_load(&st->first_missing, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMin(&st->first_missing, (unsigned long long)meta.x);
+      return;
+    }
+    const uint32_t widx = (uint32_t)k;
+    if (widx < nrec && lk_recs_equal(tab, widx, src, idx)) {
+      atomicAdd(&count[widx], meta.y);
+      return;
+    }
+  }
+  atomicOr(&st->err, 1u);
+}
+
+// Finish: the counters came back in the positions the records were sent in;
+// the meta kept in the send buffer names each position's row.  out was zeroed:
+// a row that was no representative, or whose tuple a lower row won, stays 0.
+__global__ __launch_bounds__(LK_BLOCK) void k_lookup_finish_routed(
+    LkRecs sent, const uint32_t* __restrict__ back, uint32_t nrec, uint64_t row_base,
+    uint32_t tab_len, Fr* __restrict__ out) {
+  const uint64_t i64 = (uint64_t)blockIdx.x * LK_BLOCK + threadIdx.x;
+  if (i64 >= nrec) return;
+  const uint2 meta = lk_rec_meta(sent, (uint32_t)i64);
+  if (meta.x == LK_EMPTY) return;
+  const uint64_t local = (uint64_t)meta.x - row_base;
+  if (local >= tab_len) return;  // this rank wrote the meta: cannot happen
+  Fr x = Fr::zero();
+  x.v[0] = back[i64];
+  out[local] = to_mont(x);
+}
+
+static constexpr LkNames LK_DEDUP_TAB = {"lkp_tslots", "lkp_tcount", "lkp_tstate", "lookup_dedup",
+                                         "lookup_dedup"};
+static constexpr LkNames LK_DEDUP_SRC = {"lkp_sslots", "lkp_scount", "lkp_sstate", "lookup_dedup",
+                                         "lookup_dedup"};
+
+// this rank's block of the global m into d_out; returns the lowest GLOBAL source
+// row that is in no table row, or -1 (the same value on every rank)
+static int64_t lookup_run_partitioned(qg_ctx* ctx, uint32_t ncols, const LkCols& src,
+                                      size_t src_len, const LkCols& tab, size_t tab_len,
+                                      Fr* d_out) {
+  const uint32_t W = (uint32_t)ctx->world;
+  QG_CHECK(W <= LK_MAX_WORLD, QG_ERR_UNSUPPORTED,
+           "lookup multiplicities: partitioned table on more than 1024 ranks");
+  const uint32_t hash_mask = lk_hash_mask_env(), owner_mask = lk_owner_mask_env();
+  hipStream_t st = ctx->stream;
+  // 2. local dedup: counter > 0 exactly at the lowest local row of each tuple
+  const LkWork dt = lookup_build_count(ctx, ncols, tab, tab_len, tab, tab_len, LK_DEDUP_TAB);
+  const LkWork ds = lookup_build_count(ctx, ncols, src, src_len, src, src_len, LK_DEDUP_SRC);
+  // 3. owners and per-destination counts: [table W][source W]
+  uint32_t* d_dest_t = ctx->scratch_as<uint32_t>("lkp_tdest", tab_len);
+  uint32_t* d_dest_s = ctx->scratch_as<uint32_t>("lkp_sdest", src_len);
+  uint32_t* d_totals = ctx->scratch_as<uint32_t>("lkp_totals", 4 * (size_t)W);  // + cursors
+  uint32_t* d_cursors = d_totals + 2 * (size_t)W;
+  uint32_t* d_sizes = ctx->scratch_as<uint32_t>("lkp_sizes", 2 * (size_t)W * W);
+  const unsigned grid_t = div_up(tab_len, LK_BLOCK), grid_s = div_up(src_len, LK_BLOCK);
+  {
+    QgTimed tm(ctx, "lookup_route");
+    QG_HIP(hipMemsetAsync(d_totals, 0, 4 * (size_t)W * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_lookup_route_count, dim3(grid_t), dim3(LK_BLOCK), 0, st, tab, ncols,
+                       (uint64_t)tab_len, dt.d_count, W, owner_mask, d_dest_t, d_totals);
+    QG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_lookup_route_count, dim3(grid_s), dim3(LK_BLOCK), 0, st, src, ncols,
+                       (uint64_t)src_len, ds.d_count, W, owner_mask, d_dest_s, d_totals + W);
+    QG_LAUNCH_CHECK();
+  }
+  // 4. size agreement
+  std::vector<uint32_t> sizes(2 * (size_t)W * W);
+  {
+    QgTimed tm(ctx, "lookup_exchange");
+    comm_allgather_bytes(ctx, d_totals, d_sizes, 2 * (size_t)W * sizeof(uint32_t));
+    ctx->lookup_collectives++;
+  }
+  QG_HIP(hipMemcpyAsync(sizes.data(), d_sizes, sizes.size() * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost, st));
+  ctx->sync();
+  const LkPartPlan p = lk_part_plan(W, ncols, src_len, tab_len, lk_pair_max(sizes.data(), W));
+  const uint32_t* own = sizes.data() + (size_t)ctx->rank * 2 * W;
+  for (uint32_t d = 0; d < W; d++) {
+    ctx->lookup_routed_tab += own[d];
+    ctx->lookup_routed_src += own[W + d];
+  }
+  // 5. scatter into the send buffers (meta all ones: padding, and nothing of an
+  //    earlier call)
+  uint8_t* d_send_t = ctx->scratch_as<uint8_t>("lkp_tsend", p.tab_buf_bytes);
+  uint8_t* d_recv_t = ctx->scratch_as<uint8_t>("lkp_trecv", p.tab_buf_bytes);
+  uint8_t* d_send_s = ctx->scratch_as<uint8_t>("lkp_ssend", p.src_buf_bytes);
+  uint8_t* d_recv_s = ctx->scratch_as<uint8_t>("lkp_srecv", p.src_buf_bytes);
+  LkState* d_st = ctx->scratch_as<LkState>("lkp_state", 1);
+  {
+    QgTimed tm(ctx, "lookup_route");
+    QG_HIP(hipMemsetAsync(&d_st->first_missing, 0xff, sizeof(unsigned long long), st));
+    QG_HIP(hipMemsetAsync(&d_st->err, 0, 2 * sizeof(uint32_t), st));
+    for (uint32_t d = 0; d < W; d++) {
+      QG_HIP(hipMemsetAsync(d_send_t + d * p.tab.bytes(), 0xff, p.tab.max * LK_META_BYTES, st));
+      QG_HIP(hipMemsetAsync(d_send_s + d * p.src.bytes(), 0xff, p.src.max * LK_META_BYTES, st));
+    }
+    hipLaunchKernelGGL(k_lookup_route_scatter<false>, dim3(grid_t), dim3(LK_BLOCK), 0, st, tab,
+                       ncols, (uint64_t)tab_len, dt.d_count, d_dest_t, W,
+                       (uint64_t)ctx->rank * tab_len, d_cursors, d_send_t, p.tab, d_st);
+    QG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_lookup_route_scatter<true>, dim3(grid_s), dim3(LK_BLOCK), 0, st, src,
+                       ncols, (uint64_t)src_len, ds.d_count, d_dest_s, W,
+                       (uint64_t)ctx->rank * src_len, d_cursors + W, d_send_s, p.src, d_st);
+    QG_LAUNCH_CHECK();
+  }
+  // 6. payload
+  {
+    QgTimed tm(ctx, "lookup_exchange");
+    comm_alltoall_bytes(ctx, d_send_t, d_recv_t, p.tab.bytes());
+    comm_alltoall_bytes(ctx, d_send_s, d_recv_s, p.src.bytes());
+    ctx->lookup_collectives += 2;
+  }
+  // 7, 8. the owner matches what it received
+  unsigned long long* d_slots = ctx->scratch_as<unsigned long long>("lkp_oslots", p.cap);
+  uint32_t* d_count = ctx->scratch_as<uint32_t>("lkp_ocount", p.tab_records);
+  uint32_t* d_back = ctx->scratch_as<uint32_t>("lkp_back", p.tab_records);
+  const LkRecs rt{d_recv_t, p.tab, p.tab.bytes()}, rs{d_recv_s, p.src, p.src.bytes()};
+  const uint32_t nrec = (uint32_t)p.tab_records;
+  const uint32_t nsrc = (uint32_t)p.src_records;
+  {
+    QgTimed tm(ctx, "lookup_owner");
+    QG_HIP(hipMemsetAsync(d_slots, 0xff, p.cap * sizeof(unsigned long long), st));
+    QG_HIP(hipMemsetAsync(d_count, 0, p.tab_records * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_lookup_owner_build, dim3(div_up(nrec, LK_BLOCK)), dim3(LK_BLOCK), 0, st,
+                       rt, nrec, d_slots, p.cap, hash_mask, d_st);
+    QG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_lookup_owner_count, dim3(div_up(nsrc, LK_BLOCK)), dim3(LK_BLOCK), 0, st,
+                       rs, nsrc, rt, nrec, d_slots, p.cap, hash_mask, d_count, d_st);
+    QG_LAUNCH_CHECK();
+  }
+  // 9. the counters go back in arrival positions
+  {
+    QgTimed tm(ctx, "lookup_exchange");
+    comm_alltoall_bytes(ctx, d_count, d_back, p.return_bytes);
+    ctx->lookup_collectives++;
+  }
+  ctx->lookup_exchange_bytes += p.exchange_bytes;
+  {
+    QgTimed tm(ctx, "lookup_finish");
+    QG_HIP(hipMemsetAsync(d_out, 0, tab_len * sizeof(Fr), st));
+    const LkRecs sent{d_send_t, p.tab, p.tab.bytes()};
+    hipLaunchKernelGGL(k_lookup_finish_routed, dim3(div_up(nrec, LK_BLOCK)), dim3(LK_BLOCK), 0, st,
+                       sent, d_back, nrec, (uint64_t)ctx->rank * tab_len, (uint32_t)tab_len, d_out);
+    QG_LAUNCH_CHECK();
+  }
+  // 10. lowest missing row and error words (the two dedups' and the owner's)
+  LkState h, ht, hs;
+  QG_HIP(hipMemcpyAsync(&h, d_st, sizeof(h), hipMemcpyDeviceToHost, st));
+  QG_HIP(hipMemcpyAsync(&ht, dt.d_st, sizeof(ht), hipMemcpyDeviceToHost, st));
+  QG_HIP(hipMemcpyAsync(&hs, ds.d_st, sizeof(hs), hipMemcpyDeviceToHost, st));
+  ctx->sync();
+  // first_missing holds a global row already (below 2^32) or all ones
+  const LkResult mine{h.first_missing, h.err | ht.err | hs.err, 0};
   unsigned long long first = ~0ull;
   uint32_t err = 0;
   for (const LkResult& r : lookup_exchange(ctx, mine)) {
@@ -501,18 +825,20 @@ int qg_lookup_multiplicities(qg_ctx* ctx, uint32_t ncols, const uint64_t* const*
   });
 }
 
-int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols, const qg_buf* const* src_cols,
-                                 size_t src_len, const qg_buf* const* tab_cols, size_t tab_len,
-                                 qg_buf* out_m, int64_t* first_missing) {
+int qg_lookup_multiplicities_dev_ex(qg_ctx* ctx, uint32_t ncols, const qg_buf* const* src_cols,
+                                    size_t src_len, const qg_buf* const* tab_cols, size_t tab_len,
+                                    qg_buf* out_m, int64_t* first_missing, uint32_t table_mode) {
   if (!ctx) return QG_ERR_INVALID;
   return qg_guard(ctx, [&] {
     LkCols src{}, tab{};
     if (!ctx->sharded) {
+      lk_check_mode(table_mode);
       QG_CHECK(src_cols && tab_cols && out_m, QG_ERR_INVALID, "null argument");
       lookup_check_lengths(ncols, src_len, tab_len);
       lookup_check_dev_args(ncols, src_cols, src_len, tab_cols, tab_len, out_m, true, src, tab);
       QG_HIP(hipSetDevice(ctx->device));
       if (first_missing) *first_missing = -1;
+      // one context holds the whole table: both modes are the same flow
       const int64_t miss = lookup_run(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
       lookup_report(miss, first_missing);
       return;
@@ -521,9 +847,10 @@ int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols, const qg_buf* cons
     // end the call on their own: their status travels in the header, so that
     // every rank leaves here together or goes on together.
     QG_HIP(hipSetDevice(ctx->device));
-    LkHeader mine{QG_OK, ncols, (uint64_t)src_len, (uint64_t)tab_len, 0};
+    LkHeader mine{QG_OK, ncols, (uint64_t)src_len, (uint64_t)tab_len, (uint64_t)table_mode};
     std::string why;
     try {
+      lk_check_mode(table_mode);
       const bool under = ncols <= LK_MAXCOLS && !lk_global_over(ctx->world, tab_len, 1ull << 31) &&
                          !lk_global_over(ctx->world, src_len, 1ull << 32);
       lookup_check_dev_args(ncols, src_cols, src_len, tab_cols, tab_len, out_m, under, src, tab);
@@ -540,12 +867,25 @@ int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols, const qg_buf* cons
                QG_ERR_INVALID,
                "lookup multiplicities: rank " + std::to_string(r) +
                    " passed another ncols, src_len or tab_len (every rank passes the same)");
+      QG_CHECK(all[r].mode == table_mode, QG_ERR_INVALID,
+               "lookup multiplicities: rank " + std::to_string(r) +
+                   " passed another table mode (every rank passes the same)");
     }
-    lookup_check_global(ctx, ncols, src_len, tab_len);
+    lk_check_global(ctx->world, ncols, src_len, tab_len);
     if (first_missing) *first_missing = -1;
-    const int64_t miss = lookup_run_sharded(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
+    const int64_t miss =
+        table_mode == QG_LOOKUP_TABLE_PARTITIONED
+            ? lookup_run_partitioned(ctx, ncols, src, src_len, tab, tab_len, out_m->d)
+            : lookup_run_sharded(ctx, ncols, src, src_len, tab, tab_len, out_m->d);
     lookup_report(miss, first_missing);
   });
+}
+
+int qg_lookup_multiplicities_dev(qg_ctx* ctx, uint32_t ncols, const qg_buf* const* src_cols,
+                                 size_t src_len, const qg_buf* const* tab_cols, size_t tab_len,
+                                 qg_buf* out_m, int64_t* first_missing) {
+  return qg_lookup_multiplicities_dev_ex(ctx, ncols, src_cols, src_len, tab_cols, tab_len, out_m,
+                                         first_missing, QG_LOOKUP_TABLE_REPLICATED);
 }
 
 }  // extern "C"

@@ -13,6 +13,20 @@ device time by kernel group (HIP events), one part per run:
                        loopback communicator SHARING ONE GPU, so the figures are
                        contended (the ranks' kernels interleave and a collective
                        waits for the slowest rank): not multi-GPU figures
+  --part modes         the two sharded table modes (replicated / partitioned,
+                       qg_lookup_multiplicities_dev_ex) at world 4 on two shapes:
+                       "small_table" (2^16 global table rows under 2^log-src
+                       source rows) and "table_is_source" (2^log-big distinct
+                       rows per rank in both).  Per rank: device time by kernel
+                       group, lookup_exchange_bytes per call and the lookup's
+                       arena scratch.  Each rank drives one context per mode and
+                       alternates the modes call by call in one process.  The
+                       same caveat: the loopback ranks share one GPU and their
+                       collectives are device copies, so the times describe work
+                       done, not link time.  On a library without the _ex entry
+                       (QG_LIB = the parent's build) only "replicated" is run;
+                       --modes replicated runs it alone on this build too, which
+                       is the like-for-like comparison of two builds.
   --merge a.json ...   one object from the parts' outputs (--out writes it)
 
   QG_LIB=<libquill_gpu.so> python quill-zkvm_amd/micro/lookup_sharded_cost.py
@@ -196,9 +210,123 @@ def part_sharded(args):
     return res
 
 
+MODE_GROUPS = {"replicated": SHARD_GROUPS,
+               "partitioned": ("lookup_dedup", "lookup_route", "lookup_exchange", "lookup_owner",
+                               "lookup_finish")}
+
+
+def part_modes(args):
+    import ctypes as C
+    import quill_amd as q
+    from quill_amd._lib import check
+    L = q.lib()
+    has_ex = hasattr(L, "qg_lookup_multiplicities_dev_ex")
+    modes = ("replicated", "partitioned") if has_ex else ("replicated",)
+    if args.modes:
+        modes = tuple(m for m in modes if m in args.modes.split(","))
+    world = 4
+    res = {"world": world, "columns": 2, "modes": list(modes), "reps_per_median": args.reps,
+           "medians": args.medians,
+           "note": "loopback ranks are host threads sharing one GPU and their collectives are "
+                   "device copies: the times describe work done, not link time; exchange "
+                   "groups include the wait for the slowest rank"}
+
+    def count(dev, sc, dc, out, mode):
+        miss = C.c_int64(-1)
+        sp = (C.c_void_p * 2)(*[v.h.value for v in sc])
+        tp = (C.c_void_p * 2)(*[v.h.value for v in dc])
+        if has_ex:
+            rc = L.qg_lookup_multiplicities_dev_ex(dev.h, 2, sp, sc[0].n, tp, dc[0].n, out.h,
+                                                   C.byref(miss), 0 if mode == "replicated" else 1)
+        else:
+            rc = L.qg_lookup_multiplicities_dev(dev.h, 2, sp, sc[0].n, tp, dc[0].n, out.h,
+                                                C.byref(miss))
+        check(rc, dev.h)
+
+    def counter(dev, name):
+        v = C.c_uint64()
+        check(L.qg_ctx_counter(dev.h, name.encode(), C.byref(v)), dev.h)
+        return v.value
+
+    shapes = {}
+    ns, nt = 1 << args.log_src, 1 << 16
+    rnd = np.random.RandomState(16)
+    idx = rnd.randint(0, nt, size=ns).astype(np.uint64)
+    shapes["small_table"] = (idx, np.arange(nt, dtype=np.uint64),
+                             np.bincount(idx.astype(np.int64), minlength=nt).astype(np.uint64))
+    nb = world << args.log_big
+    shapes["table_is_source"] = (np.random.RandomState(20).permutation(nb).astype(np.uint64),
+                                 np.arange(nb, dtype=np.uint64), np.ones(nb, dtype=np.uint64))
+    for name, (src, tab, want) in shapes.items():
+        S, T = len(src) // world, len(tab) // world
+        groups = {m: q.Device.loopback_group(world) for m in modes}
+        out, err = [None] * world, []
+
+        def body(rank, src=src, tab=tab, want=want, S=S, T=T, groups=groups):
+            try:
+                sl, tl = slice(rank * S, (rank + 1) * S), slice(rank * T, (rank + 1) * T)
+                ctx = {}
+                for m in modes:
+                    dev = q.Device(0)
+                    dev.attach_loopback(groups[m], rank)
+                    sc = [q.DeviceVec.from_u64(dev, c) for c in (src[sl], src[sl] ^ np.uint64(42))]
+                    dc = [q.DeviceVec.from_u64(dev, c) for c in (tab[tl], tab[tl] ^ np.uint64(42))]
+                    o_ = q.DeviceVec(dev, T)
+                    count(dev, sc, dc, o_, m)  # warm, and checked right before it is timed
+                    ref = q.DeviceVec.from_u64(dev, want[tl])
+                    assert o_.first_mismatch(ref) == -1, "multiplicities differ from the host count"
+                    ref.close()
+                    ctx[m] = (dev, sc, dc, o_)
+                runs = {m: [] for m in modes}
+                bytes_per_call = {}
+                for _ in range(args.medians):
+                    samples = {m: [] for m in modes}
+                    for _ in range(args.reps):
+                        for m in modes:  # interleaved
+                            dev, sc, dc, o_ = ctx[m]
+                            b0 = (counter(dev, "lookup_exchange_bytes") if has_ex else 0)
+                            samples[m].append(timed(dev, lambda: count(dev, sc, dc, o_, m),
+                                                    MODE_GROUPS[m]))
+                            if has_ex:
+                                bytes_per_call[m] = counter(dev, "lookup_exchange_bytes") - b0
+                    for m in modes:
+                        med = {g: statistics.median(x[g] for x in samples[m])
+                               for g in MODE_GROUPS[m]}
+                        med["total_ms"] = statistics.median(sum(x.values()) for x in samples[m])
+                        runs[m].append(med)
+                r = {}
+                for m in modes:
+                    dev = ctx[m][0]
+                    r[m] = {k: spread([x[k] for x in runs[m]])
+                            for k in MODE_GROUPS[m] + ("total_ms",)}
+                    if has_ex:
+                        r[m]["lookup_exchange_bytes_per_call"] = bytes_per_call[m]
+                        r[m]["lookup_scratch_bytes"] = counter(dev, "lookup_scratch_bytes")
+                    for v in ctx[m][1] + ctx[m][2] + [ctx[m][3]]:
+                        v.close()
+                    dev.close()
+                out[rank] = r
+            except Exception as e:
+                err.append(e)
+        ths = [threading.Thread(target=body, args=(r,)) for r in range(world)]
+        for t in ths:
+            t.start()
+        for t in ths:
+            t.join()
+        for g in groups.values():
+            q.lib().qg_loopback_destroy(g)
+        if err:
+            raise err[0]
+        res[name] = {"source_rows_per_rank": S, "table_rows_per_rank": T, "ranks": out}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("single", "materialiser", "sharded"))
+    ap.add_argument("--part", choices=("single", "materialiser", "sharded", "modes"))
+    ap.add_argument("--log-big", type=int, default=20)
+    ap.add_argument("--modes", default=None,
+                    help="part modes: comma list (replicated alone compares two builds)")
     ap.add_argument("--merge", nargs="*")
     ap.add_argument("--log-src", type=int, default=22)
     ap.add_argument("--reps", type=int, default=5)
@@ -213,7 +341,8 @@ def main():
             with open(f) as fh:
                 res[os.path.splitext(os.path.basename(f))[0]] = json.load(fh)
     else:
-        res = part_materialiser(args) if args.part == "materialiser" else part_sharded(args)
+        res = {"materialiser": part_materialiser, "sharded": part_sharded,
+               "modes": part_modes}[args.part](args)
     txt = json.dumps(res, indent=1, sort_keys=True)
     print(txt)
     if args.out:

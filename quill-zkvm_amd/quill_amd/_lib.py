@@ -62,6 +62,9 @@ class ExprOp(C.Structure):
     _fields_ = [("op", C.c_uint32), ("arg", C.c_uint32)]
 
 
+# table_mode of qg_lookup_multiplicities_dev_ex
+LOOKUP_TABLE_MODES = {"replicated": 0, "partitioned": 1}
+
 P = C.c_void_p
 U64P = C.POINTER(C.c_uint64)
 U8P = C.POINTER(C.c_uint8)
@@ -168,6 +171,8 @@ PROTOTYPES = {
                                            SZ, U64P, C.POINTER(C.c_int64)]),
     "qg_lookup_multiplicities_dev": (C.c_int, [P, C.c_uint32, C.POINTER(P), SZ, C.POINTER(P), SZ,
                                                P, C.POINTER(C.c_int64)]),
+    "qg_lookup_multiplicities_dev_ex": (C.c_int, [P, C.c_uint32, C.POINTER(P), SZ, C.POINTER(P),
+                                                  SZ, P, C.POINTER(C.c_int64), C.c_uint32]),
     "qg_expr_column": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(U64P), C.POINTER(ExprOp), SZ,
                                  U64P, SZ, U64P]),
     "qg_expr_column_dev": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(P), C.POINTER(ExprOp),

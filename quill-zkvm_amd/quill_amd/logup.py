@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import LOOKUP_TABLE_MODES, check, lib
 from .device import Device, DeviceVec
 from .field import R_MOD, eq_eval, fr_c, fr_from_mont_limbs, fr_inv, fr_list, u64p
 from .hyperplonk import (SumcheckProof, VirtualPolyExpr, VirtualPolynomialStore, _default_device,
@@ -120,7 +120,7 @@ def _lookup_columns(store: VirtualPolynomialStore, cols, materialise: bool, dev:
 
 def lookup_multiplicities(source_store: VirtualPolynomialStore, source_cols,
                           dest_store: VirtualPolynomialStore, dest_cols, dev: Device = None,
-                          materialise: bool = False):
+                          materialise: bool = False, table: str = "replicated"):
     """The multiplicity column of a Logup lookup (what lookup.rs:186-193 builds
     by hand): m[j] = number of source rows equal to table row j, a row being the
     tuple of its columns; a tuple the table holds at several rows is counted at
@@ -132,8 +132,15 @@ def lookup_multiplicities(source_store: VirtualPolynomialStore, source_cols,
     Host stores return a list of ints (qg_lookup_multiplicities), device stores
     a DeviceVec (qg_lookup_multiplicities_dev).  On sharded device stores the
     call is collective: every rank passes its blocks and receives its block of
-    the global column.  A source row that is in no table row raises
-    QuillGpuError(QG_ERR_ASSERT) naming the lowest such (global) row."""
+    the global column.  `table` names the sharded flow: "replicated" gathers the
+    table on every rank, "partitioned" matches every tuple on an owner rank
+    chosen by its hash (qg_lookup_multiplicities_dev_ex); the column is the
+    same, and on unsharded stores so is the flow.  A source row that is in no
+    table row raises QuillGpuError(QG_ERR_ASSERT) naming the lowest such
+    (global) row."""
+    if table not in LOOKUP_TABLE_MODES:
+        raise ValueError("lookup_multiplicities: table must be 'replicated' or 'partitioned', "
+                         "not %r" % (table,))
     if len(source_cols) != len(dest_cols):
         raise ValueError("The number of source and destination columns must be equal")
     if source_store.on_device != dest_store.on_device:
@@ -152,8 +159,9 @@ def lookup_multiplicities(source_store: VirtualPolynomialStore, source_cols,
             sp = (C.c_void_p * max(k, 1))(*[v.h.value for v in sc])
             tp = (C.c_void_p * max(k, 1))(*[v.h.value for v in dc])
             try:
-                check(lib().qg_lookup_multiplicities_dev(d.h, k, sp, ns, tp, nt, out.h,
-                                                         C.byref(miss)), d.h)
+                check(lib().qg_lookup_multiplicities_dev_ex(d.h, k, sp, ns, tp, nt, out.h,
+                                                            C.byref(miss),
+                                                            LOOKUP_TABLE_MODES[table]), d.h)
             except Exception:
                 out.close()
                 raise
@@ -402,7 +410,7 @@ class LookupProof:
 
     @staticmethod
     def prove(source_store: VirtualPolynomialStore, source_cols, dest_store: VirtualPolynomialStore,
-              dest_cols, multiplicities, transcript: Transcript, pcs):
+              dest_cols, multiplicities, transcript: Transcript, pcs, table: str = "replicated"):
         """lookup.rs:28-84 -> (proof, (source point, dest point)).
         multiplicities=None: the column is counted on the device
         (lookup_multiplicities with materialise=True: columns that are not plain
@@ -411,14 +419,15 @@ class LookupProof:
         transcript, so the proof and the transcript are those of a caller who
         supplied the same column; a source row that is in no table row raises
         there.  Sharded device stores: every rank holds its block of each table
-        and calls this collectively."""
+        and calls this collectively; `table` picks the sharded flow of the count
+        (lookup_multiplicities)."""
         assert len(source_cols) == len(dest_cols), \
             "The number of source and destination columns must be equal"
         n = len(source_cols)
         if multiplicities is None:
             assert n > 0, "Lookup must be applied to at least one column"
             m = lookup_multiplicities(source_store, source_cols, dest_store, dest_cols, pcs.dev,
-                                      materialise=True)
+                                      materialise=True, table=table)
             multiplicities = dest_store.new_virtual_from_input(dest_store.allocate_polynomial(m))
         transcript.append_u64(n)
         assert n > 0, "Lookup must be applied to at least one column"
