@@ -45,6 +45,7 @@ extern "C" {
 typedef struct qg_ctx qg_ctx;
 typedef struct qg_srs qg_srs;
 typedef struct qg_buf qg_buf;
+struct qg_kzg_vk; /* the verifier's part of the CRS, defined with qg_kzg_verify */
 
 /* ---------------------------------------------------------------- context */
 /* Device context (one HIP device, its streams and scratch). */
@@ -113,7 +114,10 @@ int qg_g1_serialize(const uint64_t xy[8], uint8_t infinity, uint8_t out[64]);
  * limbs per point (n x 8 uint64) + per-point infinity flags (may be NULL).
  * The device keeps the bases affine (this removes the per-commit
  * `into_affine` of every SRS point, kzg.rs:67-71) together with the MSM's
- * precomputed window-shifted copies. */
+ * precomputed window-shifted copies.  The limbs are trusted: nothing is
+ * checked.  Points from a file or another party go through qg_srs_import
+ * (ark-serialize bytes, every point validated) or are checked afterwards with
+ * qg_srs_validate / qg_srs_check_powers. */
 int qg_srs_upload(qg_ctx* ctx, const uint64_t* affine_xy, const uint8_t* infinity, size_t n,
                   qg_srs** out);
 /* Bases for one-shot MSMs (VariableBaseMSM::msm_unchecked over bases used
@@ -142,6 +146,52 @@ int qg_srs_window_info(const qg_srs* srs, int* c, int* windows);
 /* Copy bases [offset, offset+n) back to the host (affine, Montgomery). */
 int qg_srs_download(const qg_srs* srs, size_t offset, size_t n, uint64_t* affine_xy,
                     uint8_t* infinity);
+
+/* ---- SRS as ark-serialize bytes (CanonicalSerialize of G1Affine, no length
+ * prefix).  Coordinates are canonical little-endian; two flag bits sit in the
+ * top two bits of the LAST byte of a point: bit 7 = y is the larger root
+ * (y > p - y), bit 6 = the point at infinity (every other bit zero). */
+#define QG_G1_UNCOMPRESSED 0 /* 64 B/point: x || y LE, flags in y's top byte == qg_g1_serialize */
+#define QG_G1_COMPRESSED 1   /* 32 B/point: x LE, flags in x's top byte */
+#define QG_SRS_ONESHOT 1u    /* one table, as qg_bases_upload */
+/* why a point was refused (bad_reason) */
+#define QG_SRS_BAD_NONCANONICAL 1u /* coordinate >= p */
+#define QG_SRS_BAD_INFINITY 2u     /* infinity flag with nonzero coordinate bits or the sign flag */
+#define QG_SRS_BAD_NOT_SQUARE 3u   /* x^3 + 3 is not a square (compressed) */
+#define QG_SRS_BAD_NOT_ON_CURVE 4u /* y^2 != x^3 + 3 (uncompressed, and table rows) */
+#define QG_SRS_BAD_SIGN_FLAG 5u    /* sign flag inconsistent with y (uncompressed) */
+/* `n` points from `bytes` (n * 64 or n * 32 bytes), decoded, decompressed and
+ * validated on the device with the rules of CanonicalDeserialize under
+ * Validate::Yes (G1 has cofactor 1: on the curve is in the group), then the
+ * tables of qg_srs_upload (flags = 0) or qg_bases_upload (QG_SRS_ONESHOT).
+ * A bad point: QG_ERR_INVALID, *out = NULL, *bad_index = the LOWEST bad index,
+ * *bad_reason = that point's reason (both pointers may be NULL), and
+ * qg_last_error says both in words.  On success *bad_reason = 0. */
+int qg_srs_import(qg_ctx* ctx, const uint8_t* bytes, size_t n, int format, uint32_t flags,
+                  qg_srs** out, uint64_t* bad_index, uint32_t* bad_reason);
+/* Bases [offset, offset+n) as bytes of `format` into out (n * 64 or n * 32). */
+int qg_srs_export(const qg_srs* srs, size_t offset, size_t n, int format, uint8_t* out);
+/* The canonical and on-curve checks over the bases a handle holds, however it
+ * was made (qg_srs_upload and qg_bases_upload check nothing).  A bad row:
+ * QG_ERR_INVALID with the lowest index and its reason as for qg_srs_import
+ * (QG_SRS_BAD_NONCANONICAL, QG_SRS_BAD_NOT_ON_CURVE, or QG_SRS_BAD_INFINITY
+ * for an infinity flag over nonzero coordinates). */
+int qg_srs_validate(qg_ctx* ctx, const qg_srs* srs, uint64_t* bad_index, uint32_t* bad_reason);
+/* Are the bases P_0 .. P_{N-1} the powers [tau^i] g of the verifying key, i.e.
+ * P_0 == vk.g1 and P_{i+1} = tau P_i for the tau of vk.g2_tau?  One random
+ * linear combination: rho_i = the low 128 bits (LE) of BLAKE3(seed || u64_le(i)),
+ * A = sum_{i<N-1} rho_i P_i, B = sum_{1<=j<N} rho_{j-1} P_j (two MSMs over the
+ * same bases), and e(A, tau g2) e(-B, g2) == 1 on the host.  *ok = 1 / 0;
+ * QG_ERR_INVALID only for bad arguments or a malformed vk.  N == 1 checks P_0.
+ * SOUNDNESS: the seed must be unknown to whoever produced the SRS; a wrong SRS
+ * then passes with probability about 2^-128.  seed == NULL draws 32 bytes from
+ * std::random_device.  A fixed seed is for reproducible tests only.
+ * On a sharded context the call is collective: rank r holds the global range
+ * [r n, (r+1) n) (n = qg_srs_len, N = world n), the multipliers are indexed
+ * globally, rank 0's seed and its P_0 verdict are shared, and every rank
+ * returns the same *ok. */
+int qg_srs_check_powers(qg_ctx* ctx, const qg_srs* srs, const struct qg_kzg_vk* vk,
+                        const uint8_t seed[32], int* ok);
 
 /* ---------------------------------------------------------------- device vectors */
 /* Fr vectors resident in HBM (for callers that keep witnesses on the device). */

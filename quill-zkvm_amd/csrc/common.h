@@ -333,6 +333,16 @@ G1Affine msm_device(qg_ctx* ctx, const qg_srs* srs, const Fr* d_scalars, size_t 
 std::vector<G1Affine> msm_device_batch(qg_ctx* ctx, const qg_srs* srs,
                                        const std::vector<const Fr*>& scalars,
                                        const std::vector<size_t>& ns);
+// SRS handle with its window geometry and (uninitialised) tables; the tables
+// from table 0's points in `base`, queued on the context stream; rows back as
+// affine points (msm.hip; shared with the byte import / export of srs_io.hip)
+qg_srs* srs_alloc(qg_ctx* ctx, size_t n, bool oneshot = false);
+void srs_build_tables(qg_ctx* ctx, qg_srs* srs, const G1Affine* base);
+void srs_unpack_rows(qg_ctx* ctx, const qg_srs* srs, size_t offset, size_t n, G1Affine* d_out);
+// host pairing side of qg_srs_check_powers (pairing.hip): the validated g1 of a
+// verifying key, and e(A, g2_tau) e(-B, g2) == 1
+G1Affine kzg_vk_g1(const qg_kzg_vk* vk);
+bool kzg_tau_relation(const qg_kzg_vk* vk, const G1Affine& A, const G1Affine& B);
 void fr_upload(qg_ctx* ctx, Fr* d, const uint64_t* h, size_t n);
 void fr_download(qg_ctx* ctx, uint64_t* h, const Fr* d, size_t n);
 // affine G1 -> ABI (xy Montgomery limbs + inf flag)

@@ -1501,7 +1501,7 @@ __global__ void k_import_bases(const uint64_t* __restrict__ xy, const uint8_t* _
 
 // table 0 arrives as arkworks affine points (R = 2^256) in `base`; every row
 // is kept in the R = 2^261 domain of the 29-bit-limb accumulation (curve29.h)
-static void srs_build_tables(qg_ctx* ctx, qg_srs* srs, const G1Affine* base) {
+void srs_build_tables(qg_ctx* ctx, qg_srs* srs, const G1Affine* base) {
   QgTimed tm(ctx, "srs_shift");
   hipLaunchKernelGGL(k_srs_pack, dim3(div_up(srs->n, 256)), dim3(256), 0, ctx->stream, base,
                      srs->n, srs->d_table);
@@ -1513,7 +1513,7 @@ static void srs_build_tables(qg_ctx* ctx, qg_srs* srs, const G1Affine* base) {
   }
 }
 
-static qg_srs* srs_alloc(qg_ctx* ctx, size_t n, bool oneshot = false) {
+qg_srs* srs_alloc(qg_ctx* ctx, size_t n, bool oneshot) {
   qg_srs* srs = new qg_srs();
   srs->ctx = ctx;
   srs->n = n;
@@ -1536,6 +1536,14 @@ static qg_srs* srs_alloc(qg_ctx* ctx, size_t n, bool oneshot = false) {
     throw Error(QG_ERR_OOM, "qg_srs: hipMalloc of the window tables failed");
   }
   return srs;
+}
+
+// bases [offset, offset + n) as arkworks affine points into d_out, queued on the
+// context stream (qg_srs_download, qg_srs_export)
+void srs_unpack_rows(qg_ctx* ctx, const qg_srs* srs, size_t offset, size_t n, G1Affine* d_out) {
+  hipLaunchKernelGGL(k_srs_unpack, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,
+                     srs->d_table + offset, n, d_out);
+  QG_LAUNCH_CHECK();
 }
 
 // One MSM of a batch after bucketing + accumulation: its partial slots and
@@ -2608,9 +2616,7 @@ int qg_srs_download(const qg_srs* srs, size_t offset, size_t n, uint64_t* affine
     QG_HIP(hipSetDevice(ctx->device));
     std::vector<G1Affine> h(n);
     G1Affine* d = ctx->scratch_as<G1Affine>("srs_download", n);
-    hipLaunchKernelGGL(k_srs_unpack, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,
-                       srs->d_table + offset, n, d);
-    QG_LAUNCH_CHECK();
+    srs_unpack_rows(ctx, srs, offset, n, d);
     QG_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
     for (size_t i = 0; i < n; i++) g1_export(h[i], affine_xy + 8 * i, infinity ? infinity + i : nullptr);

@@ -369,6 +369,17 @@ Fr eval_pr(const std::vector<Fr>& r, Fr x) {
 }
 
 }  // namespace
+
+// the whole key is validated (g1 on the curve, both G2 points in the subgroup)
+G1Affine kzg_vk_g1(const qg_kzg_vk* vk) { return vk_in(vk).g1; }
+
+// tau A == B for the tau of the key, as e(A, g2_tau) e(-B, g2) == 1 with one
+// final exponentiation (qg_srs_check_powers)
+bool kzg_tau_relation(const qg_kzg_vk* vk, const G1Affine& A, const G1Affine& B) {
+  const Vk v = vk_in(vk);
+  const Fq12 f = miller_loop(A, v.g2_tau) * miller_loop(affine_neg(B), v.g2);
+  return final_exp(f) == Fq12::one();
+}
 }  // namespace qg
 
 using namespace qg;

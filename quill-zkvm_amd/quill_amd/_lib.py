@@ -23,9 +23,20 @@ ERRORS = {
 
 
 class QuillGpuError(RuntimeError):
-    def __init__(self, code, msg=""):
+    def __init__(self, code, msg="", bad_index=None, bad_reason=None):
         self.code = code
+        # the refused point of an SRS import / validation (qg_srs_import,
+        # qg_srs_validate): its index and QG_SRS_BAD_* reason, else None
+        self.bad_index, self.bad_reason = bad_index, bad_reason
         super().__init__(f"{ERRORS.get(code, code)}: {msg}")
+
+
+# format / flags of qg_srs_import and qg_srs_export, reasons of a refused point
+QG_G1_UNCOMPRESSED, QG_G1_COMPRESSED = 0, 1
+QG_SRS_ONESHOT = 1
+SRS_BAD_REASONS = {1: "coordinate >= p", 2: "malformed point at infinity",
+                   3: "x^3 + 3 is not a square", 4: "point not on the curve",
+                   5: "y-sign flag inconsistent with the point"}
 
 
 class KzgOpening(C.Structure):
@@ -104,6 +115,11 @@ PROTOTYPES = {
     "qg_srs_len": (SZ, [P]),
     "qg_srs_window_info": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "qg_srs_download": (C.c_int, [P, SZ, SZ, U64P, U8P]),
+    "qg_srs_import": (C.c_int, [P, P, SZ, C.c_int, C.c_uint32, C.POINTER(P),
+                                C.POINTER(C.c_uint64), U32P]),
+    "qg_srs_export": (C.c_int, [P, SZ, SZ, C.c_int, P]),
+    "qg_srs_validate": (C.c_int, [P, P, C.POINTER(C.c_uint64), U32P]),
+    "qg_srs_check_powers": (C.c_int, [P, P, C.POINTER(KzgVk), P, C.POINTER(C.c_int)]),
     "qg_buf_create": (C.c_int, [P, SZ, C.POINTER(P)]),
     "qg_buf_destroy": (C.c_int, [P]),
     "qg_buf_len": (SZ, [P]),

@@ -6,10 +6,20 @@ import os
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import (QG_G1_COMPRESSED, QG_G1_UNCOMPRESSED, QG_SRS_ONESHOT, KzgVk, QuillGpuError,
+                   check, lib)
 from .field import fr_array, fr_c, fr_list, g1_from_abi, g1_to_abi, u64p
 
 _NO_POOL = os.environ.get("QG_NO_POOL") == "1"  # A/B runs: every buffer freed on close
+
+
+def _check_srs(rc, dev, idx, why):
+    """check() for the calls that name a refused point"""
+    if rc != 0:
+        m = lib().qg_last_error(dev.h)
+        bad = why.value != 0
+        raise QuillGpuError(rc, m.decode() if m else "", idx.value if bad else None,
+                            why.value if bad else None)
 
 
 class Device:
@@ -323,6 +333,73 @@ class Srs:
         check(fn(dev.h, u64p(xy), inf.ctypes.data_as(C.POINTER(C.c_uint8)), xy.shape[0],
                  C.byref(h)), dev.h)
         return cls(dev, h)
+
+    @classmethod
+    def from_bytes(cls, dev: Device, data, compressed: bool = True, oneshot: bool = False,
+                   offset: int = 0, n: int = None):
+        """bases from ark-serialize bytes (qg_srs_import): 32 B/point compressed,
+        64 B/point uncompressed, no length prefix; every point is decoded and
+        validated on the device.  `data` is any contiguous buffer (bytes, a
+        memoryview, an np.memmap); offset / n select points [offset, offset+n)
+        of it without a copy.  A refused point raises QuillGpuError carrying
+        .bad_index (relative to `offset`) and .bad_reason."""
+        pb = 32 if compressed else 64
+        arr = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        arr = arr.reshape(-1).view(np.uint8)
+        if arr.size % pb:
+            raise QuillGpuError(-1, f"SRS bytes are not a multiple of {pb}")
+        n = arr.size // pb - offset if n is None else n
+        if offset < 0 or n < 0 or (offset + n) * pb > arr.size:
+            raise QuillGpuError(-1, "SRS byte range out of bounds")
+        part = np.ascontiguousarray(arr[offset * pb:(offset + n) * pb])
+        h = C.c_void_p()
+        idx, why = C.c_uint64(), C.c_uint32()
+        rc = lib().qg_srs_import(dev.h, part.ctypes.data_as(C.c_void_p), n,
+                                 QG_G1_COMPRESSED if compressed else QG_G1_UNCOMPRESSED,
+                                 QG_SRS_ONESHOT if oneshot else 0, C.byref(h), C.byref(idx),
+                                 C.byref(why))
+        _check_srs(rc, dev, idx, why)
+        return cls(dev, h)
+
+    def to_bytes(self, offset: int = 0, n: int = None, compressed: bool = True) -> bytes:
+        """bases [offset, offset+n) as ark-serialize bytes (qg_srs_export)"""
+        n = len(self) - offset if n is None else n
+        out = np.zeros(max(n, 1) * (32 if compressed else 64), dtype=np.uint8)
+        check(lib().qg_srs_export(self.h, offset, n,
+                                  QG_G1_COMPRESSED if compressed else QG_G1_UNCOMPRESSED,
+                                  out.ctypes.data_as(C.c_void_p)), self.dev.h)
+        return out[:n * (32 if compressed else 64)].tobytes()
+
+    def validate(self):
+        """the canonical and on-curve checks over the bases of this handle
+        (qg_srs_validate); raises QuillGpuError with .bad_index / .bad_reason"""
+        idx, why = C.c_uint64(), C.c_uint32()
+        rc = lib().qg_srs_validate(self.dev.h, self.h, C.byref(idx), C.byref(why))
+        _check_srs(rc, self.dev, idx, why)
+
+    def check_powers(self, g1, g2_points, seed: bytes = None) -> bool:
+        """are the bases [tau^i] g1 for the tau of g2_points = [g2, tau g2]
+        (qg_srs_check_powers)?  Collective on a sharded device (this handle is
+        the rank's shard).  seed: 32 bytes the maker of the SRS cannot know;
+        None draws them from the operating system."""
+        from .field import g1_to_abi, g2_to_abi
+        vk = KzgVk()
+        xy, inf = g1_to_abi(g1)
+        if inf:
+            raise QuillGpuError(-1, "g1 generator is the identity")
+        C.memmove(vk.g1_xy, xy, 64)
+        for fld, Q in (("g2_xy", g2_points[0]), ("g2_tau_xy", g2_points[1])):
+            qxy, qinf = g2_to_abi(Q)
+            if qinf:
+                raise QuillGpuError(-1, "G2 point is the identity")
+            C.memmove(getattr(vk, fld), qxy, 128)
+        if seed is not None and len(seed) != 32:
+            raise QuillGpuError(-1, "seed must be 32 bytes")
+        sd = None if seed is None else C.create_string_buffer(bytes(seed), 32)
+        ok = C.c_int()
+        check(lib().qg_srs_check_powers(self.dev.h, self.h, C.byref(vk), sd, C.byref(ok)),
+              self.dev.h)
+        return bool(ok.value)
 
     def __len__(self):
         return lib().qg_srs_len(self.h)

@@ -197,6 +197,7 @@ class KZG:
         self._max_degree = max_degree
         self._tau, self._g = tau, g
         self._shards = {}
+        self._bytes = None  # (buffer, compressed, check) of from_bytes on a sharded device
         # the verifier's part of the CRS (kzg.rs:14-22): g1, g2 = g2_points[0],
         # g2_points[1] = tau g2 (kzg.rs:52-53)
         self.g1 = g if g is not None else G1_GENERATOR
@@ -225,6 +226,19 @@ class KZG:
         L = n_local * self.dev.world
         if L > self._max_degree + 1:
             raise QuillGpuError(-1, "Polynomial degree exceeds max degree")
+        if self._tau is None and self._bytes is not None:
+            if n_local not in self._shards:
+                # an imported SRS: this rank's range of the bytes, validated on the
+                # device, then (check=True) the powers check over all ranks' shards
+                data, compressed, chk = self._bytes
+                s = Srs.from_bytes(self.dev, data, compressed, offset=self.dev.rank * n_local,
+                                   n=n_local)
+                if chk and not s.check_powers(self.g1, self.g2_points):
+                    s.close()
+                    raise QuillGpuError(-5, "SRS powers check failed: the points are not "
+                                            "[tau^i] g1 for the tau of g2_points")
+                self._shards[n_local] = s
+            return self._shards[n_local]
         if self._tau is None:
             raise QuillGpuError(-4, "sharded commitments need a generated (tau) SRS")
         if n_local not in self._shards:
@@ -245,6 +259,42 @@ class KZG:
         dev = dev or Device(0)
         return cls(dev, Srs.upload(dev, g1_points), len(g1_points) - 1, None, g1_points[0],
                    g2_points)
+
+    @classmethod
+    def from_bytes(cls, g1_bytes, g2_points, dev: Device = None, compressed: bool = True,
+                   check: bool = True):
+        """a CRS from ark-serialize G1 bytes (an ark `Vec` length prefix is
+        stripped when present) and g2_points = [g2, tau g2]; g1 = the first
+        point.  Every point is validated on the device (Srs.from_bytes);
+        check=True also runs the powers check against g2_points and raises
+        when it fails.  On a sharded device the buffer is kept (any buffer, e.g.
+        an np.memmap) and srs_for(n_local) imports and checks this rank's range
+        [rank n_local, (rank + 1) n_local) on first use."""
+        dev = dev or Device(0)
+        pb = 32 if compressed else 64
+        arr = g1_bytes if isinstance(g1_bytes, np.ndarray) else np.frombuffer(g1_bytes,
+                                                                              dtype=np.uint8)
+        arr = arr.reshape(-1).view(np.uint8)
+        if arr.size % pb == 8 and int.from_bytes(bytes(arr[:8]), "little") * pb == arr.size - 8:
+            arr = arr[8:]
+        if arr.size == 0 or arr.size % pb:
+            raise QuillGpuError(-1, f"SRS bytes are not a positive multiple of {pb}")
+        n = arr.size // pb
+        one = Srs.from_bytes(dev, arr, compressed, offset=0, n=1)  # g1 = P_0, validated
+        g1 = one.download()[0]
+        one.close()
+        if g1 is None:
+            raise QuillGpuError(-1, "the first SRS point is the identity")
+        if dev.world > 1:
+            kzg = cls(dev, None, n - 1, None, g1, g2_points)
+            kzg._bytes = (arr, compressed, check)
+            return kzg
+        srs = Srs.from_bytes(dev, arr, compressed)
+        if check and not srs.check_powers(g1, g2_points):
+            srs.close()
+            raise QuillGpuError(-5, "SRS powers check failed: the points are not [tau^i] g1 "
+                                    "for the tau of g2_points")
+        return cls(dev, srs, n - 1, None, g1, g2_points)
 
     @classmethod
     def verifier(cls, tau: int = None, g1=None, g2_points=None):
