@@ -435,6 +435,71 @@ int qg_ipa_verify(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1
                   const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
                   uint8_t state[32], int* ok);
 
+/* ---- batched KZG verification: one pairing check for any number of openings.
+ * A claim is one KZG::verify call's input: a commitment and its opening. */
+typedef struct qg_kzg_claim {
+  uint64_t comm_xy[8];
+  uint8_t comm_inf;
+  uint8_t _pad[7];
+  qg_kzg_opening opening;
+} qg_kzg_claim;
+/* All n claims under one key hold exactly when, for weights rho_i,
+ *     L = sum_i rho_i (C_i - y_i g1 + x_i pi_i),    R = sum_i rho_i pi_i,
+ *     e(L, g2) e(-R, tau g2) == 1
+ * (two Miller loops and one final exponentiation for the whole set), except
+ * that a set with a false claim passes with probability about 2^-128 over the
+ * weights.  The weights are Fiat-Shamir, so anyone can restate them: a fresh
+ * transcript qg_transcript_new("quill_kzg_batch") - not the proof's - absorbs,
+ * each as one qg_transcript_append, n as 8 bytes little-endian, then per claim
+ * C (the 64 bytes of qg_g1_serialize), x, y (32 bytes each, qg_fr_serialize)
+ * and pi (64 bytes), then the 32 `seed` bytes when seed != NULL (a verifier's
+ * own randomness; NULL leaves the weights a function of the claims alone).
+ * Then n - 1 field elements are drawn (qg_transcript_draw_fr): rho_0 = 1 and
+ * rho_i = the i-th drawn element's canonical value mod 2^128, i >= 1.
+ * As an MSM: scalars rho_i on C_i, rho_i x_i mod r on pi_i and
+ * -sum_i rho_i y_i on g1 give L; rho_i on pi_i give R.
+ * Every point is checked to be on the curve (QG_ERR_INVALID otherwise, as
+ * qg_kzg_verify); infinity is a legal C and pi (the zero polynomial's).
+ * qg_kzg_batch_fold returns L and R from the host fold, _dev from the device
+ * fold (below); both are the same group elements. */
+int qg_kzg_batch_fold(const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                      const uint8_t seed[32], uint64_t l_xy[8], uint8_t* l_inf, uint64_t r_xy[8],
+                      uint8_t* r_inf);
+int qg_kzg_batch_fold_dev(qg_ctx* ctx, const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                          const uint8_t seed[32], uint64_t l_xy[8], uint8_t* l_inf,
+                          uint64_t r_xy[8], uint8_t* r_inf);
+/* *ok = 1 when the folded check holds (n == 0: always).  Otherwise *ok = 0 and
+ * the claims are checked one by one from index 0 like qg_kzg_verify;
+ * *first_bad (nullable) receives the first that fails - a failing fold implies
+ * one does, and only a rejection pays for the scan.  *first_bad is untouched
+ * on acceptance.  The host entry folds with one double-and-add per point. */
+int qg_kzg_verify_batch(const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                        const uint8_t seed[32], int* ok, size_t* first_bad);
+/* Same, with the fold on the device: [C_0 .. C_{n-1}, pi_0 .. pi_{n-1}, g1] is
+ * uploaded once as one-shot bases (qg_bases_upload), L is the MSM over all
+ * 2n + 1 of them (qg_msm_g1) and R the MSM over the slice [n, 2n)
+ * (qg_msm_g1_at); the two Miller loops stay on the host.  Claims are host
+ * data: on a context with a communicator attached the call returns
+ * QG_ERR_UNSUPPORTED ("sharded" in qg_last_error) before any device work. */
+int qg_kzg_verify_batch_dev(qg_ctx* ctx, const qg_kzg_vk* vk, const qg_kzg_claim* claims,
+                            size_t n, const uint8_t seed[32], int* ok, size_t* first_bad);
+/* qg_mle_verify without its four pairing checks: the same transcript replay
+ * and final `state`, the r = 0 assertion and the inner-product equation
+ * (mlpcs.rs:155-160), which *ok reports; out receives the four (commitment,
+ * opening) pairs in the reference's order (poly, poly_inv, s, s_inv), each
+ * proof point checked to be on the curve.  The proof verifies when *ok = 1 and
+ * a batch holding the four claims does. */
+int qg_mle_verify_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                        const uint64_t* point, size_t nvars, const qg_mle_proof* proof,
+                        uint8_t state[32], qg_kzg_claim out[4], int* ok);
+/* qg_ipa_verify without its six pairing checks (ipa.rs:179-188): out receives
+ * f, f_inv (comm1), g, g_inv (comm2), s, s_inv (s_comm).  One difference from
+ * the sequential call: `state` ALWAYS advances (inner_product, s_comm, draw r),
+ * where qg_ipa_verify returns before touching it when an opening fails. */
+int qg_ipa_verify_defer(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                        const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
+                        uint8_t state[32], qg_kzg_claim out[6], int* ok);
+
 /* Building blocks of the opening, exposed for testing and for callers that
  * batch their own protocol:
  *  compute_pr (mlpcs.rs:68-78) == eq(bin(i), point) table, untrimmed (2^nvars) */

@@ -2,9 +2,22 @@
 //
 // Replaces `E::pairing` of ark-bn254 0.5.0 (a crates.io dependency) at its one
 // call site, KZG::verify (pcs/src/kzg.rs:98-108), and restates
-// MLEvalProof::verify (pcs/src/mlpcs.rs:126-161) on top of it.  Verification
-// is a handful of pairings per proof — latency, not throughput — so it runs on
-// the host next to the transcript, with no device round trip.
+// MLEvalProof::verify (pcs/src/mlpcs.rs:126-161) and InnerProductProof::verify
+// (pcs/src/ipa.rs:160-202) on top of it.  The pairing itself stays on the host
+// next to the transcript.  The sequential verifiers run one pairing check per
+// KZG opening: four per ML opening, six per inner-product proof, 104 for a
+// config-5 HyperPlonk proof of two traces.  The batched
+// verifier (qg_kzg_verify_batch, bottom of this file) folds any number of
+// openings under one key into ONE check, two Miller loops and one final
+// exponentiation: every check shares g2 and tau g2, so for Fiat-Shamir weights
+// rho_i
+//     L = sum rho_i (C_i - y_i g1 + x_i pi_i),   R = sum rho_i pi_i,
+//     accept  <=>  e(L, g2) e(-R, tau g2) == 1.
+// The fold is an MSM over the 2n + 1 points [C.., pi.., g1]: on the host by
+// g1_mul / g1_add, or on the device through the one-shot-bases MSM entries
+// (qg_kzg_verify_batch_dev; no new kernel).  The _defer forms of the two proof
+// verifiers do everything but the pairing checks and hand the openings out as
+// claims for such a batch.
 //
 // Tower: Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - xi), xi = 9 + u,
 // Fq12 = Fq6[w]/(w^2 - v).  G2 is the D-type twist E'/Fq2: y^2 = x^3 + 3/xi,
@@ -368,6 +381,241 @@ Fr eval_pr(const std::vector<Fr>& r, Fr x) {
   return acc;
 }
 
+// ---------------------------------------------------------------- batched KZG check
+struct Claim {
+  G1Affine comm, proof;
+  Fr x, y;
+};
+// every point through g1_in (QG_ERR_INVALID off the curve), as qg_kzg_verify
+std::vector<Claim> claims_in(const qg_kzg_claim* c, size_t n) {
+  std::vector<Claim> out(n);
+  for (size_t i = 0; i < n; i++)
+    out[i] = {g1_in(c[i].comm_xy, c[i].comm_inf),
+              g1_in(c[i].opening.proof_xy, c[i].opening.proof_inf), fr_import(c[i].opening.x),
+              fr_import(c[i].opening.y)};
+  return out;
+}
+void claim_out(const G1Affine& comm, const qg_kzg_opening& op, qg_kzg_claim* out) {
+  (void)g1_in(op.proof_xy, op.proof_inf);
+  memset(out, 0, sizeof *out);
+  g1_export(comm, out->comm_xy, &out->comm_inf);
+  out->opening = op;
+}
+
+// The weights (documented with qg_kzg_batch_fold): a transcript of its own,
+// rho_0 = 1, rho_i = the i-th drawn element mod 2^128 (Montgomery out).
+std::vector<Fr> batch_weights(const std::vector<Claim>& cl, const uint8_t* seed) {
+  static const uint8_t domain[] = "quill_kzg_batch";
+  uint8_t st[32], b8[8], b32[32], b64[64];
+  transcript_init(st, domain, sizeof domain - 1);
+  u64_to_bytes((uint64_t)cl.size(), b8);
+  transcript_append(st, b8, 8);
+  for (const Claim& c : cl) {
+    g1_serialize(c.comm, b64);
+    transcript_append(st, b64, 64);
+    fr_to_bytes(c.x, b32);
+    transcript_append(st, b32, 32);
+    fr_to_bytes(c.y, b32);
+    transcript_append(st, b32, 32);
+    g1_serialize(c.proof, b64);
+    transcript_append(st, b64, 64);
+  }
+  if (seed) transcript_append(st, seed, 32);
+  std::vector<Fr> rho(cl.size());
+  for (size_t i = 0; i < cl.size(); i++) {
+    if (i == 0) {
+      rho[i] = Fr::one();
+      continue;
+    }
+    Fr lo = from_mont(transcript_draw_fr(st));
+    for (int k = 4; k < 8; k++) lo.v[k] = 0;
+    rho[i] = to_mont(lo);
+  }
+  return rho;
+}
+
+// The fold as an MSM: bases [C_0.., pi_0.., g1], the scalars of L over all
+// 2n + 1 of them (rho_i, rho_i x_i, -sum rho_i y_i); R's are sc[0..n) again,
+// over the bases [n, 2n).
+struct Fold {
+  std::vector<G1Affine> bases;
+  std::vector<Fr> sc;
+};
+Fold fold_plan(const Vk& vk, const std::vector<Claim>& cl, const std::vector<Fr>& rho) {
+  const size_t n = cl.size();
+  Fold f;
+  f.bases.resize(2 * n + 1);
+  f.sc.resize(2 * n + 1);
+  Fr ysum = Fr::zero();
+  for (size_t i = 0; i < n; i++) {
+    f.bases[i] = cl[i].comm;
+    f.bases[n + i] = cl[i].proof;
+    f.sc[i] = rho[i];
+    f.sc[n + i] = rho[i] * cl[i].x;
+    ysum = ysum + rho[i] * cl[i].y;
+  }
+  f.bases[2 * n] = vk.g1;
+  f.sc[2 * n] = Fr::zero() - ysum;
+  return f;
+}
+G1Affine msm_host_naive(const G1Affine* bases, const Fr* sc, size_t n) {
+  G1Affine acc = G1Affine::infinity();
+  for (size_t i = 0; i < n; i++)
+    if (!bases[i].is_inf() && !sc[i].is_zero()) acc = g1_add(acc, g1_mul(bases[i], from_mont(sc[i])));
+  return acc;
+}
+struct Folded {
+  G1Affine L, R;
+};
+Folded fold_host(const Fold& f) {
+  const size_t n = f.bases.size() / 2;
+  return {msm_host_naive(f.bases.data(), f.sc.data(), 2 * n + 1),
+          msm_host_naive(f.bases.data() + n, f.sc.data(), n)};
+}
+// the same two sums by the device MSM: the bases uploaded once as one-shot
+// bases, L over all of them, R over the slice [n, 2n) by the base offset
+Folded fold_device(qg_ctx* ctx, const Fold& f) {
+  const size_t n = f.bases.size() / 2, m = 2 * n + 1;
+  std::vector<uint64_t> xy(8 * m), sc(4 * m);
+  std::vector<uint8_t> inf(m);
+  for (size_t i = 0; i < m; i++) {
+    g1_export(f.bases[i], &xy[8 * i], &inf[i]);
+    fr_export(f.sc[i], &sc[4 * i]);
+  }
+  qg_srs* srs = nullptr;
+  int rc = qg_bases_upload(ctx, xy.data(), inf.data(), m, &srs);
+  uint64_t lxy[8], rxy[8];
+  uint8_t linf = 0, rinf = 0;
+  if (rc == QG_OK) rc = qg_msm_g1(ctx, srs, sc.data(), m, lxy, &linf);
+  if (rc == QG_OK) rc = qg_msm_g1_at(ctx, srs, n, sc.data(), n, rxy, &rinf);
+  (void)qg_srs_destroy(srs);
+  if (rc != QG_OK) throw Error(rc, ctx->last_error);
+  return {g1_import(lxy, linf), g1_import(rxy, rinf)};
+}
+bool folded_check(const Vk& vk, const Folded& f) {
+  const Fq12 m = miller_loop(f.L, vk.g2) * miller_loop(affine_neg(f.R), vk.g2_tau);
+  return final_exp(m) == Fq12::one();
+}
+
+// ctx == nullptr: the host fold
+void verify_batch(qg_ctx* ctx, const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                  const uint8_t* seed, int* ok, size_t* first_bad) {
+  const Vk v = vk_in(vk);
+  const std::vector<Claim> cl = claims_in(claims, n);
+  *ok = 1;
+  if (n == 0) return;
+  const Fold f = fold_plan(v, cl, batch_weights(cl, seed));
+  if (folded_check(v, ctx ? fold_device(ctx, f) : fold_host(f))) return;
+  // rejection only: the first claim that fails on its own
+  *ok = 0;
+  for (size_t i = 0; i < n; i++)
+    if (!kzg_verify(v, cl[i].comm, cl[i].x, cl[i].y, cl[i].proof)) {
+      if (first_bad) *first_bad = i;
+      return;
+    }
+  throw Error(QG_ERR_ASSERT, "batched KZG check failed but every claim verifies alone");
+}
+
+void fold_out(const Folded& f, uint64_t l_xy[8], uint8_t* l_inf, uint64_t r_xy[8], uint8_t* r_inf) {
+  g1_export(f.L, l_xy, l_inf);
+  g1_export(f.R, r_xy, r_inf);
+}
+
+// MLEvalProof::verify (mlpcs.rs:126-161).  defer == nullptr: the four pairing
+// checks run here and a failing one returns before the equation; otherwise
+// the four (commitment, opening) pairs are written to defer[0..4) instead.
+void mle_verify_impl(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                     const uint64_t* point, size_t nvars, const qg_mle_proof* proof,
+                     uint8_t state[32], qg_kzg_claim* defer, int* ok) {
+  const Vk v = vk_in(vk);
+  const G1Affine comm = g1_in(comm_xy, comm_inf);
+  const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
+  // reconstruct the transcript (mlpcs.rs:133-140): point, evaluation, s_comm; draw r
+  std::vector<Fr> r(nvars);
+  std::vector<uint8_t> msg(8 + 32 * nvars);
+  u64_to_bytes(nvars, msg.data());
+  for (size_t i = 0; i < nvars; i++) {
+    r[i] = fr_import(point + 4 * i);
+    fr_to_bytes(r[i], msg.data() + 8 + 32 * i);
+  }
+  transcript_append(state, msg.data(), msg.size());
+  uint8_t b32[32], b64[64];
+  const Fr evaluation = fr_import(proof->evaluation);
+  fr_to_bytes(evaluation, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr x = transcript_draw_fr(state);
+  // r.inverse().unwrap() (mlpcs.rs:141)
+  QG_CHECK(!x.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  const Fr x_inv = finv(x);
+  // the four openings (mlpcs.rs:143-151), then the inner-product equation
+  // (:153-160); like the reference, the openings' own x are not compared with r
+  *ok = 0;
+  if (defer) {
+    claim_out(comm, proof->poly_opening, defer + 0);
+    claim_out(comm, proof->poly_opening_inv, defer + 1);
+    claim_out(s_comm, proof->s_opening, defer + 2);
+    claim_out(s_comm, proof->s_opening_inv, defer + 3);
+  } else if (!kzg_verify_abi(v, comm, proof->poly_opening) ||
+             !kzg_verify_abi(v, comm, proof->poly_opening_inv) ||
+             !kzg_verify_abi(v, s_comm, proof->s_opening) ||
+             !kzg_verify_abi(v, s_comm, proof->s_opening_inv)) {
+    return;
+  }
+  const Fr pr_r = eval_pr(r, x), pr_r_inv = eval_pr(r, x_inv);
+  const Fr lhs = fr_import(proof->poly_opening.y) * pr_r_inv +
+                 fr_import(proof->poly_opening_inv.y) * pr_r;
+  const Fr rhs = x * fr_import(proof->s_opening.y) + x_inv * fr_import(proof->s_opening_inv.y) +
+                 from_u64<FrP>(2) * evaluation;
+  *ok = lhs == rhs ? 1 : 0;
+}
+
+// InnerProductProof::verify (ipa.rs:160-202).  defer == nullptr: the six
+// pairing checks first, a failure returns before the transcript is touched;
+// otherwise the six pairs go to defer[0..6) and the transcript always advances.
+void ipa_verify_impl(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                     const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
+                     uint8_t state[32], qg_kzg_claim* defer, int* ok) {
+  const Vk v = vk_in(vk);
+  const G1Affine comm1 = g1_in(comm1_xy, comm1_inf), comm2 = g1_in(comm2_xy, comm2_inf);
+  const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
+  *ok = 0;
+  if (defer) {
+    claim_out(comm1, proof->f_opening, defer + 0);
+    claim_out(comm1, proof->f_opening_inv, defer + 1);
+    claim_out(comm2, proof->g_opening, defer + 2);
+    claim_out(comm2, proof->g_opening_inv, defer + 3);
+    claim_out(s_comm, proof->s_opening, defer + 4);
+    claim_out(s_comm, proof->s_opening_inv, defer + 5);
+  } else if (!kzg_verify_abi(v, comm1, proof->f_opening) ||
+             !kzg_verify_abi(v, comm1, proof->f_opening_inv) ||
+             !kzg_verify_abi(v, comm2, proof->g_opening) ||
+             !kzg_verify_abi(v, comm2, proof->g_opening_inv) ||
+             !kzg_verify_abi(v, s_comm, proof->s_opening) ||
+             !kzg_verify_abi(v, s_comm, proof->s_opening_inv)) {
+    // the six openings first (ipa.rs:179-188): a failure returns before the
+    // transcript is touched
+    return;
+  }
+  // inner_product, s_comm; draw r (ipa.rs:191-195)
+  uint8_t b32[32], b64[64];
+  const Fr ip = fr_import(proof->inner_product);
+  fr_to_bytes(ip, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr r = transcript_draw_fr(state);
+  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  const Fr r_inv = finv(r);
+  // ipa.rs:198-201; like the reference, the openings' own x are not compared with r
+  const Fr lhs = fr_import(proof->f_opening.y) * fr_import(proof->g_opening_inv.y) +
+                 fr_import(proof->f_opening_inv.y) * fr_import(proof->g_opening.y);
+  const Fr rhs = r * fr_import(proof->s_opening.y) + r_inv * fr_import(proof->s_opening_inv.y) +
+                 from_u64<FrP>(2) * ip;
+  *ok = lhs == rhs ? 1 : 0;
+}
+
 }  // namespace
 
 // the whole key is validated (g1 on the curve, both G2 points in the subgroup)
@@ -450,42 +698,20 @@ int qg_mle_verify(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_i
                   uint8_t state[32], int* ok) {
   if (!vk || !comm_xy || (!point && nvars) || !proof || !state || !ok) return QG_ERR_INVALID;
   try {
-    const Vk v = vk_in(vk);
-    const G1Affine comm = g1_in(comm_xy, comm_inf);
-    const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
-    // reconstruct the transcript (mlpcs.rs:133-140): point, evaluation, s_comm; draw r
-    std::vector<Fr> r(nvars);
-    std::vector<uint8_t> msg(8 + 32 * nvars);
-    u64_to_bytes(nvars, msg.data());
-    for (size_t i = 0; i < nvars; i++) {
-      r[i] = fr_import(point + 4 * i);
-      fr_to_bytes(r[i], msg.data() + 8 + 32 * i);
-    }
-    transcript_append(state, msg.data(), msg.size());
-    uint8_t b32[32], b64[64];
-    const Fr evaluation = fr_import(proof->evaluation);
-    fr_to_bytes(evaluation, b32);
-    transcript_append(state, b32, 32);
-    g1_serialize(s_comm, b64);
-    transcript_append(state, b64, 64);
-    const Fr x = transcript_draw_fr(state);
-    // r.inverse().unwrap() (mlpcs.rs:141)
-    QG_CHECK(!x.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-    const Fr x_inv = finv(x);
-    // the four openings (mlpcs.rs:143-151), then the inner-product equation
-    // (:153-160); like the reference, the openings' own x are not compared with r
-    *ok = 0;
-    if (!kzg_verify_abi(v, comm, proof->poly_opening) ||
-        !kzg_verify_abi(v, comm, proof->poly_opening_inv) ||
-        !kzg_verify_abi(v, s_comm, proof->s_opening) ||
-        !kzg_verify_abi(v, s_comm, proof->s_opening_inv))
-      return QG_OK;
-    const Fr pr_r = eval_pr(r, x), pr_r_inv = eval_pr(r, x_inv);
-    const Fr lhs = fr_import(proof->poly_opening.y) * pr_r_inv +
-                   fr_import(proof->poly_opening_inv.y) * pr_r;
-    const Fr rhs = x * fr_import(proof->s_opening.y) + x_inv * fr_import(proof->s_opening_inv.y) +
-                   from_u64<FrP>(2) * evaluation;
-    *ok = lhs == rhs ? 1 : 0;
+    mle_verify_impl(vk, comm_xy, comm_inf, point, nvars, proof, state, nullptr, ok);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_mle_verify_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                        const uint64_t* point, size_t nvars, const qg_mle_proof* proof,
+                        uint8_t state[32], qg_kzg_claim out[4], int* ok) {
+  if (!vk || !comm_xy || (!point && nvars) || !proof || !state || !out || !ok)
+    return QG_ERR_INVALID;
+  try {
+    mle_verify_impl(vk, comm_xy, comm_inf, point, nvars, proof, state, out, ok);
     return QG_OK;
   } catch (const Error& e) {
     return e.code;
@@ -497,39 +723,76 @@ int qg_ipa_verify(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1
                   uint8_t state[32], int* ok) {
   if (!vk || !comm1_xy || !comm2_xy || !proof || !state || !ok) return QG_ERR_INVALID;
   try {
-    const Vk v = vk_in(vk);
-    const G1Affine comm1 = g1_in(comm1_xy, comm1_inf), comm2 = g1_in(comm2_xy, comm2_inf);
-    const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
-    // the six openings first (ipa.rs:179-188): a failure returns before the
-    // transcript is touched
-    *ok = 0;
-    if (!kzg_verify_abi(v, comm1, proof->f_opening) ||
-        !kzg_verify_abi(v, comm1, proof->f_opening_inv) ||
-        !kzg_verify_abi(v, comm2, proof->g_opening) ||
-        !kzg_verify_abi(v, comm2, proof->g_opening_inv) ||
-        !kzg_verify_abi(v, s_comm, proof->s_opening) ||
-        !kzg_verify_abi(v, s_comm, proof->s_opening_inv))
-      return QG_OK;
-    // inner_product, s_comm; draw r (ipa.rs:191-195)
-    uint8_t b32[32], b64[64];
-    const Fr ip = fr_import(proof->inner_product);
-    fr_to_bytes(ip, b32);
-    transcript_append(state, b32, 32);
-    g1_serialize(s_comm, b64);
-    transcript_append(state, b64, 64);
-    const Fr r = transcript_draw_fr(state);
-    QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-    const Fr r_inv = finv(r);
-    // ipa.rs:198-201; like the reference, the openings' own x are not compared with r
-    const Fr lhs = fr_import(proof->f_opening.y) * fr_import(proof->g_opening_inv.y) +
-                   fr_import(proof->f_opening_inv.y) * fr_import(proof->g_opening.y);
-    const Fr rhs = r * fr_import(proof->s_opening.y) + r_inv * fr_import(proof->s_opening_inv.y) +
-                   from_u64<FrP>(2) * ip;
-    *ok = lhs == rhs ? 1 : 0;
+    ipa_verify_impl(vk, comm1_xy, comm1_inf, comm2_xy, comm2_inf, proof, state, nullptr, ok);
     return QG_OK;
   } catch (const Error& e) {
     return e.code;
   }
+}
+
+int qg_ipa_verify_defer(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                        const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
+                        uint8_t state[32], qg_kzg_claim out[6], int* ok) {
+  if (!vk || !comm1_xy || !comm2_xy || !proof || !state || !out || !ok) return QG_ERR_INVALID;
+  try {
+    ipa_verify_impl(vk, comm1_xy, comm1_inf, comm2_xy, comm2_inf, proof, state, out, ok);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_kzg_batch_fold(const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                      const uint8_t seed[32], uint64_t l_xy[8], uint8_t* l_inf, uint64_t r_xy[8],
+                      uint8_t* r_inf) {
+  if (!vk || (!claims && n) || !l_xy || !l_inf || !r_xy || !r_inf) return QG_ERR_INVALID;
+  try {
+    const Vk v = vk_in(vk);
+    const std::vector<Claim> cl = claims_in(claims, n);
+    fold_out(fold_host(fold_plan(v, cl, batch_weights(cl, seed))), l_xy, l_inf, r_xy, r_inf);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+static void batch_dev_entry_checks(qg_ctx* ctx) {
+  QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
+           "the batched KZG check is not supported on a sharded context (communicator "
+           "attached): claims are host data, fold them on a single-device context");
+}
+
+int qg_kzg_batch_fold_dev(qg_ctx* ctx, const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                          const uint8_t seed[32], uint64_t l_xy[8], uint8_t* l_inf,
+                          uint64_t r_xy[8], uint8_t* r_inf) {
+  if (!ctx || !vk || (!claims && n) || !l_xy || !l_inf || !r_xy || !r_inf) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    batch_dev_entry_checks(ctx);
+    const Vk v = vk_in(vk);
+    const std::vector<Claim> cl = claims_in(claims, n);
+    fold_out(fold_device(ctx, fold_plan(v, cl, batch_weights(cl, seed))), l_xy, l_inf, r_xy,
+             r_inf);
+  });
+}
+
+int qg_kzg_verify_batch(const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
+                        const uint8_t seed[32], int* ok, size_t* first_bad) {
+  if (!vk || (!claims && n) || !ok) return QG_ERR_INVALID;
+  try {
+    verify_batch(nullptr, vk, claims, n, seed, ok, first_bad);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_kzg_verify_batch_dev(qg_ctx* ctx, const qg_kzg_vk* vk, const qg_kzg_claim* claims,
+                            size_t n, const uint8_t seed[32], int* ok, size_t* first_bad) {
+  if (!ctx || !vk || (!claims && n) || !ok) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    batch_dev_entry_checks(ctx);
+    verify_batch(ctx, vk, claims, n, seed, ok, first_bad);
+  });
 }
 
 }  // extern "C"

@@ -59,6 +59,11 @@ class IpaProof(C.Structure):
                 ("s_opening", KzgOpening), ("s_opening_inv", KzgOpening)]
 
 
+class KzgClaim(C.Structure):
+    _fields_ = [("comm_xy", C.c_uint64 * 8), ("comm_inf", C.c_uint8), ("_pad", C.c_uint8 * 7),
+                ("opening", KzgOpening)]
+
+
 class MleOpenItem(C.Structure):
     _fields_ = [("poly", C.c_void_p), ("n", C.c_size_t), ("point", C.POINTER(C.c_uint64)),
                 ("nvars", C.c_size_t), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
@@ -157,6 +162,20 @@ PROTOTYPES = {
     "qg_ipa_prove_dev": (C.c_int, [P, P, P, SZ, P, SZ, U8P, C.POINTER(IpaProof)]),
     "qg_ipa_verify": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,
                                 C.POINTER(IpaProof), U8P, C.POINTER(C.c_int)]),
+    "qg_kzg_batch_fold": (C.c_int, [C.POINTER(KzgVk), C.POINTER(KzgClaim), SZ, U8P, U64P, U8P,
+                                    U64P, U8P]),
+    "qg_kzg_batch_fold_dev": (C.c_int, [P, C.POINTER(KzgVk), C.POINTER(KzgClaim), SZ, U8P, U64P,
+                                        U8P, U64P, U8P]),
+    "qg_kzg_verify_batch": (C.c_int, [C.POINTER(KzgVk), C.POINTER(KzgClaim), SZ, U8P,
+                                      C.POINTER(C.c_int), C.POINTER(SZ)]),
+    "qg_kzg_verify_batch_dev": (C.c_int, [P, C.POINTER(KzgVk), C.POINTER(KzgClaim), SZ, U8P,
+                                          C.POINTER(C.c_int), C.POINTER(SZ)]),
+    "qg_mle_verify_defer": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, SZ,
+                                      C.POINTER(MleProof), U8P, C.POINTER(KzgClaim),
+                                      C.POINTER(C.c_int)]),
+    "qg_ipa_verify_defer": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,
+                                      C.POINTER(IpaProof), U8P, C.POINTER(KzgClaim),
+                                      C.POINTER(C.c_int)]),
     "qg_eq_table": (C.c_int, [P, U64P, SZ, U64P]),
     "qg_eq_table_dev": (C.c_int, [P, U64P, SZ, P]),
     "qg_s_polynomial": (C.c_int, [P, U64P, SZ, U64P, SZ, U64P]),

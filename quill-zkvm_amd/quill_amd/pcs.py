@@ -10,8 +10,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (IpaProof, KzgOpening, KzgVk, MleOpenItem, MleProof, QuillGpuError, check,
-                   lib)
+from ._lib import (IpaProof, KzgClaim, KzgOpening, KzgVk, MleOpenItem, MleProof, QuillGpuError,
+                   check, lib)
 from .device import Device, DeviceVec, Srs
 from .field import (fq_from_mont_limbs, fr_array, fr_c, fr_from_mont_limbs, g1_from_abi,
                     g1_to_abi, g2_from_abi, g2_to_abi, u64p)
@@ -173,7 +173,11 @@ class InnerProductProof:
     def verify(self, comm1, comm2, kzg: "KZG", transcript: Transcript) -> bool:
         """ipa.rs:160-202 (host pairing checks, qg_ipa_verify): the six KZG
         checks first - a failure leaves the transcript untouched -, then the
-        transcript replay and the equation at r"""
+        transcript replay and the equation at r.  With a deferring view
+        (KZG.deferring) the six openings become claims of the view's batch, the
+        transcript always advances and only the equation's verdict returns."""
+        if isinstance(kzg, DeferringKZG):
+            return kzg.verify_inner_product(comm1, comm2, self, transcript)
         xy1, inf1 = g1_to_abi(comm1)
         xy2, inf2 = g1_to_abi(comm2)
         ok = C.c_int()
@@ -319,6 +323,14 @@ class KZG:
             C.memmove(getattr(vk, fld), qxy, 128)
         return vk
 
+    def deferring(self, dev: Device = None, seed: bytes = None) -> "DeferringKZG":
+        """a view of this key that collects pairing checks instead of running
+        them (DeferringKZG): pass it wherever a verifier takes `pcs`, then call
+        its check().  dev: fold the claims on that Device (qg_kzg_verify_batch_dev)
+        instead of on the host; seed: 32 bytes of the verifier's own randomness
+        mixed into the weights."""
+        return DeferringKZG(self, dev, seed)
+
     # KZG::verify (kzg.rs:98-108)
     def verify_univariate(self, commitment, opening: KZGOpeningProof) -> bool:
         xy, inf = g1_to_abi(commitment)
@@ -445,3 +457,105 @@ class KZG:
                            g1_from_abi(out.s_comm_xy, out.s_comm_inf),
                            _opening(out.poly_opening), _opening(out.poly_opening_inv),
                            _opening(out.s_opening), _opening(out.s_opening_inv))
+
+
+_MLE_OPENINGS = ("poly_opening", "poly_opening_inv", "s_opening", "s_opening_inv")
+
+
+def _claim_c(commitment, opening: KZGOpeningProof) -> KzgClaim:
+    c = KzgClaim()
+    xy, inf = g1_to_abi(commitment)
+    C.memmove(c.comm_xy, xy, 64)
+    c.comm_inf = inf
+    c.opening = _opening_c(opening)
+    return c
+
+
+def _claim_copy(c: KzgClaim) -> KzgClaim:
+    out = KzgClaim()
+    C.memmove(C.byref(out), C.byref(c), C.sizeof(KzgClaim))
+    return out
+
+
+class DeferringKZG:
+    """Batched verification (qg_kzg_verify_batch): a view of a KZG key whose
+    verify, verify_univariate and InnerProductProof.verify path run everything
+    but the pairing checks, append those as claims and return only the
+    non-pairing verdict (the ML / inner-product equation; True for a univariate
+    opening).  check() then verifies every collected claim with ONE pairing
+    check - two Miller loops and one final exponentiation, the fold on the host
+    or, with `dev`, as two device MSMs.  Every other attribute is the key's.
+
+    `claims` holds (label, KzgClaim) in call order.  A label is `labels[id(proof)]`
+    when the caller registered the proof object there, else "opening <k>" for
+    the k-th deferred call; the opening's field name is appended.  `messages`
+    maps id(proof) to the error text check() raises for that proof's claims.
+
+    Accepted set: what the sequential verifier accepts is accepted; a set with
+    a false opening is accepted with probability at most about 2^-128 (the
+    weights are 128-bit Fiat-Shamir values over all the claims)."""
+
+    def __init__(self, base: "KZG", dev: Device = None, seed: bytes = None):
+        if seed is not None and len(seed) != 32:
+            raise QuillGpuError(-1, "the batch seed is 32 bytes")
+        self.base, self.batch_dev, self.seed = base, dev, seed
+        self.claims, self.labels, self.messages = [], {}, {}
+        self._msgs = []
+        self._calls = 0
+
+    def __getattr__(self, name):
+        return getattr(self.base, name)
+
+    def _push(self, proof, names, cs):
+        label = self.labels.get(id(proof), f"opening {self._calls}")
+        self._calls += 1
+        for name, c in zip(names, cs):
+            self.claims.append((f"{label}, {name}" if name else label, _claim_copy(c)))
+            self._msgs.append(self.messages.get(id(proof), "KZG opening verification failed"))
+
+    def verify_univariate(self, commitment, opening: KZGOpeningProof) -> bool:
+        self._push(opening, (None,), (_claim_c(commitment, opening),))
+        return True
+
+    def verify(self, commitment, proof: MLEvalProof, transcript: Transcript) -> bool:
+        xy, inf = g1_to_abi(commitment)
+        pt = proof.evaluation_point
+        arr = fr_array(pt) if len(pt) else np.zeros((1, 4), dtype=np.uint64)
+        ok, out = C.c_int(), (KzgClaim * 4)()
+        check(lib().qg_mle_verify_defer(C.byref(self.base._vk()), xy, inf, u64p(arr), len(pt),
+                                        C.byref(_mle_proof_c(proof)), transcript.c_state(), out,
+                                        C.byref(ok)))
+        self._push(proof, _MLE_OPENINGS, out)
+        return bool(ok.value)
+
+    def verify_inner_product(self, comm1, comm2, proof: InnerProductProof,
+                             transcript: Transcript) -> bool:
+        xy1, inf1 = g1_to_abi(comm1)
+        xy2, inf2 = g1_to_abi(comm2)
+        ok, out = C.c_int(), (KzgClaim * 6)()
+        check(lib().qg_ipa_verify_defer(C.byref(self.base._vk()), xy1, inf1, xy2, inf2,
+                                        C.byref(_ipa_proof_c(proof)), transcript.c_state(), out,
+                                        C.byref(ok)))
+        self._push(proof, _IPA_OPENINGS, out)
+        return bool(ok.value)
+
+    def check(self) -> None:
+        """one pairing check over every claim collected so far.  Raises
+        ValueError naming the label of the lowest failing claim (found by a
+        sequential scan that only a rejection pays for); the claims stay."""
+        n = len(self.claims)
+        arr = (KzgClaim * max(n, 1))()
+        for i, (_, c) in enumerate(self.claims):
+            arr[i] = c
+        seed = None if self.seed is None else (C.c_uint8 * 32).from_buffer_copy(self.seed)
+        ok, bad = C.c_int(), C.c_size_t()
+        vk = self.base._vk()
+        if self.batch_dev is not None:
+            check(lib().qg_kzg_verify_batch_dev(self.batch_dev.h, C.byref(vk), arr, n, seed,
+                                                C.byref(ok), C.byref(bad)), self.batch_dev.h)
+        else:
+            check(lib().qg_kzg_verify_batch(C.byref(vk), arr, n, seed, C.byref(ok),
+                                            C.byref(bad)))
+        if not ok.value:
+            raise ValueError(f"{self._msgs[bad.value]} ({self.claims[bad.value][0]}; "
+                             f"batched claim {bad.value} of {n})")

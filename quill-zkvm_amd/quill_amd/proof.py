@@ -102,9 +102,27 @@ def _verify_trace_proof(witness_commitment, vk: "TraceVK", pcs, proof: TraceProo
         raise ValueError("Permutation trace commitment opening verification failed")
 
 
-def _hyperplonk_verify(self, vk, pcs) -> Transcript:
+def _hyperplonk_verify(self, vk, pcs, batch: bool = False, dev: Device = None) -> Transcript:
     """proof.rs:494-521: raises ValueError on rejection; returns the final
-    transcript (equal to the prover's when the proof verifies)"""
+    transcript (equal to the prover's when the proof verifies).
+
+    batch=True runs the same verifier over pcs.deferring(dev): every pairing
+    check of every opening (about fifty for two traces) is collected and
+    checked at the end as ONE (DeferringKZG.check; dev: the fold as device
+    MSMs).  The final transcript is the sequential one.
+    Accepted set: batch mode accepts what sequential mode accepts, and accepts
+    a proof with a false opening with probability at most about 2^-128.
+    Error order on rejection: a failing non-pairing check (sumcheck rounds,
+    point and evaluation mismatches, the ML equation of any opening) raises
+    first, with the reference's message, also when an earlier opening's
+    pairing check would have failed before it in sequential mode; otherwise
+    the message of the lowest failing opening is raised, with its label."""
+    if batch:
+        view = pcs.deferring(dev)
+        _label_openings(self, view)
+        t = _hyperplonk_verify(self, vk, view)
+        view.check()
+        return t
     t = Transcript(b"hyperplonk_proof")
     for c in self.witness_commitment:
         t.append_g1(c)
@@ -114,6 +132,29 @@ def _hyperplonk_verify(self, vk, pcs) -> Transcript:
     for c, tvk, tp in zip(self.witness_commitment, vks, self.trace_proofs):
         _verify_trace_proof(c, tvk, pcs, tp, t)
     return t
+
+
+def _label_openings(proof: HyperPlonkProof, view) -> None:
+    """names and the sequential verifier's messages for the openings of
+    `proof`, keyed by object for a deferring view"""
+    def put(op, label, msg):
+        view.labels[id(op)] = label
+        view.messages[id(op)] = msg
+    for k, tp in enumerate(proof.trace_proofs):
+        me = tp.permutation_check_proof.multiset_equality_proof
+        put(me.opening_proof_denom_left, f"trace {k} permutation-check left denominator opening",
+            "Multiset equality opening proof verification failed")
+        put(me.opening_proof_denom_right, f"trace {k} permutation-check right denominator opening",
+            "Multiset equality opening proof verification failed")
+        for i, op in enumerate(tp.openings_zero_check):
+            put(op, f"trace {k} zero-check opening {i}", "Zero check opening verification failed")
+        for i, op in enumerate(tp.openings_public):
+            put(op, f"trace {k} public opening {i}", "Public opening verification failed")
+        put(tp.opening_id, f"trace {k} id opening", "ID commitment opening verification failed")
+        put(tp.opening_permutation, f"trace {k} permutation opening",
+            "Permutation commitment opening verification failed")
+        put(tp.opening_permutation_trace, f"trace {k} permutation-trace opening",
+            "Permutation trace commitment opening verification failed")
 
 
 HyperPlonkProof.verify = _hyperplonk_verify
