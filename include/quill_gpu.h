@@ -516,6 +516,34 @@ int qg_s_polynomial(qg_ctx* ctx, const uint64_t* f, size_t nf, const uint64_t* g
 /*  sum_i f[i] g[i] over min(nf, ng)  (mlpcs.rs:91-94, ipa.rs:66-69) */
 int qg_inner_product(qg_ctx* ctx, const uint64_t* f, size_t nf, const uint64_t* g, size_t ng,
                      uint64_t out[4]);
+/*  The streaming pieces of the multi-point batch opening (HyperPlonk paper,
+ *  section 3.8; no counterpart in the reference, composed in
+ *  quill_amd/multiopen.py).  Index bit j of a table corresponds to point[j];
+ *  results are canonical residues.  Limits: 1 <= k <= 256, 1 <= P <= 16,
+ *  1 <= nvars, 2^nvars entries fit the buffers; anything else, null pointers
+ *  included, is QG_ERR_INVALID.  With a communicator attached the three device
+ *  entries return QG_ERR_UNSUPPORTED (single-context only so far; the sharded
+ *  form is the follow-up of DESIGN section 8).
+ *
+ *  out[x] = sum_{i<k} weights[i] eq(bin(x), points[i]) for x < 2^nvars.
+ *  points: k x nvars Fr, weights: k Fr (host).  No eq table is materialised:
+ *  per point a low and a high half-table, k products per output entry. */
+int qg_eq_multi_dev(qg_ctx* ctx, const uint64_t* points, const uint64_t* weights, size_t k,
+                    size_t nvars, qg_buf* out);
+/*  out[i] = sum_x poly[x] eq(bin(x), points[i]) for k points (k Fr on the
+ *  host), in one pass over the first n = 2^nvars entries of poly. */
+int qg_mle_eval_multi_dev(qg_ctx* ctx, const qg_buf* poly, size_t n, const uint64_t* points,
+                          size_t k, size_t nvars, uint64_t* out);
+/*  out[x] = sum_{j<P} coeffs[j] bufs[j][x] for x < n (coeffs: P Fr on the
+ *  host).  out must not overlap an input: QG_ERR_INVALID. */
+int qg_lincomb_dev(qg_ctx* ctx, const qg_buf* const* bufs, const uint64_t* coeffs, size_t P,
+                   size_t n, qg_buf* out);
+/*  sum_i scalars[i] points[i] over n <= 65536 G1 points, on the host (no
+ *  context): how a verifier forms the combined commitment of a batch opening.
+ *  Identity inputs (infs[i] != 0) and an identity result are valid; a point
+ *  off the curve is QG_ERR_INVALID. */
+int qg_g1_lincomb(const uint64_t* points_xy, const uint8_t* infs, const uint64_t* scalars, size_t n,
+                  uint64_t out_xy[8], uint8_t* out_inf);
 
 /* ---------------------------------------------------------------- sumcheck */
 /* Virtual-polynomial expression (hyperplonk/src/utils/virtual_polynomial.rs:9-18)

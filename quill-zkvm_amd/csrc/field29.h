@@ -658,6 +658,18 @@ QG_HD F29<C> red16p29(const F29<C>& a) {
   return condsub29<C>(x, F29P<C>::P2);
 }
 
+// lazy value < 128p (limbs < 2^32) -> normalized, < 2p
+template <class C>
+QG_HD F29<C> red128p29(const F29<C>& a) {
+  F29<C> x = normfull29<C>(a);
+  x = condsub29<C>(x, l9_mul_small(F29P<C>::P, 64));
+  x = condsub29<C>(x, l9_mul_small(F29P<C>::P, 32));
+  x = condsub29<C>(x, F29P<C>::KP20.k[16]);
+  x = condsub29<C>(x, F29P<C>::P8);
+  x = condsub29<C>(x, F29P<C>::P4);
+  return condsub29<C>(x, F29P<C>::P2);
+}
+
 // lazy value < 6p -> normalized, < 2p
 template <class C>
 QG_HD F29<C> red6p29(const F29<C>& a) {

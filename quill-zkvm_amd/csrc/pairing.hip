@@ -756,6 +756,24 @@ int qg_kzg_batch_fold(const qg_kzg_vk* vk, const qg_kzg_claim* claims, size_t n,
   }
 }
 
+int qg_g1_lincomb(const uint64_t* points_xy, const uint8_t* infs, const uint64_t* scalars, size_t n,
+                  uint64_t out_xy[8], uint8_t* out_inf) {
+  if (!points_xy || !infs || !scalars || !out_xy || !out_inf || n < 1 || n > 65536)
+    return QG_ERR_INVALID;
+  try {
+    std::vector<G1Affine> bases(n);
+    std::vector<Fr> sc(n);
+    for (size_t i = 0; i < n; i++) {
+      bases[i] = g1_in(points_xy + 8 * i, infs[i]);
+      sc[i] = fr_import(scalars + 4 * i);
+    }
+    g1_export(msm_host_naive(bases.data(), sc.data(), n), out_xy, out_inf);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
 static void batch_dev_entry_checks(qg_ctx* ctx) {
   QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
            "the batched KZG check is not supported on a sharded context (communicator "

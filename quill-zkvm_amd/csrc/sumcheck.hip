@@ -362,15 +362,7 @@ QG_DEV void round_sweep(RoundLds<K, NP, BLOCK>& L, const SopLds<NP>& sp, const S
 }
 
 // lazy value < 128p (limbs < 2^32) -> normalized, < 2p
-QG_DEV R29 red128p(const R29& a) {
-  R29 x = normfull29<FrP>(a);
-  x = condsub29<FrP>(x, l9_mul_small(F29P<FrP>::P, 64));
-  x = condsub29<FrP>(x, l9_mul_small(F29P<FrP>::P, 32));
-  x = condsub29<FrP>(x, F29P<FrP>::KP20.k[16]);
-  x = condsub29<FrP>(x, F29P<FrP>::P8);
-  x = condsub29<FrP>(x, F29P<FrP>::P4);
-  return condsub29<FrP>(x, F29P<FrP>::P2);
-}
+QG_DEV R29 red128p(const R29& a) { return red128p29<FrP>(a); }
 
 // Block sums of NP per-thread values acc[t] (each < 2p, normalized) -> res[t]
 // (LDS, canonical words), visible to all threads on return.  All points move

@@ -9,11 +9,12 @@ from .device import Device, DeviceVec, Srs  # noqa: F401
 from .hyperplonk import (SumcheckProof, VirtualPolyExpr, VirtualPolynomialStore,  # noqa: F401
                          ZeroCheckProof)
 from .pcs import (KZG, DeferringKZG, EvaluationClaim, InnerProductProof,  # noqa: F401
-                  KZGOpeningProof, MLEvalProof, g2_generator, g2_mul, pairing)
+                  KZGOpeningProof, MLEvalProof, g1_lincomb, g2_generator, g2_mul, pairing)
 from .transcript import Transcript  # noqa: F401
 from .logup import (LookupMode, LookupProof, MultisetEqualityProof,  # noqa: F401
                     PermutationCheckProof, SetInclusionProof, expr_column,
                     lookup_multiplicities)
+from .multiopen import MultiOpenProof  # noqa: F401
 from .frontend import StateCell, TransitionCircuit, TransitionCircuitTarget  # noqa: F401
 from .proof import (HyperPlonk, HyperPlonkProof, TracePK, TraceProof, TraceVK,  # noqa: F401
                     TraceWitness)

@@ -180,6 +180,10 @@ PROTOTYPES = {
     "qg_eq_table_dev": (C.c_int, [P, U64P, SZ, P]),
     "qg_s_polynomial": (C.c_int, [P, U64P, SZ, U64P, SZ, U64P]),
     "qg_inner_product": (C.c_int, [P, U64P, SZ, U64P, SZ, U64P]),
+    "qg_eq_multi_dev": (C.c_int, [P, U64P, U64P, SZ, SZ, P]),
+    "qg_mle_eval_multi_dev": (C.c_int, [P, P, SZ, U64P, SZ, SZ, U64P]),
+    "qg_lincomb_dev": (C.c_int, [P, C.POINTER(P), U64P, SZ, SZ, P]),
+    "qg_g1_lincomb": (C.c_int, [U64P, U8P, U64P, SZ, U64P, U8P]),
     "qg_expr_degree": (C.c_int, [C.POINTER(ExprOp), SZ, U32P]),
     "qg_sumcheck_prove": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(U64P),
                                     C.POINTER(ExprOp), SZ, U64P, SZ, U64P, U8P, U64P, U32P,

@@ -162,6 +162,40 @@ class Device:
         check(lib().qg_eq_table_dev(self.h, u64p(pt), n, out.h), self.h)
         return out
 
+    # ---- multi-point batch opening (multiopen.py) ----
+    def eq_multi_dev(self, points, weights, out: "DeviceVec" = None) -> "DeviceVec":
+        """sum_i weights[i] eq(., points[i]) over the hypercube of len(points[0])
+        variables into a device vector (qg_eq_multi_dev)"""
+        k, n = len(points), len(points[0])
+        assert len(weights) == k and all(len(p) == n for p in points)
+        pts = fr_array([c for p in points for c in p])
+        out = out if out is not None else DeviceVec(self, 1 << n, pooled=True)
+        check(lib().qg_eq_multi_dev(self.h, u64p(pts), u64p(fr_array(weights)), k, n, out.h),
+              self.h)
+        return out
+
+    def mle_eval_multi(self, poly: "DeviceVec", points) -> list:
+        """[poly's multilinear extension at p for p in points], one pass over
+        poly (qg_mle_eval_multi_dev)"""
+        k, n = len(points), len(points[0])
+        assert all(len(p) == n for p in points)
+        pts = fr_array([c for p in points for c in p])
+        out = np.zeros((k, 4), dtype=np.uint64)
+        check(lib().qg_mle_eval_multi_dev(self.h, poly.h, 1 << n, u64p(pts), k, n, u64p(out)),
+              self.h)
+        return fr_list(out)
+
+    def lincomb_dev(self, vecs, coeffs, n: int = None, out: "DeviceVec" = None) -> "DeviceVec":
+        """sum_j coeffs[j] vecs[j] over the first n entries (qg_lincomb_dev);
+        out must not alias an input"""
+        assert len(vecs) == len(coeffs)
+        n = min(v.n for v in vecs) if n is None else n
+        out = out if out is not None else DeviceVec(self, n, pooled=True)
+        hs = (C.c_void_p * max(len(vecs), 1))(*[v.h.value for v in vecs])
+        cs = fr_array(coeffs) if len(coeffs) else np.zeros((1, 4), dtype=np.uint64)
+        check(lib().qg_lincomb_dev(self.h, hs, u64p(cs), len(vecs), n, out.h), self.h)
+        return out
+
     def eq_table(self, point):
         n = len(point)
         pt = fr_array(point)

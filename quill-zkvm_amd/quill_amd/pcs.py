@@ -74,6 +74,23 @@ def g2_mul(Q, k: int):
     return g2_from_abi(out, oinf.value)
 
 
+def g1_lincomb(points, scalars):
+    """sum_i scalars[i] points[i] on the host (qg_g1_lincomb): the combined
+    commitment of a batch opening.  None is the identity, as input and result."""
+    n = len(points)
+    assert n == len(scalars) and n >= 1
+    xy = np.zeros((n, 8), dtype=np.uint64)
+    inf = np.zeros(n, dtype=np.uint8)
+    for i, pt in enumerate(points):
+        a, f = g1_to_abi(pt)
+        xy[i, :] = list(a)
+        inf[i] = f
+    out, oinf = (C.c_uint64 * 8)(), C.c_uint8()
+    check(lib().qg_g1_lincomb(u64p(xy), inf.ctypes.data_as(C.POINTER(C.c_uint8)),
+                              u64p(fr_array(scalars)), n, out, C.byref(oinf)))
+    return g1_from_abi(out, oinf.value)
+
+
 def pairing(P, Q):
     """E::pairing(P, Q) (ark-bn254 optimal ate) in the tower layout of
     qg_pairing: 12 canonical Fq ints (c0.c0.re, c0.c0.im, c0.c1.re, ...)"""
@@ -443,6 +460,12 @@ class KZG:
                             _opening(o.poly_opening), _opening(o.poly_opening_inv),
                             _opening(o.s_opening), _opening(o.s_opening_inv))
                 for (_, _, pt, _), o in zip(items, outs)]
+
+    def open_multi(self, polys, claims, transcript: Transcript):
+        """k evaluation claims [(j, point), ...] over the device vectors `polys`
+        as one sumcheck and one opening (MultiOpenProof.prove, multiopen.py)"""
+        from .multiopen import MultiOpenProof
+        return MultiOpenProof.prove(polys, claims, self, transcript)
 
     def open(self, poly, eval_point, transcript: Transcript,
              unchanged: bool = False) -> MLEvalProof:

@@ -24,13 +24,17 @@ from .field import R_MOD
 from .frontend import TransitionCircuit
 from .hyperplonk import VirtualPolyExpr, VirtualPolynomialStore, ZeroCheckProof
 from .logup import PermutationCheckProof
-from .pcs import KZG, MLEvalProof
+from .multiopen import MultiOpenProof
+from .pcs import KZG, EvaluationClaim, MLEvalProof
 from .transcript import Transcript
 
 
 @dataclass
 class TraceProof:
-    """proof.rs:17-25"""
+    """proof.rs:17-25.  `multi_openings` (HyperPlonk.prove(multi_open=True), no
+    counterpart in the reference): the openings as MultiOpenProofs - the group
+    [full witness, id, permutation] and, when the circuit has public columns,
+    the group of those; the five opening fields are then empty / None."""
     zero_check_proof: ZeroCheckProof
     permutation_check_proof: PermutationCheckProof
     openings_zero_check: list
@@ -38,6 +42,7 @@ class TraceProof:
     opening_id: MLEvalProof
     opening_permutation: MLEvalProof
     opening_permutation_trace: MLEvalProof
+    multi_openings: list = None
 
 
 @dataclass
@@ -57,10 +62,64 @@ def _verify_opening(comm, proof: MLEvalProof, expected_point, expected_nv, pcs,
     return pcs.verify(comm, proof, transcript)
 
 
+def _multi_open_claims(zpoint, ppoint, cols: int, log2_cols: int, npub: int):
+    """the claims of the two batches of a multi_open trace proof, in the item
+    order of the one-by-one openings: over [full, id, permutation] the `cols`
+    column claims, id, permutation and the full witness at the permutation
+    point; over the public columns one claim each at the zero-check point"""
+    big = [(0, list(zpoint) + [(col >> i) & 1 for i in range(log2_cols)]) for col in range(cols)]
+    big += [(1, list(ppoint)), (2, list(ppoint)), (0, list(ppoint))]
+    return big, [(i, list(zpoint)) for i in range(npub)]
+
+
+def _verify_trace_multi(witness_commitment, vk: "TraceVK", pcs, proof: TraceProof,
+                        transcript: Transcript):
+    """_verify_trace_proof for a proof with multi_openings: the evaluations the
+    PIOP verifiers need come from the batches' `evaluations`; the batches are
+    then verified against claims whose points this verifier derives (the
+    zero-check claim and the permutation check's sumcheck point)."""
+    alpha = transcript.draw_field_element()
+    zclaim = proof.zero_check_proof.verify(transcript)
+    circuit = vk.circuit
+    cols = circuit.num_cols()
+    log2_cols, log2_rows = _log2(cols), _log2(circuit.num_rows())
+    if len(zclaim.point) != log2_rows:
+        raise ValueError("Zero check evaluation claim point length mismatch")
+    npub = len(vk.public_columns_commitments)
+    mo = proof.multi_openings
+    if (len(mo) != (2 if npub else 1) or len(mo[0].evaluations) != cols + 3
+            or (npub and len(mo[1].evaluations) != npub)):
+        raise ValueError("Multi-open proof shape mismatch")
+    # the permutation check's sumcheck point: its verifier checks this candidate
+    # against the point its own sumcheck yields
+    me = proof.permutation_check_proof.multiset_equality_proof
+    ppoint = me.opening_proof_denom_left.point()
+    if len(ppoint) != log2_rows + log2_cols:
+        raise ValueError("Permutation check evaluation point length mismatch")
+    ev = [e % R_MOD for e in mo[0].evaluations]
+    pt_claim = EvaluationClaim(ppoint, ev[cols + 2])
+    proof.permutation_check_proof.verify(transcript, pcs, pt_claim, pt_claim,
+                                         EvaluationClaim(ppoint, ev[cols]),
+                                         EvaluationClaim(ppoint, ev[cols + 1]))
+    evals = ev[:cols] + ([e % R_MOD for e in mo[1].evaluations] if npub else [])
+    acc = 0
+    for i, e in enumerate(circuit.zero_check_expressions()):
+        acc = (acc + pow(alpha, i, R_MOD) * e.evaluate(evals)) % R_MOD
+    if acc != zclaim.evaluation % R_MOD:
+        raise ValueError("Zero check evaluation mismatch")
+    big, pub = _multi_open_claims(zclaim.point, ppoint, cols, log2_cols, npub)
+    mo[0].verify([witness_commitment, vk.id_commitment, vk.permutation_commitment], big, pcs,
+                 transcript)
+    if npub:
+        mo[1].verify(vk.public_columns_commitments, pub, pcs, transcript)
+
+
 def _verify_trace_proof(witness_commitment, vk: "TraceVK", pcs, proof: TraceProof,
                         transcript: Transcript):
     """proof.rs:396-492 (with get_and_verify_column_evaluations :325-381 and
     recover_zerocheck_expr_evaluation :383-394); raises ValueError"""
+    if proof.multi_openings is not None:
+        return _verify_trace_multi(witness_commitment, vk, pcs, proof, transcript)
     alpha = transcript.draw_field_element()
     zclaim = proof.zero_check_proof.verify(transcript)
     circuit = vk.circuit
@@ -146,6 +205,11 @@ def _label_openings(proof: HyperPlonkProof, view) -> None:
             "Multiset equality opening proof verification failed")
         put(me.opening_proof_denom_right, f"trace {k} permutation-check right denominator opening",
             "Multiset equality opening proof verification failed")
+        if tp.multi_openings is not None:
+            for m, group in zip(tp.multi_openings, ("witness/id/permutation", "public-column")):
+                put(m.opening, f"trace {k} {group} multi-open opening",
+                    "Multi-open opening verification failed")
+            continue
         for i, op in enumerate(tp.openings_zero_check):
             put(op, f"trace {k} zero-check opening {i}", "Zero check opening verification failed")
         for i, op in enumerate(tp.openings_public):
@@ -296,9 +360,12 @@ class HyperPlonk:
         return list(self.trace_vks)
 
     def prove_trace(self, pcs: KZG, columns, full: DeviceVec, transcript: Transcript,
-                    pk: TracePK, circuit: TransitionCircuit) -> TraceProof:
+                    pk: TracePK, circuit: TransitionCircuit,
+                    multi_open: bool = False) -> TraceProof:
         """proof.rs:145-237 (`columns`: the witness columns on the device, or
-        this rank's row blocks; `full`: the full witness or this rank's block)"""
+        this rank's row blocks; `full`: the full witness or this rank's block).
+        multi_open: after both PIOPs, the openings as two MultiOpenProofs
+        (TraceProof.multi_openings) instead of one opening per item."""
         dev = pcs.dev
         rows, cols = circuit.num_rows(), circuit.num_cols()
         log2_rows, log2_cols = _log2(rows), _log2(cols)
@@ -321,6 +388,18 @@ class HyperPlonk:
         wv = store2.new_virtual_from_input(widx)
         pproof, ppoint = PermutationCheckProof.prove(store2, wv, wv, pk.id_poly,
                                                      pk.permutation_poly, transcript, pcs)
+
+        if multi_open:
+            if len(pk.public_rows) > 16:  # one batch holds at most 16 polynomials
+                raise ValueError("HyperPlonk.prove: multi_open takes at most 16 public columns")
+            big, pub = _multi_open_claims(zclaim.point, ppoint, cols, log2_cols,
+                                          len(pk.public_rows))
+            mo = [MultiOpenProof.prove([full, pk.id_poly, pk.permutation_poly], big, pcs,
+                                       transcript)]
+            if pub:
+                mo.append(MultiOpenProof.prove(list(pk.public_rows), pub, pcs, transcript))
+            self._close_piop_tables(store, store2, cols, len(pk.public_rows))
+            return TraceProof(zproof, pproof, [], [], None, None, None, mo)
 
         # `full` stays unchanged through these openings: its NTT transform is
         # computed once (unchanged=True, qg_mle_open_dev_ex), proofs identical.
@@ -345,16 +424,29 @@ class HyperPlonk:
         open_zc = opens[:cols]
         open_pub = opens[cols:cols + npub]
         o_id, o_perm, o_pt = opens[cols + npub:]
-        for p in store.polynomials[cols + len(pk.public_rows):]:
+        self._close_piop_tables(store, store2, cols, npub)
+        return TraceProof(zproof, pproof, open_zc, open_pub, o_id, o_perm, o_pt)
+
+    @staticmethod
+    def _close_piop_tables(store, store2, cols: int, npub: int):
+        for p in store.polynomials[cols + npub:]:
             p.close()  # eq table (zero-check)
         for p in store2.polynomials[3:]:
             p.close()  # Logup columns + eq table (permutation check)
-        return TraceProof(zproof, pproof, open_zc, open_pub, o_id, o_perm, o_pt)
 
     def prove(self, pcs: KZG, witness_traces, transcript: Transcript = None,
-              check_constraints: bool = True) -> HyperPlonkProof:
+              check_constraints: bool = True, multi_open: bool = False) -> HyperPlonkProof:
         """proof.rs:239-301.  `witness_traces`: TraceWitness (or column lists),
-        one per circuit."""
+        one per circuit.
+        multi_open=True (opt-in, no counterpart in the reference): each trace's
+        cols + npub + 3 openings become two multi-point batch openings
+        (multiopen.py), so a trace runs 2 + 2 ML openings instead of
+        2 + cols + npub + 3; the Logup denominator openings stay.  The proof
+        and the transcript differ from the default's from the first opening
+        on; HyperPlonkProof.verify accepts both kinds.  Raises on a sharded
+        device."""
+        if multi_open and (pcs.dev.world > 1 or pcs.dev.comm_info()["sharded"]):
+            raise ValueError("HyperPlonk.prove: multi_open is not supported on a sharded device")
         t = transcript if transcript is not None else Transcript(b"hyperplonk_proof")
         comms, layouts, owned = [], [], []
         for tw, vk in zip(witness_traces, self.trace_vks):
@@ -373,7 +465,7 @@ class HyperPlonk:
             t.append_g1(Cm)
         proofs = []
         for (cols, full), vk, pk in zip(layouts, self.trace_vks, self.trace_pks):
-            proofs.append(self.prove_trace(pcs, cols, full, t, pk, vk.circuit))
+            proofs.append(self.prove_trace(pcs, cols, full, t, pk, vk.circuit, multi_open))
         for b in owned:
             b.close()  # built here; caller-resident traces stay
         self.last_transcript = t

@@ -31,6 +31,16 @@ Structs (field order of the reference):
                          openings_zero_check, openings_public, opening_id,
                          opening_permutation, opening_permutation_trace (proof.rs:17-25)
   HyperPlonkProof        witness_commitment, trace_proofs (proof.rs:27-30)
+  MultiOpenProof         evaluations (Vec<Fr>), sumcheck, opening (multiopen.py;
+                         no counterpart in the reference)
+
+A TraceProof made with multi_open=True carries `multi_openings` instead of the
+five opening fields: after permutation_check_proof comes ONE flag byte, 0xFF
+(two MultiOpenProofs follow: the witness/id/permutation group, then the public
+columns) or 0xFE (a circuit without public columns: only the first).  The
+default format is unchanged; it has the u64 count of openings_zero_check at
+that position, which is the circuit's column count, a power of two, so its low
+byte is never 0xFE or 0xFF.
 
 Decoding validates like `CanonicalDeserialize` with `Validate::Yes`:
 canonical field encodings, points on the curve (G1 has cofactor 1), no
@@ -42,6 +52,7 @@ import struct
 from .field import P_MOD, R_MOD
 from .hyperplonk import SumcheckProof, ZeroCheckProof
 from .logup import MultisetEqualityProof, PermutationCheckProof
+from .multiopen import MultiOpenProof
 from .pcs import InnerProductProof, KZGOpeningProof, MLEvalProof
 from .proof import HyperPlonkProof, TraceProof
 
@@ -106,9 +117,20 @@ def _multiset(p: MultisetEqualityProof) -> bytes:
             + _mle(p.opening_proof_denom_right))
 
 
+def _multiopen(p: MultiOpenProof) -> bytes:
+    return _vec(list(p.evaluations), _fr) + _sumcheck(p.sumcheck) + _mle(p.opening)
+
+
+_MULTI_FLAGS = {2: 0xFF, 1: 0xFE}  # flag byte of a multi-open TraceProof by group count
+
+
 def _trace(p: TraceProof) -> bytes:
-    return (_zerocheck(p.zero_check_proof)
-            + _multiset(p.permutation_check_proof.multiset_equality_proof)
+    head = (_zerocheck(p.zero_check_proof)
+            + _multiset(p.permutation_check_proof.multiset_equality_proof))
+    if p.multi_openings is not None:
+        return (head + bytes([_MULTI_FLAGS[len(p.multi_openings)]])
+                + b"".join(_multiopen(m) for m in p.multi_openings))
+    return (head
             + _vec(list(p.openings_zero_check), _mle) + _vec(list(p.openings_public), _mle)
             + _mle(p.opening_id) + _mle(p.opening_permutation) + _mle(p.opening_permutation_trace))
 
@@ -118,7 +140,7 @@ def _hyperplonk(p: HyperPlonkProof) -> bytes:
 
 
 _ENCODERS = [(HyperPlonkProof, _hyperplonk), (TraceProof, _trace), (MLEvalProof, _mle),
-             (InnerProductProof, _ipa),
+             (InnerProductProof, _ipa), (MultiOpenProof, _multiopen),
              (SumcheckProof, _sumcheck), (ZeroCheckProof, _zerocheck),
              (MultisetEqualityProof, _multiset),
              (PermutationCheckProof, lambda p: _multiset(p.multiset_equality_proof)),
@@ -203,9 +225,19 @@ class _Reader:
         sc = self.sumcheck()
         return MultisetEqualityProof(cl, cr, sc, self.mle(), self.mle())
 
+    def multiopen(self):
+        ev = self.vec(self.fr)
+        return MultiOpenProof(ev, self.sumcheck(), self.mle())
+
     def trace(self):
         zc = self.zerocheck()
         pc = PermutationCheckProof(self.multiset())
+        flag = self.b[self.o] if self.o < len(self.b) else 0
+        if flag in _MULTI_FLAGS.values():
+            self.o += 1
+            groups = 2 if flag == _MULTI_FLAGS[2] else 1
+            return TraceProof(zc, pc, [], [], None, None, None,
+                              [self.multiopen() for _ in range(groups)])
         ozc, opub = self.vec(self.mle), self.vec(self.mle)
         return TraceProof(zc, pc, ozc, opub, self.mle(), self.mle(), self.mle())
 
@@ -215,7 +247,7 @@ class _Reader:
 
 
 _DECODERS = {HyperPlonkProof: "hyperplonk", TraceProof: "trace", MLEvalProof: "mle",
-             InnerProductProof: "ipa",
+             InnerProductProof: "ipa", MultiOpenProof: "multiopen",
              SumcheckProof: "sumcheck", ZeroCheckProof: "zerocheck",
              MultisetEqualityProof: "multiset", KZGOpeningProof: "kzg_opening"}
 
