@@ -16,12 +16,14 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "blake3.h"
 #include "common.h"
 #include "field29.h"
+#include "open_plan.h"
 
 using namespace qg;
 
@@ -1341,103 +1343,141 @@ static size_t trimmed_len(qg_ctx* ctx, const Fr* a, size_t n) {
   return (size_t)h;
 }
 
-// four KZG::open quotients at once (the ML opening's poly and S at r and
-// 1/r) on their trimmed lengths `Lt` (the caller's), one batched
-// suffix-Horner recursion, and the four values y = s_0 queued into pinned
-// memory (h_y[4]) without a round trip: the caller reads them after its next
-// synchronization (the quotient MSMs')
-// `slot` keeps the quotient buffers of several openings apart (a batch of
-// openings commits all of its quotients at once, mle_open_batch_device).
-// The quotient check (open_check_queue) over the untrimmed lengths `ns` is
-// queued behind the h_y copy: four words into pinned h_w, read by the caller
-// after that same synchronization (ck: d_w / h_w / checked, or d_w == nullptr
-// with QG_OPEN_CHECK=0).
-struct OpenCkOut {
-  uint32_t* d_w = nullptr;
-  uint32_t* h_w = nullptr;
-  uint8_t* checked = nullptr;  // [4]
-};
-static void kzg_quotients_batch(qg_ctx* ctx, const qg_srs* srs, const Fr* const polys[4],
-                                const size_t ns[4], const size_t Lt[4], const Fr xs[4],
-                                qg_kzg_opening* const outs[4], std::vector<const Fr*>& qs,
-                                std::vector<size_t>& qns, Fr* h_y, const OpenCkOut& ck,
-                                size_t slot = 0) {
-  std::vector<ShIn<1>> jobs;
-  Fr* s[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 4; i++) {
-    fr_export(xs[i], outs[i]->x);
-    if (Lt[i] == 0) continue;
-    QG_CHECK(Lt[i] - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-    s[i] = ctx->scratch_as<Fr>("open_s#" + std::to_string(4 * slot + i), Lt[i]);
-    jobs.push_back({polys[i], Lt[i], {xs[i]}, {s[i]}});
-  }
-  {
-    QgTimed tm(ctx, "kzg_division");
-    suffix_horner<1>(ctx, jobs);
-  }
-  for (int i = 0; i < 4; i++)
-    if (s[i]) fault_quotient(ctx, s[i] + 1, Lt[i] - 1);
-  Fr* d_y = ctx->scratch_as<Fr>("open_y#" + std::to_string(slot), 4);
-  QG_HIP(hipMemsetAsync(d_y, 0, 4 * sizeof(Fr), ctx->stream));
-  for (int i = 0; i < 4; i++)
-    if (s[i])
-      QG_HIP(hipMemcpyAsync(d_y + i, s[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-  QG_HIP(hipMemcpyAsync(h_y, d_y, 4 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  if (ck.d_w) {
-    OpenCk c4[4];
-    for (int i = 0; i < 4; i++) {
-      c4[i] = {ns[i] ? polys[i] : nullptr, ns[i], s[i] ? s[i] + 1 : nullptr,
-               s[i] ? Lt[i] - 1 : 0,       d_y + i, xs[i]};
-      ck.checked[i] = s[i] ? CK_QUOT : ns[i] ? CK_ZERO : CK_NONE;
-    }
-    open_check_queue(ctx, c4, ck.d_w);
-    QG_HIP(hipMemcpyAsync(ck.h_w, ck.d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-  }
-  qs.clear();
-  qns.clear();
-  for (int i = 0; i < 4; i++) {
-    qs.push_back(s[i] ? s[i] + 1 : nullptr);
-    qns.push_back(s[i] ? Lt[i] - 1 : 0);
-  }
+// ---------------------------------------------------------------- quotient stage
+// The second half of every proof here: polynomials and points in, KZG::open
+// quotients (kzg.rs:75-96), their values y, kzg.rs:85's check and one MSM
+// batch out.  The jobs of both stages (single-context below, sharded further
+// down) come in groups of `per` - one proof's openings: 4 for an ML opening
+// (OPEN_QNAME), 6 for the inner-product argument (IPA_QNAME), 1 for a bare
+// KZG::open - and inside a group in pairs: jobs 2p and 2p + 1 are one
+// polynomial at two points (r, 1/r).  Scratch and pinned slots are named
+// open_<what>, per-job ones open_<what>#<job index>, for every protocol.
+
+// The scans of one group's nonempty jobs, in job order: groups of SH_J (an ML
+// opening's four are one suffix_horner<1>), or, where the caller's jobs may
+// pair and QG_IPA_PAIRED=1 (read per call, here only), each pair as one
+// suffix_horner<2> job; the same bits either way.
+static void quotient_scans(qg_ctx* ctx, const std::vector<ShIn<1>>& in, bool may_pair) {
+  QgTimed tm(ctx, "kzg_division");
+  const char* pe = may_pair ? getenv("QG_IPA_PAIRED") : nullptr;
+  if (!(pe && atoi(pe) != 0)) return suffix_horner_many(ctx, in);
+  std::vector<ShIn<2>> two;
+  for (size_t i = 0; i + 1 < in.size(); i += 2)
+    two.push_back({in[i].c, in[i].L, {in[i].x[0], in[i + 1].x[0]}, {in[i].s[0], in[i + 1].s[0]}});
+  suffix_horner<2>(ctx, two);
 }
 
-// KZG::open on a device polynomial; fills x, y, proof
+// One KZG::open on a device polynomial p of n coefficients whose trimmed
+// length is Lt (the caller's: DensePolynomial::from_coefficients_slice trims
+// what KZG::open is given, kzg.rs:77), at x; `out` receives x, y and the proof.
+struct QuotJob {
+  const Fr* p;
+  size_t n, Lt;
+  Fr x;
+  qg_kzg_opening* out;
+};
+
+// What quotients_queue leaves for after the caller's one MSM batch over
+// (qs, qns) and its synchronization: the values y = s_0 and the check words
+// in pinned memory, queued without a round trip.
+struct QuotStage {
+  size_t per = 1, wpg = 4;  // check words per group: open_check_queue's fours
+  std::vector<qg_kzg_opening*> outs;
+  std::vector<const Fr*> qs;  // q_i = s_{i+1}, i < Lt - 1 (kzg.rs:88-89)
+  std::vector<size_t> qns;
+  const Fr* h_y = nullptr;
+  const uint32_t* h_w = nullptr;
+  std::vector<uint8_t> checked;  // empty: QG_OPEN_CHECK=0
+
+  void fit(const qg_srs* srs) const {
+    for (size_t n : qns)
+      QG_CHECK(n <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+  }
+  // after the synchronization: count, and raise on the first failed quotient
+  void settle(qg_ctx* ctx, const char* const* qname) const {
+    if (checked.empty()) return;
+    std::vector<uint32_t> bad(outs.size());
+    for (size_t j = 0; j < bad.size(); j++) bad[j] = h_w[j / per * wpg + j % per];
+    open_check_settle(ctx, bad, checked, per, qname);
+  }
+  void store(const std::vector<G1Affine>& pis) const {
+    for (size_t j = 0; j < outs.size(); j++) {
+      fr_export(h_y[j], outs[j]->y);
+      g1_export(pis[j], outs[j]->proof_xy, &outs[j]->proof_inf);
+    }
+  }
+};
+
+// Queues, group by group: one batched suffix-Horner recursion over the
+// trimmed lengths, the test fault, the values y into pinned memory, and the
+// quotient check (open_check_queue's groups of four in job order, so equal
+// (p, n) are evaluated once per four) over the UNtrimmed lengths: p over all n
+// coefficients, q as the MSM will read it; a job trimmed to nothing has no
+// quotient, y = 0, and all n coefficients must be 0.
+static QuotStage quotients_queue(qg_ctx* ctx, const std::vector<QuotJob>& jobs, size_t per,
+                                 bool may_pair = false) {
+  const size_t J = jobs.size(), G = J / per;
+  QuotStage st;
+  st.per = per, st.wpg = 4 * div_up(per, (size_t)4);
+  std::vector<Fr*> s(J, nullptr);
+  size_t nmax = 0;
+  for (size_t j = 0; j < J; j++) {
+    fr_export(jobs[j].x, jobs[j].out->x);
+    st.outs.push_back(jobs[j].out);
+    nmax = std::max(nmax, jobs[j].n);
+    if (jobs[j].Lt) s[j] = ctx->scratch_as<Fr>("open_s#" + std::to_string(j), jobs[j].Lt);
+    st.qs.push_back(s[j] ? s[j] + 1 : nullptr);
+    st.qns.push_back(s[j] ? jobs[j].Lt - 1 : 0);
+  }
+  Fr* d_y = ctx->scratch_as<Fr>("open_y", J);
+  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("open_y_h", J * sizeof(Fr)));
+  const bool check = open_check_on();
+  uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", G * st.wpg) : nullptr;
+  uint32_t* h_w =
+      reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", G * st.wpg * sizeof(uint32_t)));
+  // the evaluation's span scratch at its largest before anything is queued
+  if (check) poly_eval_reserve(ctx, 6, nmax);
+  if (check) st.checked.assign(J, CK_NONE);
+  QG_HIP(hipMemsetAsync(d_y, 0, J * sizeof(Fr), ctx->stream));
+  for (size_t g = 0; g < G; g++) {
+    const size_t j0 = g * per;
+    std::vector<ShIn<1>> in;
+    for (size_t j = j0; j < j0 + per; j++)
+      if (s[j]) in.push_back({jobs[j].p, jobs[j].Lt, {jobs[j].x}, {s[j]}});
+    quotient_scans(ctx, in, may_pair);
+    for (size_t j = j0; j < j0 + per; j++)
+      if (s[j]) fault_quotient(ctx, s[j] + 1, jobs[j].Lt - 1);
+    for (size_t j = j0; j < j0 + per; j++)
+      if (s[j])
+        QG_HIP(hipMemcpyAsync(d_y + j, s[j], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    QG_HIP(hipMemcpyAsync(h_y + j0, d_y + j0, per * sizeof(Fr), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    if (!check) continue;
+    std::vector<OpenCk> ck(st.wpg);
+    for (size_t j = j0; j < j0 + per; j++) {
+      const QuotJob& q = jobs[j];
+      ck[j - j0] = {q.n ? q.p : nullptr, q.n, st.qs[j], st.qns[j], d_y + j, q.x};
+      st.checked[j] = s[j] ? CK_QUOT : q.n ? CK_ZERO : CK_NONE;
+    }
+    for (size_t c = 0; c < st.wpg; c += 4) open_check_queue(ctx, &ck[c], d_w + g * st.wpg + c);
+    QG_HIP(hipMemcpyAsync(h_w + g * st.wpg, d_w + g * st.wpg, st.wpg * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost, ctx->stream));
+  }
+  st.h_y = h_y, st.h_w = h_w;
+  return st;
+}
+
+// KZG::open on a device polynomial; fills x, y, proof.  A stage of one job in
+// this path's own order: the check settles before the degree is judged and
+// the quotient committed.
 static void kzg_open_device(qg_ctx* ctx, const qg_srs* srs, const Fr* c, size_t L, const Fr& x,
                             qg_kzg_opening* out) {
-  fr_export(x, out->x);
-  // DensePolynomial::from_coefficients_slice trims
   const size_t Lt = fault_short_trim(ctx, trimmed_len(ctx, c, L));
-  Fr y = Fr::zero();
-  G1Affine pi = G1Affine::infinity();
-  Fr* s = Lt ? ctx->scratch_as<Fr>("open_s#0", Lt) : nullptr;
-  if (s) {
-    {
-      QgTimed tm(ctx, "kzg_division");
-      suffix_horner<1>(ctx, {{c, Lt, {x}, {s}}});
-    }
-    fault_quotient(ctx, s + 1, Lt - 1);
-    QG_HIP(hipMemcpyAsync(&y, s, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  // kzg.rs:85: p over all L coefficients, q as the MSM will read it; trimmed to
-  // nothing: all L coefficients must be 0
-  const bool check = L > 0 && open_check_on();
-  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * sizeof(uint32_t)));
-  if (check) {
-    uint32_t* d_w = ctx->scratch_as<uint32_t>("open_ck_w", 4);
-    const OpenCk c4[4] = {{c, L, s ? s + 1 : nullptr, s ? Lt - 1 : 0, s, x}, {}, {}, {}};
-    open_check_queue(ctx, c4, d_w);
-    QG_HIP(hipMemcpyAsync(h_w, d_w, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (s || check) ctx->sync();
-  if (check) open_check_settle(ctx, {h_w[0]}, {s ? CK_QUOT : CK_ZERO}, 1, OPEN_UNAME);
-  if (s) {
-    // q_i = s_{i+1}, i < Lt - 1; commit(q) (kzg.rs:88-89)
-    QG_CHECK(Lt - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-    pi = msm_device(ctx, srs, s + 1, Lt - 1);
-  }
-  fr_export(y, out->y);
-  g1_export(pi, out->proof_xy, &out->proof_inf);
+  const QuotStage st = quotients_queue(ctx, {{c, L, Lt, x, out}}, 1);
+  ctx->sync();
+  st.settle(ctx, OPEN_UNAME);
+  st.fit(srs);
+  st.store(msm_device_batch(ctx, srs, st.qs, st.qns));
 }
 
 // ---------------------------------------------------------------- sharded opening
@@ -1462,6 +1502,133 @@ static void allgather_host(qg_ctx* ctx, const void* src, size_t bytes, void* dst
   QG_HIP(hipMemcpyAsync(dst_all, dr, bytes * (size_t)ctx->world, hipMemcpyDeviceToHost,
                         ctx->stream));
   ctx->sync();
+}
+
+// One quotient of a sharded proof: this rank's slice p (L coefficients) of a
+// polynomial whose global trimmed length is glt, at x.  glt and x are gathered
+// or transcript values: the same on every rank.
+struct ShardQuotJob {
+  const Fr* p;
+  size_t L, glt;
+  Fr x;
+  qg_kzg_opening* out;
+};
+
+// The quotient stage on a sharded context (groups and pairs as in
+// quotients_queue), collective: the jobs' local suffix-Horner scans of this
+// rank's live coefficients into s_j[0 .. le_j), T_j = s_j[0]; ONE allgather of
+// every rank's T; the carries (x^(le - i) C) on the host and the device; the
+// quotient check on the ranks' summed parts - per group p(sigma) of each pair
+// over the untrimmed local slices, then every q(sigma): ONE allgather, after
+// the carries, which need the first - around the quotient commitments as ONE
+// sharded MSM batch; the export.  Returns the values y.  before_settle runs
+// after the last synchronization and before a failed check leaves the call
+// (the caller's scratch release).  The caller has judged the degrees
+// (op_fits), on gathered values: nothing here ends the call on a value that
+// differs between ranks.
+static std::vector<Fr> quotients_sharded(qg_ctx* ctx, const qg_srs* srs,
+                                         const std::vector<ShardQuotJob>& jobs, size_t per,
+                                         bool may_pair, const char* const* qname,
+                                         const std::function<void()>& before_settle = {}) {
+  const size_t J = jobs.size(), G = J / per;
+  const size_t W = (size_t)ctx->world, rank = (size_t)ctx->rank;
+  std::vector<size_t> le(J);
+  std::vector<Fr*> sq(J);
+  size_t max_le = 0;
+  for (size_t j = 0; j < J; j++) {
+    le[j] = op_live(jobs[j].glt, rank, jobs[j].L);
+    sq[j] = ctx->scratch_as<Fr>("open_s#" + std::to_string(j), le[j] + 1);
+    max_le = std::max(max_le, le[j]);
+  }
+  Fr* d_T = ctx->scratch_as<Fr>("open_T", J);
+  QG_HIP(hipMemsetAsync(d_T, 0, J * sizeof(Fr), ctx->stream));
+  for (size_t g = 0; g < G; g++) {
+    std::vector<ShIn<1>> in;
+    for (size_t j = g * per; j < (g + 1) * per; j++)
+      if (le[j]) in.push_back({jobs[j].p, le[j], {jobs[j].x}, {sq[j]}});
+    quotient_scans(ctx, in, may_pair);
+    for (size_t j = g * per; j < (g + 1) * per; j++)
+      if (le[j])
+        QG_HIP(hipMemcpyAsync(d_T + j, sq[j], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  // exchange: every rank's T values
+  Fr* d_Tall = ctx->scratch_as<Fr>("open_T_all", J * W);
+  comm_allgather_bytes(ctx, d_T, d_Tall, J * sizeof(Fr));
+  std::vector<Fr> Tall(J * W);
+  QG_HIP(hipMemcpyAsync(Tall.data(), d_Tall, J * W * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  // C_rank = sum_{r' > rank} T_r' x^((r' - rank - 1) L);  y = sum_r T_r x^(r L)
+  std::vector<Fr> ys(J);
+  Fr* pw = ctx->scratch_as<Fr>("open_pw", max_le + 1);
+  std::vector<const Fr*> qs(J);
+  std::vector<size_t> qn(J);
+  for (size_t j = 0; j < J; j++) {
+    const Fr x = jobs[j].x, xL = fpow_small(x, jobs[j].L);
+    Fr C = Fr::zero(), y = Fr::zero();
+    for (size_t r = W; r-- > 0;) {
+      if (r == rank) C = y;
+      y = Tall[r * J + j] + xL * y;
+    }
+    ys[j] = y;
+    if (le[j] > 0) {
+      QgTimed tm(ctx, "kzg_division");
+      const int KP = 64;
+      hipLaunchKernelGGL(k_powers_ml, dim3(div_up(div_up(le[j] + 1, (size_t)KP), ML_BLOCK)),
+                         dim3(ML_BLOCK), 0, ctx->stream, x, le[j] + 1, KP, pw);
+      QG_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_sh_carry, dim3(div_up(le[j] + 1, ML_BLOCK)), dim3(ML_BLOCK), 0,
+                         ctx->stream, sq[j], le[j], pw, C);
+      QG_LAUNCH_CHECK();
+    }
+    // q_i = s_{i+1} for global i < glt - 1; this rank's part starts at s + 1
+    qn[j] = op_qlive(jobs[j].glt, rank, jobs[j].L);
+    qs[j] = sq[j] + 1;
+    fault_quotient(ctx, sq[j] + 1, qn[j]);
+  }
+  // kzg.rs:85 on the ranks' summed parts; per group per / 2 + per values
+  const bool check = open_check_on();
+  const size_t E = G * (per / 2 + per);
+  auto p_at = [&](size_t j) { return j / per * (per / 2 + per) + j % per / 2; };
+  auto q_at = [&](size_t j) { return j / per * (per / 2 + per) + per / 2 + j % per; };
+  Fr* d_ev = check ? ctx->scratch_as<Fr>("open_ck_ev_sh", E) : nullptr;
+  if (check) {
+    QgTimed tm(ctx, "kzg_open_check");
+    std::vector<EvIn> in(E);
+    for (size_t j = 0; j < J; j++) {
+      const uint64_t off = (uint64_t)(rank * jobs[j].L);
+      in[p_at(j)] = {jobs[j].p, jobs[j].L, off};
+      in[q_at(j)] = {qs[j], qn[j], off};
+    }
+    poly_eval_queue(ctx, in, ctx->open_sigma, d_ev);
+  }
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qn);
+  std::vector<uint32_t> bad(J, 0);
+  std::vector<uint8_t> checked(J, 0);
+  if (check) {
+    Fr* d_evall = ctx->scratch_as<Fr>("open_ck_ev_all", E * W);
+    comm_allgather_bytes(ctx, d_ev, d_evall, E * sizeof(Fr));
+    std::vector<Fr> ev(E * W);
+    QG_HIP(hipMemcpyAsync(ev.data(), d_evall, ev.size() * sizeof(Fr), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    ctx->sync();
+    for (size_t j = 0; j < J; j++) {
+      Fr P = Fr::zero(), Q = Fr::zero();
+      for (size_t r = 0; r < W; r++) {
+        P = P + ev[r * E + p_at(j)];
+        Q = Q + ev[r * E + q_at(j)];
+      }
+      checked[j] = jobs[j].glt ? CK_QUOT : CK_ZERO;
+      bad[j] = open_check_host(P, ys[j], Q, ctx->open_sigma, jobs[j].x);
+    }
+  }
+  if (before_settle) before_settle();
+  if (check) open_check_settle(ctx, bad, checked, per, qname);
+  for (size_t j = 0; j < J; j++) {
+    fr_export(jobs[j].x, jobs[j].out->x);
+    fr_export(ys[j], jobs[j].out->y);
+    g1_export(pis[j], jobs[j].out->proof_xy, &jobs[j].out->proof_inf);
+  }
+  return ys;
 }
 
 // ---------------------------------------------------------------- sharded S polynomial
@@ -1818,6 +1985,18 @@ static OpenChallenge open_transcript_step(uint8_t state[32], const uint64_t* poi
   QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
   return {r, finv(r)};
 }
+// ... and of the inner-product argument (ipa.rs:76-83): append inner_product
+// and s_comm; draw r
+static OpenChallenge ipa_transcript_step(uint8_t state[32], const Fr& ip, const G1Affine& s_comm) {
+  uint8_t b32[32], b64[64];
+  fr_to_bytes(ip, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr r = transcript_draw_fr(state);
+  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  return {r, finv(r)};
+}
 
 // the four KZG openings of a proof in quotient order (OPEN_QNAME)
 struct Open4 {
@@ -1825,6 +2004,14 @@ struct Open4 {
 };
 static Open4 open4(qg_mle_proof& p) {
   return {{&p.poly_opening, &p.poly_opening_inv, &p.s_opening, &p.s_opening_inv}};
+}
+// ... and the six of an inner-product proof (IPA_QNAME)
+struct Open6 {
+  qg_kzg_opening* o[6];
+};
+static Open6 open6(qg_ipa_proof& p) {
+  return {{&p.f_opening, &p.f_opening_inv, &p.g_opening, &p.g_opening_inv, &p.s_opening,
+           &p.s_opening_inv}};
 }
 
 // Per-item scratch of a batch of openings (S vectors, quotient vectors, eq
@@ -1839,7 +2026,6 @@ static void open_batch_trim_scratch(qg_ctx* ctx, size_t K) {
     ctx->arena.release("mleb_S#" + std::to_string(k));
     ctx->arena.release("mleb_Sl#" + std::to_string(k));
     ctx->arena.release("mleb_z#" + std::to_string(k));
-    ctx->arena.release("open_y#" + std::to_string(k));
   }
   for (size_t j = 4 * OPEN_KEEP; j < 4 * K; j++) {
     ctx->arena.release("open_s#" + std::to_string(j));
@@ -1855,13 +2041,16 @@ static void open_batch_trim_scratch(qg_ctx* ctx, size_t K) {
 // table, the local dot, the gathered vector's residue-split S slice
 // (s_poly_sharded; QG_S_REPLICATED=1: the whole S on every rank, A/B runs) and
 // the local trimmed lengths are queued; ONE allgather carries every item's dot
-// part and local lengths; the S commitments run as ONE MSM batch (one
+// part and local lengths and this rank's shard size, so the global trimmed
+// lengths and the "Polynomial degree exceeds max degree" decision (op_fits)
+// are the same on every rank; the S commitments run as ONE MSM batch (one
 // allgather of the per-rank partials); the transcript steps run on the host
-// in item order; the 4K quotients' local suffix-Horner scans are queued, ONE
-// allgather carries their slice-end values T; the carries (x^(le - i) C) are
-// applied; the 4K quotient commitments run as ONE sharded MSM batch.  Four
-// exchanges per call; the proofs and the final transcript state of a batch of
-// K equal K batches of one, and the single-context ones
+// in item order; the 4K quotients are quotients_sharded's (one allgather of
+// the slice-end values T, one of the check's evaluations, ONE sharded MSM
+// batch).  Four exchanges per call, the check's included; between the first
+// collective and the last no decision that ends the call is taken on a value
+// that differs between ranks.  The proofs and the final transcript state of a
+// batch of K equal K batches of one, and the single-context ones
 // (tests/test_gpu_multirank.py).
 static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
                                    const std::vector<MleOpenItem>& items, uint8_t state[32],
@@ -1873,12 +2062,14 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
     QG_CHECK(it.n * W == ((size_t)1 << it.nvars), QG_ERR_UNSUPPORTED,
              "sharded opening needs world * local length == 2^nvars");
   }
-  // small per-item values of this rank: K dot parts, 2K local trimmed lengths
-  const size_t sm_bytes = K * sizeof(Fr) + 2 * K * sizeof(unsigned long long);
+  // small values of this rank: K dot parts, 2K local trimmed lengths, the shard size
+  const size_t sm_bytes = K * sizeof(Fr) + (2 * K + 1) * sizeof(unsigned long long);
   uint8_t* d_sm = ctx->scratch_as<uint8_t>("mlebs_small", sm_bytes);
   Fr* d_part = reinterpret_cast<Fr*>(d_sm);
   unsigned long long* d_len = reinterpret_cast<unsigned long long*>(d_sm + K * sizeof(Fr));
   QG_HIP(hipMemsetAsync(d_sm, 0, sm_bytes, ctx->stream));
+  const unsigned long long my_n = srs->n;
+  QG_HIP(hipMemcpyAsync(d_len + 2 * K, &my_n, sizeof my_n, hipMemcpyHostToDevice, ctx->stream));
   const char* rep = getenv("QG_S_REPLICATED");  // read per call: tests toggle it in-process
   const bool replicated = rep && atoi(rep) != 0;
   std::vector<Fr*> Sl(K);
@@ -1915,160 +2106,54 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
                        (unsigned long long)ctx->open_fault_value);
     QG_LAUNCH_CHECK();
   }
-  // exchange 1: dot parts and local lengths of every rank
+  // exchange 1: dot parts, local lengths and shard size of every rank
   uint8_t* d_all = ctx->scratch_as<uint8_t>("mlebs_small_all", sm_bytes * W);
   comm_allgather_bytes(ctx, d_sm, d_all, sm_bytes);
   std::vector<uint8_t> h_all(sm_bytes * W);
   QG_HIP(hipMemcpyAsync(h_all.data(), d_all, sm_bytes * W, hipMemcpyDeviceToHost, ctx->stream));
   ctx->sync();
+  auto lens_of = [&](size_t r) {
+    return reinterpret_cast<const unsigned long long*>(h_all.data() + r * sm_bytes + K * sizeof(Fr));
+  };
   std::vector<Fr> evaluation(K, Fr::zero());
-  std::vector<size_t> Lt(K, 0), Slen(K, 0);
-  for (size_t r = 0; r < W; r++) {
-    const uint8_t* b = h_all.data() + r * sm_bytes;
-    const Fr* parts = reinterpret_cast<const Fr*>(b);
-    const unsigned long long* lens = reinterpret_cast<const unsigned long long*>(b + K * sizeof(Fr));
-    for (size_t k = 0; k < K; k++) {
-      evaluation[k] = evaluation[k] + parts[k];
-      const size_t L = items[k].n;
-      // the global trimmed length: the largest (rank offset + local length) of a nonzero slice
-      if (lens[2 * k]) Lt[k] = std::max(Lt[k], r * L + (size_t)lens[2 * k]);
-      if (lens[2 * k + 1]) Slen[k] = std::max(Slen[k], r * L + (size_t)lens[2 * k + 1]);
-    }
+  std::vector<size_t> Lt(K), Slen(K);  // global trimmed lengths
+  std::vector<unsigned long long> shard(W), loc(W);
+  for (size_t r = 0; r < W; r++) shard[r] = lens_of(r)[2 * K];
+  for (size_t k = 0; k < K; k++) {
+    const size_t L = items[k].n;
+    for (size_t r = 0; r < W; r++)
+      evaluation[k] = evaluation[k] + reinterpret_cast<const Fr*>(h_all.data() + r * sm_bytes)[k];
+    for (size_t r = 0; r < W; r++) loc[r] = lens_of(r)[2 * k];
+    Lt[k] = op_global_len(loc.data(), W, L);
+    for (size_t r = 0; r < W; r++) loc[r] = lens_of(r)[2 * k + 1];
+    Slen[k] = op_global_len(loc.data(), W, L);
+    // every rank knows every rank's part lengths and bases: the same decision on all
+    const size_t opened[2] = {Lt[k], Slen[k]};
+    QG_CHECK(op_fits(Slen[k], opened, 2, L, shard.data(), W), QG_ERR_INVALID,
+             "Polynomial degree exceeds max degree");
   }
   // the S commitments: one MSM batch over the local parts of the trimmed S
-  std::vector<const Fr*> sp(K);
+  std::vector<const Fr*> sp(Sl.begin(), Sl.end());
   std::vector<size_t> sloc(K);
-  for (size_t k = 0; k < K; k++) {
-    const size_t L = items[k].n, off = rank * L;
-    sp[k] = Sl[k];
-    sloc[k] = Slen[k] > off ? std::min(L, Slen[k] - off) : 0;
-    QG_CHECK(sloc[k] <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-  }
+  for (size_t k = 0; k < K; k++) sloc[k] = op_live(Slen[k], rank, items[k].n);
   const std::vector<G1Affine> s_comm = msm_device_batch(ctx, srs, sp, sloc);
-  // the transcript steps in item order (mlpcs.rs:100-107)
-  std::vector<Fr> xs(4 * K);
+  // the transcript steps in item order (mlpcs.rs:100-107), then the 4K
+  // quotients: job 4k + i is item k's OPEN_QNAME[i]
+  std::vector<ShardQuotJob> jobs;
   for (size_t k = 0; k < K; k++) {
     const OpenChallenge ch =
         open_transcript_step(state, items[k].point, items[k].nvars, evaluation[k], s_comm[k]);
     fr_export(evaluation[k], outs[k].evaluation);
     g1_export(s_comm[k], outs[k].s_comm_xy, &outs[k].s_comm_inf);
-    xs[4 * k] = xs[4 * k + 2] = ch.r;
-    xs[4 * k + 1] = xs[4 * k + 3] = ch.r_inv;
-  }
-  // the 4K quotients' local scans: job j = 4k + i (global trimmed length
-  // glt_j, slices of L) scans this rank's le live coefficients into
-  // s_j[0..le); T_j = s_j[0]
-  const size_t J = 4 * K;
-  std::vector<size_t> le(J, 0), glt(J, 0);
-  std::vector<Fr*> sq(J, nullptr);
-  Fr* d_T = ctx->scratch_as<Fr>("mlebs_T", J);
-  QG_HIP(hipMemsetAsync(d_T, 0, J * sizeof(Fr), ctx->stream));
-  for (size_t k = 0; k < K; k++) {
-    const size_t L = items[k].n, off = rank * L;
-    std::vector<ShIn<1>> jobs;
-    for (int i = 0; i < 4; i++) {
-      const size_t j = 4 * k + i;
-      glt[j] = i < 2 ? Lt[k] : Slen[k];
-      le[j] = glt[j] > off ? std::min(L, glt[j] - off) : 0;
-      sq[j] = ctx->scratch_as<Fr>("open_s#" + std::to_string(j), le[j] + 1);
-      if (le[j]) jobs.push_back({i < 2 ? items[k].poly : Sl[k], le[j], {xs[j]}, {sq[j]}});
-    }
-    {
-      QgTimed tm(ctx, "kzg_division");
-      suffix_horner<1>(ctx, jobs);
-    }
-    for (int i = 0; i < 4; i++) {
-      const size_t j = 4 * k + i;
-      if (le[j])
-        QG_HIP(hipMemcpyAsync(d_T + j, sq[j], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-  }
-  // exchange 2: every rank's T values
-  Fr* d_Tall = ctx->scratch_as<Fr>("mlebs_T_all", J * W);
-  comm_allgather_bytes(ctx, d_T, d_Tall, J * sizeof(Fr));
-  std::vector<Fr> Tall(J * W);
-  QG_HIP(hipMemcpyAsync(Tall.data(), d_Tall, J * W * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  ctx->sync();
-  // C_rank = sum_{r' > rank} T_r' x^((r' - rank - 1) L);  y = sum_r T_r x^(r L)
-  std::vector<Fr> ys(J);
-  size_t max_le = 0;
-  for (size_t j = 0; j < J; j++) max_le = std::max(max_le, le[j]);
-  Fr* pw = ctx->scratch_as<Fr>("open_pw", max_le + 1);
-  std::vector<const Fr*> qs(J);
-  std::vector<size_t> qn(J);
-  for (size_t j = 0; j < J; j++) {
-    const size_t L = items[j / 4].n, off = rank * L;
-    const Fr x = xs[j], xL = fpow_small(x, L);
-    Fr C = Fr::zero(), y = Fr::zero();
-    for (size_t r = W; r-- > 0;) {
-      if (r == rank) C = y;
-      y = Tall[r * J + j] + xL * y;
-    }
-    ys[j] = y;
-    if (le[j] > 0) {
-      QgTimed tm(ctx, "kzg_division");
-      const int KP = 64;
-      hipLaunchKernelGGL(k_powers_ml, dim3(div_up(div_up(le[j] + 1, (size_t)KP), ML_BLOCK)),
-                         dim3(ML_BLOCK), 0, ctx->stream, x, le[j] + 1, KP, pw);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_sh_carry, dim3(div_up(le[j] + 1, ML_BLOCK)), dim3(ML_BLOCK), 0,
-                         ctx->stream, sq[j], le[j], pw, C);
-      QG_LAUNCH_CHECK();
-    }
-    // q_i = s_{i+1} for global i < Lt - 1; this rank's part starts at s + 1
-    qn[j] = (glt[j] > 0 && glt[j] - 1 > off) ? std::min(le[j], glt[j] - 1 - off) : 0;
-    QG_CHECK(qn[j] <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-    qs[j] = sq[j] + 1;
-    fault_quotient(ctx, sq[j] + 1, qn[j]);
-  }
-  // the quotient check: per item this rank's parts of p(sigma), S(sigma) and the
-  // four q(sigma); ONE more allgather per batch carries them (they exist only
-  // after the carries, which need exchange 2)
-  const bool check = open_check_on();
-  Fr* d_ev = check ? ctx->scratch_as<Fr>("open_ck_ev_sh", 6 * K) : nullptr;
-  if (check) {
-    QgTimed tm(ctx, "kzg_open_check");
-    std::vector<EvIn> in;
-    for (size_t k = 0; k < K; k++) {
-      const uint64_t off = (uint64_t)(rank * items[k].n);
-      in.push_back({items[k].poly, items[k].n, off});
-      in.push_back({Sl[k], items[k].n, off});
-      for (int i = 0; i < 4; i++) in.push_back({qs[4 * k + i], qn[4 * k + i], off});
-    }
-    poly_eval_queue(ctx, in, ctx->open_sigma, d_ev);
-  }
-  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qn);
-  if (check) {
-    Fr* d_evall = ctx->scratch_as<Fr>("open_ck_ev_all", 6 * K * W);
-    comm_allgather_bytes(ctx, d_ev, d_evall, 6 * K * sizeof(Fr));
-    std::vector<Fr> all(6 * K * W);
-    QG_HIP(hipMemcpyAsync(all.data(), d_evall, all.size() * sizeof(Fr), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    ctx->sync();
-    std::vector<uint32_t> bad(J, 0);
-    std::vector<uint8_t> checked(J, 0);
-    for (size_t j = 0; j < J; j++) {
-      const size_t k = j / 4, i = j % 4;
-      Fr P = Fr::zero(), Q = Fr::zero();
-      for (size_t rk = 0; rk < W; rk++) {
-        P = P + all[6 * (rk * K + k) + (i < 2 ? 0 : 1)];
-        Q = Q + all[6 * (rk * K + k) + 2 + i];
-      }
-      checked[j] = glt[j] ? CK_QUOT : CK_ZERO;
-      bad[j] = open_check_host(P, ys[j], Q, ctx->open_sigma, xs[j]);
-    }
-    open_batch_trim_scratch(ctx, K);  // (before a failure leaves the call)
-    open_check_settle(ctx, bad, checked, 4, OPEN_QNAME);
-  }
-  for (size_t k = 0; k < K; k++) {
     const Open4 o4 = open4(outs[k]);
-    for (int i = 0; i < 4; i++) {
-      fr_export(xs[4 * k + i], o4.o[i]->x);
-      fr_export(ys[4 * k + i], o4.o[i]->y);
-      g1_export(pis[4 * k + i], o4.o[i]->proof_xy, &o4.o[i]->proof_inf);
-    }
+    const size_t L = items[k].n;
+    jobs.push_back({items[k].poly, L, Lt[k], ch.r, o4.o[0]});
+    jobs.push_back({items[k].poly, L, Lt[k], ch.r_inv, o4.o[1]});
+    jobs.push_back({Sl[k], L, Slen[k], ch.r, o4.o[2]});
+    jobs.push_back({Sl[k], L, Slen[k], ch.r_inv, o4.o[3]});
   }
-  open_batch_trim_scratch(ctx, K);
+  quotients_sharded(ctx, srs, jobs, 4, false, OPEN_QNAME,
+                    [&] { open_batch_trim_scratch(ctx, K); });
 }
 
 // MLEvalProof::prove (mlpcs.rs:83-124) for K >= 1 device-resident evaluation
@@ -2179,48 +2264,24 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
     fr_export(evaluation, outs[k].evaluation);
     g1_export(s_comm[k], outs[k].s_comm_xy, &outs[k].s_comm_inf);
   }
-  // every item's four quotients (mlpcs.rs:108-113), then all 4K commitments
-  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("mleb_y_h", 4 * K * sizeof(Fr)));
-  std::vector<const Fr*> qs_all;
-  std::vector<size_t> qns_all;
-  const bool check = open_check_on();
-  std::vector<uint8_t> checked(4 * K, 0);
-  uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 4 * K) : nullptr;
-  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 4 * K * sizeof(uint32_t)));
-  if (check) {  // the evaluation's span scratch at its largest before anything is queued
-    size_t nmax = 0;
-    for (size_t k = 0; k < K; k++) nmax = std::max(nmax, std::max(items[k].n, Sn[k]));
-    poly_eval_reserve(ctx, 6, nmax);
-  }
+  // every item's four quotients (mlpcs.rs:108-113; job 4k + i is item k's
+  // OPEN_QNAME[i]), then all 4K commitments
+  std::vector<QuotJob> jobs;
   for (size_t k = 0; k < K; k++) {
-    const Fr* polys[4] = {items[k].poly, items[k].poly, dS[k], dS[k]};
     const size_t slen = fault_short_trim(ctx, (size_t)h_len[2 * k + 1]);
-    const size_t ns[4] = {items[k].n, items[k].n, Sn[k], Sn[k]};
-    const size_t lts[4] = {Lq[k], Lq[k], slen, slen};
-    const Fr xs[4] = {rs[k], rinv[k], rs[k], rinv[k]};
-    std::vector<const Fr*> qs;
-    std::vector<size_t> qns;
-    OpenCkOut ck;
-    if (check) ck.d_w = d_w + 4 * k, ck.h_w = h_w + 4 * k, ck.checked = checked.data() + 4 * k;
     const Open4 o4 = open4(outs[k]);
-    kzg_quotients_batch(ctx, srs, polys, ns, lts, xs, o4.o, qs, qns, h_y + 4 * k, ck, k);
-    qs_all.insert(qs_all.end(), qs.begin(), qs.end());
-    qns_all.insert(qns_all.end(), qns.begin(), qns.end());
+    jobs.push_back({items[k].poly, items[k].n, Lq[k], rs[k], o4.o[0]});
+    jobs.push_back({items[k].poly, items[k].n, Lq[k], rinv[k], o4.o[1]});
+    jobs.push_back({dS[k], Sn[k], slen, rs[k], o4.o[2]});
+    jobs.push_back({dS[k], Sn[k], slen, rinv[k], o4.o[3]});
   }
-  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs_all, qns_all);
+  const QuotStage st = quotients_queue(ctx, jobs, 4);
+  st.fit(srs);
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, st.qs, st.qns);
   ctx->sync();  // (drained already unless every quotient was empty)
-  if (check) {
-    open_batch_trim_scratch(ctx, K);  // (before a failure leaves the call)
-    open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + 4 * K), checked, 4, OPEN_QNAME);
-  }
-  for (size_t k = 0; k < K; k++) {
-    const Open4 o4 = open4(outs[k]);
-    for (int i = 0; i < 4; i++) {
-      fr_export(h_y[4 * k + i], o4.o[i]->y);
-      g1_export(pis[4 * k + i], o4.o[i]->proof_xy, &o4.o[i]->proof_inf);
-    }
-  }
-  open_batch_trim_scratch(ctx, K);
+  open_batch_trim_scratch(ctx, K);  // (before a failed check leaves the call)
+  st.settle(ctx, OPEN_QNAME);
+  st.store(pis);
 }
 
 // a single opening is a batch of one
@@ -2287,6 +2348,12 @@ struct OpenCall {
 static const char* const IPA_QNAME[6] = {"f at r", "f at 1/r", "g at r",
                                          "g at 1/r", "S at r", "S at 1/r"};
 
+// ipa.rs:94-100 on the six values y (IPA_QNAME order)
+static void ipa_check_equation(const Fr y[6], const Fr& r, const Fr& r_inv, const Fr& ip) {
+  QG_CHECK(y[0] * y[3] + y[1] * y[2] == r * y[4] + r_inv * y[5] + from_u64<FrP>(2) * ip,
+           QG_ERR_ASSERT, "Inner product verification equation failed");
+}
+
 static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_t nf,
                              const Fr* dg, size_t ng, uint8_t state[32], qg_ipa_proof* out) {
   const size_t M = nf > ng ? nf : ng;  // >= 1 (the caller's check)
@@ -2324,93 +2391,24 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
   const size_t Lf = fault_short_trim(ctx, (size_t)h_len[0]);
   const size_t Lg = fault_short_trim(ctx, (size_t)h_len[1]);
   const size_t Ls = fault_short_trim(ctx, (size_t)h_len[2]);
-  // transcript: inner_product, s_comm; draw r (ipa.rs:76-83)
-  uint8_t b32[32], b64[64];
-  fr_to_bytes(ip, b32);
-  transcript_append(state, b32, 32);
-  g1_serialize(s_comm, b64);
-  transcript_append(state, b64, 64);
-  const Fr r = transcript_draw_fr(state);
-  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-  const Fr r_inv = finv(r);
+  const OpenChallenge ch = ipa_transcript_step(state, ip, s_comm);
   fr_export(ip, out->inner_product);
   g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
-  // six KZG::open (ipa.rs:87-92): the quotients, then their commitments as one MSM batch
-  qg_kzg_opening* outs[6] = {&out->f_opening, &out->f_opening_inv, &out->g_opening,
-                             &out->g_opening_inv, &out->s_opening, &out->s_opening_inv};
+  // six KZG::open (ipa.rs:87-92): the quotients (job 2p + i: polynomial p of
+  // f, g, S at r, 1/r), then their commitments as one MSM batch
   const Fr* polys[3] = {df, dg, dS};
-  const size_t ns[3] = {nf, ng, Sn};
-  const size_t lts[3] = {Lf, Lg, Ls};
-  const Fr xs[2] = {r, r_inv};
-  Fr* s[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 6; i++) {
-    fr_export(xs[i & 1], outs[i]->x);
-    const size_t L = lts[i >> 1];
-    if (L == 0) continue;
-    QG_CHECK(L - 1 <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
-    s[i] = ctx->scratch_as<Fr>("ipa_s#" + std::to_string(i), L);
-  }
-  const char* pe = getenv("QG_IPA_PAIRED");
-  const bool paired = pe && atoi(pe) != 0;
-  {
-    QgTimed tm(ctx, "kzg_division");
-    if (paired) {
-      std::vector<ShIn<2>> jobs;
-      for (int p = 0; p < 3; p++)
-        if (lts[p]) jobs.push_back({polys[p], lts[p], {r, r_inv}, {s[2 * p], s[2 * p + 1]}});
-      suffix_horner<2>(ctx, jobs);
-    } else {
-      std::vector<ShIn<1>> jobs;
-      for (int i = 0; i < 6; i++)
-        if (s[i]) jobs.push_back({polys[i >> 1], lts[i >> 1], {xs[i & 1]}, {s[i]}});
-      suffix_horner_many(ctx, jobs);
-    }
-  }
+  const size_t ns[3] = {nf, ng, Sn}, lts[3] = {Lf, Lg, Ls};
+  const Open6 o6 = open6(*out);
+  std::vector<QuotJob> jobs;
   for (int i = 0; i < 6; i++)
-    if (s[i]) fault_quotient(ctx, s[i] + 1, lts[i >> 1] - 1);
-  Fr* d_y = ctx->scratch_as<Fr>("ipa_y", 6);
-  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("ipa_y_h", 6 * sizeof(Fr)));
-  QG_HIP(hipMemsetAsync(d_y, 0, 6 * sizeof(Fr), ctx->stream));
-  for (int i = 0; i < 6; i++)
-    if (s[i])
-      QG_HIP(hipMemcpyAsync(d_y + i, s[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-  QG_HIP(hipMemcpyAsync(h_y, d_y, 6 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  // every quotient through kzg.rs:85's check, as two groups of open_check_queue:
-  // (f, g) at r and 1/r, then S at r and 1/r
-  const bool check = open_check_on();
-  std::vector<uint8_t> checked(6, CK_NONE);
-  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("ipa_ck_h", 8 * sizeof(uint32_t)));
-  if (check) {
-    uint32_t* d_w = ctx->scratch_as<uint32_t>("ipa_ck_w", 8);
-    OpenCk c8[8] = {};
-    for (int i = 0; i < 6; i++) {
-      const size_t n = ns[i >> 1];
-      c8[i] = {n ? polys[i >> 1] : nullptr, n, s[i] ? s[i] + 1 : nullptr,
-               s[i] ? lts[i >> 1] - 1 : 0, d_y + i, xs[i & 1]};
-      checked[i] = s[i] ? CK_QUOT : n ? CK_ZERO : CK_NONE;
-    }
-    open_check_queue(ctx, c8, d_w);
-    open_check_queue(ctx, c8 + 4, d_w + 4);
-    QG_HIP(hipMemcpyAsync(h_w, d_w, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  std::vector<const Fr*> qs;
-  std::vector<size_t> qns;
-  for (int i = 0; i < 6; i++) {
-    qs.push_back(s[i] ? s[i] + 1 : nullptr);
-    qns.push_back(s[i] ? lts[i >> 1] - 1 : 0);
-  }
-  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
+    jobs.push_back({polys[i >> 1], ns[i >> 1], lts[i >> 1], i & 1 ? ch.r_inv : ch.r, o6.o[i]});
+  const QuotStage st = quotients_queue(ctx, jobs, 6, true);
+  st.fit(srs);
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, st.qs, st.qns);
   ctx->sync();  // (drained already unless every quotient was empty)
-  if (check) open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + 6), checked, 6, IPA_QNAME);
-  Fr y[6];
-  for (int i = 0; i < 6; i++) {
-    y[i] = h_y[i];
-    fr_export(y[i], outs[i]->y);
-    g1_export(pis[i], outs[i]->proof_xy, &outs[i]->proof_inf);
-  }
-  // ipa.rs:94-100
-  QG_CHECK(y[0] * y[3] + y[1] * y[2] == r * y[4] + r_inv * y[5] + from_u64<FrP>(2) * ip,
-           QG_ERR_ASSERT, "Inner product verification equation failed");
+  st.settle(ctx, IPA_QNAME);
+  st.store(pis);
+  ipa_check_equation(st.h_y, ch.r, ch.r_inv, ip);
 }
 
 // The local geometry of a sharded inner-product argument, decided from this
@@ -2442,10 +2440,11 @@ static size_t ipa_sharded_geometry(qg_ctx* ctx, size_t nf, size_t ng) {
 //      rank then knows every rank's part lengths and bases - the "Polynomial
 //      degree exceeds max degree" decision, the same on all ranks;
 //   4. the S commitment (sharded MSM), the transcript step on every rank;
-//   5. six local suffix-Horner scans (QG_IPA_PAIRED=1: three paired ones),
-//      ONE allgather of their slice-end values T, the carries;
-//   6. the quotient check on the ranks' summed parts (ONE allgather) and the
-//      six commitments as ONE sharded MSM batch; ipa.rs:94-100.
+//   5. quotients_sharded on six jobs: the local suffix-Horner scans
+//      (QG_IPA_PAIRED=1: three paired ones), ONE allgather of their slice-end
+//      values T, the carries, the quotient check on the ranks' summed parts
+//      (ONE allgather) and the six commitments as ONE sharded MSM batch;
+//   6. ipa.rs:94-100.
 // Every decision that ends the call is taken on gathered values, which all
 // ranks hold alike, so no rank leaves between two collectives its peers enter.
 // The scratch is the flow's own and s_poly_sharded's (sp_*): no transform the
@@ -2455,7 +2454,7 @@ static size_t ipa_sharded_geometry(qg_ctx* ctx, size_t nf, size_t ng) {
 static void ipa_prove_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* df, const Fr* dg, size_t L,
                               size_t nvars, uint8_t state[32], qg_ipa_proof* out) {
   const size_t W = (size_t)ctx->world, rank = (size_t)ctx->rank;
-  const size_t M = W * L, off = rank * L;
+  const size_t M = W * L;
   struct Small {
     Fr part;
     unsigned long long len[3], srs_n;
@@ -2491,141 +2490,31 @@ static void ipa_prove_sharded(qg_ctx* ctx, const qg_srs* srs, const Fr* df, cons
   QG_HIP(hipMemcpyAsync(all.data(), d_all, W * sizeof(Small), hipMemcpyDeviceToHost, ctx->stream));
   ctx->sync();
   Fr ip = Fr::zero();
-  size_t glt[3] = {0, 0, 0};  // global trimmed lengths of f, g, S
+  size_t glt[3];  // global trimmed lengths of f, g, S
+  std::vector<unsigned long long> shard(W), loc(W);
   for (size_t r = 0; r < W; r++) {
     ip = ip + all[r].part;
-    // the largest (rank offset + local length) of a nonzero slice
-    for (int p = 0; p < 3; p++)
-      if (all[r].len[p]) glt[p] = std::max(glt[p], r * L + (size_t)all[r].len[p]);
+    shard[r] = all[r].srs_n;
   }
-  // rank r's live part of a polynomial of global length n, and of its quotient
-  auto live = [&](size_t n, size_t r) { return n > r * L ? std::min(L, n - r * L) : (size_t)0; };
-  auto qlive = [&](size_t n, size_t r) { return n ? live(n - 1, r) : (size_t)0; };
-  for (size_t r = 0; r < W; r++) {
-    bool fits = live(glt[2], r) <= all[r].srs_n;
-    for (int p = 0; p < 3; p++) fits = fits && qlive(glt[p], r) <= all[r].srs_n;
-    QG_CHECK(fits, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+  for (int p = 0; p < 3; p++) {
+    for (size_t r = 0; r < W; r++) loc[r] = all[r].len[p];
+    glt[p] = op_global_len(loc.data(), W, L);
   }
-  const G1Affine s_comm = msm_device_batch(ctx, srs, {Sl}, {live(glt[2], rank)})[0];
-  // transcript: inner_product, s_comm; draw r (ipa.rs:76-83), on every rank alike
-  uint8_t b32[32], b64[64];
-  fr_to_bytes(ip, b32);
-  transcript_append(state, b32, 32);
-  g1_serialize(s_comm, b64);
-  transcript_append(state, b64, 64);
-  const Fr r = transcript_draw_fr(state);
-  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
-  const Fr r_inv = finv(r);
+  QG_CHECK(op_fits(glt[2], glt, 3, L, shard.data(), W), QG_ERR_INVALID,
+           "Polynomial degree exceeds max degree");
+  const G1Affine s_comm = msm_device_batch(ctx, srs, {Sl}, {op_live(glt[2], rank, L)})[0];
+  // the transcript step on every rank alike, then the six quotients (job
+  // 2p + i: polynomial p of f, g, S at r, 1/r) and ipa.rs:94-100
+  const OpenChallenge ch = ipa_transcript_step(state, ip, s_comm);
   fr_export(ip, out->inner_product);
   g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
-  // the six quotients' local scans: job i = 2 p + (point), this rank's le[p]
-  // live coefficients of polynomial p into sq[i][0 .. le); T_i = sq[i][0]
-  qg_kzg_opening* outs[6] = {&out->f_opening, &out->f_opening_inv, &out->g_opening,
-                             &out->g_opening_inv, &out->s_opening, &out->s_opening_inv};
   const Fr* polys[3] = {df, dg, Sl};
-  const Fr xs[2] = {r, r_inv};
-  size_t le[3];
-  Fr* sq[6];
-  for (int i = 0; i < 6; i++) {
-    le[i >> 1] = live(glt[i >> 1], rank);
-    sq[i] = ctx->scratch_as<Fr>("ipas_s#" + std::to_string(i), le[i >> 1] + 1);
-  }
-  const char* pe = getenv("QG_IPA_PAIRED");
-  const bool paired = pe && atoi(pe) != 0;
-  {
-    QgTimed tm(ctx, "kzg_division");
-    if (paired) {
-      std::vector<ShIn<2>> jobs;
-      for (int p = 0; p < 3; p++)
-        if (le[p]) jobs.push_back({polys[p], le[p], {r, r_inv}, {sq[2 * p], sq[2 * p + 1]}});
-      suffix_horner<2>(ctx, jobs);
-    } else {
-      std::vector<ShIn<1>> jobs;
-      for (int i = 0; i < 6; i++)
-        if (le[i >> 1]) jobs.push_back({polys[i >> 1], le[i >> 1], {xs[i & 1]}, {sq[i]}});
-      suffix_horner_many(ctx, jobs);
-    }
-  }
-  Fr* d_T = ctx->scratch_as<Fr>("ipas_T", 6);
-  QG_HIP(hipMemsetAsync(d_T, 0, 6 * sizeof(Fr), ctx->stream));
+  const Open6 o6 = open6(*out);
+  std::vector<ShardQuotJob> jobs;
   for (int i = 0; i < 6; i++)
-    if (le[i >> 1])
-      QG_HIP(hipMemcpyAsync(d_T + i, sq[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-  // exchange 2: every rank's T values
-  Fr* d_Tall = ctx->scratch_as<Fr>("ipas_T_all", 6 * W);
-  comm_allgather_bytes(ctx, d_T, d_Tall, 6 * sizeof(Fr));
-  std::vector<Fr> Tall(6 * W);
-  QG_HIP(hipMemcpyAsync(Tall.data(), d_Tall, 6 * W * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-  ctx->sync();
-  // C_rank = sum_{r' > rank} T_r' x^((r' - rank - 1) L);  y = sum_r' T_r' x^(r' L)
-  Fr y[6];
-  Fr* pw = ctx->scratch_as<Fr>("open_pw", L + 1);
-  std::vector<const Fr*> qs(6);
-  std::vector<size_t> qn(6);
-  for (int i = 0; i < 6; i++) {
-    const size_t n = le[i >> 1];
-    const Fr x = xs[i & 1], xL = fpow_small(x, L);
-    Fr Cc = Fr::zero(), yy = Fr::zero();
-    for (size_t rr = W; rr-- > 0;) {
-      if (rr == rank) Cc = yy;
-      yy = Tall[rr * 6 + i] + xL * yy;
-    }
-    y[i] = yy;
-    if (n > 0) {
-      QgTimed tm(ctx, "kzg_division");
-      const int KP = 64;
-      hipLaunchKernelGGL(k_powers_ml, dim3(div_up(div_up(n + 1, (size_t)KP), ML_BLOCK)),
-                         dim3(ML_BLOCK), 0, ctx->stream, x, n + 1, KP, pw);
-      QG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_sh_carry, dim3(div_up(n + 1, ML_BLOCK)), dim3(ML_BLOCK), 0, ctx->stream,
-                         sq[i], n, pw, Cc);
-      QG_LAUNCH_CHECK();
-    }
-    // q_k = s_{k+1} for global k < glt - 1; this rank's part starts at s + 1
-    qn[i] = qlive(glt[i >> 1], rank);
-    qs[i] = sq[i] + 1;
-    fault_quotient(ctx, sq[i] + 1, qn[i]);
-  }
-  // kzg.rs:85 on the ranks' summed parts: f(sigma), g(sigma), S(sigma) over the
-  // untrimmed local blocks and the six q(sigma)
-  const bool check = open_check_on();
-  Fr* d_ev = check ? ctx->scratch_as<Fr>("ipas_ck_ev", 9) : nullptr;
-  if (check) {
-    QgTimed tm(ctx, "kzg_open_check");
-    std::vector<EvIn> in;
-    for (int p = 0; p < 3; p++) in.push_back({polys[p], L, (uint64_t)off});
-    for (int i = 0; i < 6; i++) in.push_back({qs[i], qn[i], (uint64_t)off});
-    poly_eval_queue(ctx, in, ctx->open_sigma, d_ev);
-  }
-  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qn);
-  if (check) {
-    Fr* d_evall = ctx->scratch_as<Fr>("ipas_ck_ev_all", 9 * W);
-    comm_allgather_bytes(ctx, d_ev, d_evall, 9 * sizeof(Fr));
-    std::vector<Fr> ev(9 * W);
-    QG_HIP(hipMemcpyAsync(ev.data(), d_evall, ev.size() * sizeof(Fr), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    ctx->sync();
-    std::vector<uint32_t> bad(6, 0);
-    std::vector<uint8_t> checked(6, 0);
-    for (int i = 0; i < 6; i++) {
-      Fr P = Fr::zero(), Q = Fr::zero();
-      for (size_t rr = 0; rr < W; rr++) {
-        P = P + ev[9 * rr + (i >> 1)];
-        Q = Q + ev[9 * rr + 3 + i];
-      }
-      checked[i] = glt[i >> 1] ? CK_QUOT : CK_ZERO;
-      bad[i] = open_check_host(P, y[i], Q, ctx->open_sigma, xs[i & 1]);
-    }
-    open_check_settle(ctx, bad, checked, 6, IPA_QNAME);
-  }
-  for (int i = 0; i < 6; i++) {
-    fr_export(xs[i & 1], outs[i]->x);
-    fr_export(y[i], outs[i]->y);
-    g1_export(pis[i], outs[i]->proof_xy, &outs[i]->proof_inf);
-  }
-  // ipa.rs:94-100
-  QG_CHECK(y[0] * y[3] + y[1] * y[2] == r * y[4] + r_inv * y[5] + from_u64<FrP>(2) * ip,
-           QG_ERR_ASSERT, "Inner product verification equation failed");
+    jobs.push_back({polys[i >> 1], L, glt[i >> 1], i & 1 ? ch.r_inv : ch.r, o6.o[i]});
+  const std::vector<Fr> y = quotients_sharded(ctx, srs, jobs, 6, true, IPA_QNAME);
+  ipa_check_equation(y.data(), ch.r, ch.r_inv, ip);
 }
 
 }  // namespace qg

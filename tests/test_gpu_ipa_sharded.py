@@ -287,6 +287,58 @@ def test_shard_too_short_fails_every_rank(short):
         assert res[0] == -1 and "Polynomial degree exceeds max degree" in res[1]
 
 
+# ---------------------------------------------------------------- shared quotient stage
+@pytest.mark.parametrize("order", ["openings first", "ipa first"])
+def test_ml_openings_and_ipa_on_the_same_contexts(order):
+    """a sharded ML opening batch of two items (world 4, nv = 6) and a sharded
+    inner-product argument (L = 16) on the same contexts, in both orders: each
+    equals its single-context counterpart, so the quotient stage's scratch
+    slots, which both protocols use, carry nothing from one into the other"""
+    import random
+    import quill_amd as q
+    world, nv, L = 4, 6, 16
+    N = 1 << nv
+    rnd = random.Random(910)
+    polys = [[rnd.randrange(o.R_MOD) for _ in range(N)],
+             [rnd.randrange(o.R_MOD) for _ in range(40)] + [0] * (N - 40)]
+    pts = [[rnd.randrange(o.R_MOD) for _ in range(nv)] for _ in polys]
+    f, g = vec(N, 911, live=N - 5), vec(N, 912)
+    dev0 = q.Device(0)
+    kz = q.KZG.trusted_setup(N, TAU, dev0)
+    vs = [q.DeviceVec.from_list(dev0, p) for p in polys]
+    t_ref = q.Transcript(DOMAIN)
+    want_open = (kz.open_batch_dev([(v, N, pt, False) for v, pt in zip(vs, pts)], t_ref),
+                 t_ref.state)
+    for x in vs + [kz]:
+        x.close()
+    dev0.close()
+    want_ipa = single("shared-stage", f, g)
+
+    def fn(dev, rank, world):
+        kzg = q.KZG.trusted_setup(N - 1, TAU, dev)
+        vecs = [q.DeviceVec.from_list(dev, p[rank * L:(rank + 1) * L]) for p in polys]
+        df = q.DeviceVec.from_list(dev, f[rank * L:(rank + 1) * L])
+        dg = q.DeviceVec.from_list(dev, g[rank * L:(rank + 1) * L])
+
+        def openings():
+            t = q.Transcript(DOMAIN)
+            return kzg.open_batch_dev([(v, L, pt, False) for v, pt in zip(vecs, pts)], t), t.state
+
+        def argument():
+            t = q.Transcript(DOMAIN)
+            return q.InnerProductProof.prove(df, dg, kzg, t), t.state
+        if order == "openings first":
+            res = (openings(), argument())
+        else:
+            res = tuple(reversed((argument(), openings())))
+        for x in vecs + [df, dg, kzg]:
+            x.close()
+        return res
+    for got_open, got_ipa in run_ranks(world, fn):
+        assert got_open == want_open
+        assert got_ipa == want_ipa
+
+
 # ---------------------------------------------------------------- Python mirror, verifier
 def test_verifier_accepts_a_sharded_proof():
     """W = 8, L = 2^12 through InnerProductProof.prove(DeviceVec, DeviceVec, kzg, t)

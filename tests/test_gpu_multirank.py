@@ -437,3 +437,44 @@ def test_sharded_mle_open_batch_matches_sequential(world):
     for (bat, sb), (seq, ss) in outs:
         assert bat == seq and sb == ss
         assert bat == ref and sb == t_ref.state
+
+
+@pytest.mark.parametrize("short", ["every rank", "rank 1 only"])
+def test_sharded_mle_open_shard_too_short(short):
+    """world 2, nv = 5: 16 local coefficients (nonzero top coefficient) against
+    an SRS shard of 8 bases: -1 "Polynomial degree exceeds max degree" - on
+    every rank, also when only rank 1's shard is short (the shard sizes travel
+    with the local lengths in exchange 1), and no rank is left in a collective"""
+    import ctypes as C
+    import quill_amd as q
+    from quill_amd._lib import MleProof, QuillGpuError, check, lib
+    from quill_amd.field import fr_array, u64p
+    rnd = random.Random(4242)
+    world, nv = 2, 5
+    N = 1 << nv
+    L = N // world
+    tau = rnd.randrange(R)
+    poly = [rnd.randrange(R) for _ in range(N - 1)] + [rnd.randrange(1, R)]
+    point = fr_array([rnd.randrange(R) for _ in range(nv)])
+
+    def fn(dev, rank, world):
+        nb = 8 if (short == "every rank" or rank == 1) else L
+        srs = q.Srs.generate(dev, tau, nb, offset=rank * L)
+        vec = q.DeviceVec.from_list(dev, poly[rank * L:(rank + 1) * L])
+        t = q.Transcript(b"shard-short")
+        out = MleProof()
+        try:
+            check(lib().qg_mle_open_dev_ex(dev.h, srs.h, vec.h, L, u64p(point), nv, t.c_state(),
+                                           0, C.byref(out)), dev.h)
+            res = ("opened",)
+        except QuillGpuError as e:
+            res = (e.code, str(e))
+        vec.close()
+        srs.close()
+        return res
+    before = threading.active_count()
+    out = run_ranks(world, fn)
+    assert threading.active_count() == before  # no rank is stuck in a collective
+    for res in out:
+        assert len(res) == 2, res
+        assert res[0] == -1 and "Polynomial degree exceeds max degree" in res[1]
