@@ -321,6 +321,70 @@ typedef struct qg_mle_open_item {
 int qg_mle_open_batch_dev(qg_ctx* ctx, const qg_srs* srs, const qg_mle_open_item* items,
                           size_t k, uint8_t state[32], qg_mle_proof* outs);
 
+/* ---- folded ML opening (opt-in; no counterpart in the reference).
+ * An MLEvalProof opens two polynomials, f and S, each at r and 1/r.  Two
+ * polynomials opened at the same point need one quotient: with gamma drawn
+ * after the four values, (h - h(x))/(X - x) for h = f + gamma S is one KZG
+ * claim against C_f + gamma s_comm (the same-point batching of GWC / PLONK;
+ * needs g2 and tau g2 only).  Per opening 3 MSMs instead of 5, 2 KZG claims
+ * instead of 4, 2 quotient vectors instead of 4, and a smaller proof.
+ * Prover: as MLEvalProof::prove up to r (append point, evaluation, s_comm;
+ * draw r; assert r != 0); y = (f(r), f(1/r), S(r), S(1/r)) over the untrimmed
+ * vectors, appended as four Fr in that order; draw gamma (not redrawn when 0);
+ * nothing further is absorbed.  h = f + gamma S over L_h = max(trimmed length
+ * of f, of S) coefficients; w = commit((h - h(r))/(X - r)), w_inv the same at
+ * 1/r, each over L_h - 1 coefficients (L_h = 0: both the identity, all y 0).
+ * The proof carries no opening x and no folded y: the verifier derives both. */
+typedef struct qg_mle_proof_folded {
+  uint64_t evaluation[4];
+  uint64_t s_comm_xy[8];
+  uint8_t s_comm_inf;
+  uint8_t _pad[7];
+  uint64_t y[4][4]; /* poly at r, poly at 1/r, S at r, S at 1/r */
+  uint64_t w_xy[8];
+  uint8_t w_inf;
+  uint8_t _pad1[7];
+  uint64_t w_inv_xy[8];
+  uint8_t w_inv_inf;
+  uint8_t _pad2[7];
+} qg_mle_proof_folded;
+/* The folded form of qg_mle_open_dev_ex (flags: QG_OPEN_UNCHANGED or 0) and of
+ * qg_mle_open_batch_dev (k <= 256; item k exactly as the k-th of k successive
+ * single calls: same proofs, same final `state`).  The K S commitments are one
+ * MSM batch and the 2K quotient commitments another; between them each item
+ * costs one host round trip (gamma_k needs item k's four values, item k + 1's
+ * r needs gamma_k's transcript state; timed region "fold_eval").  The two
+ * quotients of an item come from the plain two-point scan over h in scratch
+ * (qg_lincomb_dev's kernel), or with QG_FOLD_FUSED=1 (read per call; 0 or unset:
+ * the former) from one scan that forms the coefficients of h on the fly and
+ * never writes h; identical proofs, and the former measured faster (DESIGN
+ * section 5).  Both are checked like every opening's
+ * ("open_checks" rises by 2 per opening): at the context's sigma,
+ * f(sigma) + gamma S(sigma) - (y_f + gamma y_S) == q(sigma)(sigma - x), and the
+ * scan's own h(x) equals y_f + gamma y_S; a failure is QG_ERR_ASSERT
+ * "Polynomial division failed: opening i of K, quotient j (folded at r)" or
+ * "(folded at 1/r)".  QG_ERR_INVALID: null handles, a length beyond the
+ * buffer, nvars > 30, unknown flags, L_h - 1 beyond the SRS ("Polynomial degree
+ * exceeds max degree").  QG_ERR_UNSUPPORTED: a context with a communicator
+ * attached ("sharded" in qg_last_error), before any device work or collective. */
+int qg_mle_open_folded_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_t n,
+                           const uint64_t* point, size_t nvars, uint8_t state[32], uint32_t flags,
+                           qg_mle_proof_folded* out);
+int qg_mle_open_folded_batch_dev(qg_ctx* ctx, const qg_srs* srs, const qg_mle_open_item* items,
+                                 size_t k, uint8_t state[32], qg_mle_proof_folded* outs);
+/* The building block, for tests and for callers that batch their own
+ * protocol: KZG::open of sum_j coeffs[j] polys[j] (the first lens[j] entries
+ * of polys[j]; a shorter one counts as zero-padded; coeffs: P Fr on the host)
+ * at the nx points xs, through the folded opening's scan (QG_FOLD_FUSED as
+ * above) and with the quotient check;
+ * outs[i] = (xs[i], value, proof), the same bits as qg_kzg_open of the
+ * materialised combination.  Limits: 1 <= P <= 4, nx 1 or 2; anything else,
+ * null pointers and a length beyond its buffer included, is QG_ERR_INVALID.
+ * QG_ERR_UNSUPPORTED on a context with a communicator attached. */
+int qg_kzg_open_lincomb_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* const* polys,
+                            const size_t* lens, const uint64_t* coeffs, size_t P,
+                            const uint64_t* xs, size_t nx, qg_kzg_opening* outs);
+
 /* ---------------------------------------------------------------- inner-product argument */
 /* InnerProductProof (pcs/src/ipa.rs:40-53), fields in the reference's order. */
 typedef struct qg_ipa_proof {
@@ -499,6 +563,23 @@ int qg_mle_verify_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t 
 int qg_ipa_verify_defer(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
                         const uint64_t comm2_xy[8], uint8_t comm2_inf, const qg_ipa_proof* proof,
                         uint8_t state[32], qg_kzg_claim out[6], int* ok);
+/* The folded opening's verifier (host, no context): replays the transcript as
+ * qg_mle_verify does (point, evaluation, s_comm; draw r; r = 0 is
+ * QG_ERR_ASSERT), appends the proof's four y, draws gamma, checks the
+ * inner-product equation (mlpcs.rs:155-160) on the four y, forms
+ * C_h = comm + gamma s_comm (qg_g1_lincomb's host code) and checks the two KZG
+ * claims (C_h, r, y[0] + gamma y[2], w) and (C_h, 1/r, y[1] + gamma y[3], w_inv).
+ * Every proof point must be on the curve (QG_ERR_INVALID).  `state` ends as the
+ * prover's.  The _defer form skips the two pairing checks and hands the two
+ * claims out for qg_kzg_verify_batch; *ok then reports the equation, and
+ * `state` always advances. */
+int qg_mle_verify_folded(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                         const uint64_t* point, size_t nvars, const qg_mle_proof_folded* proof,
+                         uint8_t state[32], int* ok);
+int qg_mle_verify_folded_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                               const uint64_t* point, size_t nvars,
+                               const qg_mle_proof_folded* proof, uint8_t state[32],
+                               qg_kzg_claim out[2], int* ok);
 
 /* Building blocks of the opening, exposed for testing and for callers that
  * batch their own protocol:

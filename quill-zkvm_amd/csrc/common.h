@@ -353,6 +353,9 @@ Fr fr_import(const uint64_t v[4]);
 void fr_export(const Fr& a, uint64_t v[4]);
 // eq(bin(i), z) table on the device (sumcheck.hip)
 void eq_table_device(qg_ctx* ctx, const Fr* d_z, uint32_t nvars, Fr* d_out);
+// out[x] = sum_j coeffs[j] src[j][x], x < n, queued (multiopen.hip; 1 <= P <= 16)
+void lincomb_queue(qg_ctx* ctx, const Fr* const* src, const Fr* coeffs, size_t P, size_t n,
+                   Fr* out);
 // h(x) per row by the generic expression interpreter (sumcheck.hip)
 void expr_table_device(qg_ctx* ctx, size_t n, uint32_t ntables, const std::vector<const Fr*>& tabs,
                        const qg_expr_op* prog, size_t prog_len, const uint64_t* consts,

@@ -310,6 +310,186 @@ static void suffix_horner_many(qg_ctx* ctx, const std::vector<ShIn<1>>& in, int 
         depth);
 }
 
+// ---- the folded scan: ONE polynomial h = sum_j g_j p_j of up to SHF_P source
+// vectors, never materialised, at NP points.  The coefficient of every Horner
+// step is formed on the fly, c_i = sum_j g_j p_j[i] (a source shorter than i
+// contributes 0; g_0 = 1 skips its product), so one pass reads each source
+// once and writes NP suffix vectors.  Same blocking as above; the chunk values
+// A and carries T are plain vectors, so the levels above are the NP = 1 jobs.
+// g_j arrives as g_j 2^261 (plain limbs, x261_of), so mul29 keeps the arkworks
+// scale of the sources.
+// Bounds: a term is a canonical source value (< p, g_0 = 1) or a product
+// (< 2p, normalized); the lazy sum of P <= 4 of them is < 8p with limbs < 2^31.
+// P = 2: < 4p, red2p29's range; P > 2: red16p29.  Either way the folded
+// coefficient is normalized and < 2p, so each step c_i + x s_{i+1} is
+// < 2p + 2p = 4p before red2p29 (sh_step's own bound is p + 2p) and s stays
+// < 2p.  Stored values are canonical, so the bits equal those of the scan
+// over a materialised canonical h (k_lincomb, then suffix_horner<NP>).
+static constexpr int SHF_P = 4;
+struct ShFoldSrc {
+  const Fr* c[SHF_P];
+  size_t n[SHF_P];  // coefficients of source j (0 past them)
+  L9 g[SHF_P];      // g_j 2^261 mod p
+  int P;
+  int one0;         // g_0 == 1: source 0 enters unmultiplied
+};
+template <int NP>
+struct ShFoldJob {
+  ShFoldSrc src;
+  size_t L;         // scan length (>= every n[j])
+  L9 x[NP];
+  Fr* A[NP];
+  const Fr* T[NP];
+  size_t nch;
+  Fr* s[NP];
+};
+
+__device__ __forceinline__ F29<FrP> shf_coef(const ShFoldSrc& S, size_t i) {
+  F29<FrP> c = F29<FrP>::zero();
+  if (i < S.n[0]) {
+    c = to29(S.c[0][i]);
+    if (!S.one0) c = mul29(F29<FrP>::from_l9(S.g[0]), c);
+  }
+#pragma unroll
+  for (int j = 1; j < SHF_P; j++)
+    if (j < S.P && i < S.n[j]) c = add29(c, mul29(F29<FrP>::from_l9(S.g[j]), to29(S.c[j][i])));
+  return S.P <= 2 ? red2p29(c) : red16p29(c);
+}
+
+template <int NP>
+__global__ void __launch_bounds__(ML_BLOCK) k_shf_local(ShFoldJob<NP> J) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t s = k * SH_B;
+  if (s >= J.L) return;
+  const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
+  F29<FrP> x[NP], acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) x[p] = F29<FrP>::from_l9(J.x[p]), acc[p] = F29<FrP>::zero();
+#pragma unroll 2
+  for (size_t i = e; i-- > s;) sh_step<NP>(shf_coef(J.src, i), x, acc);
+#pragma unroll
+  for (int p = 0; p < NP; p++) J.A[p][k] = from29(canon29(acc[p]));
+}
+
+template <int NP>
+__global__ void __launch_bounds__(ML_BLOCK) k_shf_apply(ShFoldJob<NP> J) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t s = k * SH_B;
+  if (s >= J.L) return;
+  const size_t e = s + SH_B < J.L ? s + SH_B : J.L;
+  const bool carry = k + 1 < J.nch;
+  F29<FrP> x[NP], acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) {
+    x[p] = F29<FrP>::from_l9(J.x[p]);
+    acc[p] = carry ? to29(J.T[p][k + 1]) : F29<FrP>::zero();
+  }
+  Fr* __restrict__ out0 = J.s[0];
+  Fr* __restrict__ out1 = J.s[NP - 1];
+#pragma unroll 2
+  for (size_t i = e; i-- > s;) {
+    sh_step<NP>(shf_coef(J.src, i), x, acc);
+    out0[i] = from29(canon29(acc[0]));
+    if constexpr (NP == 2) out1[i] = from29(canon29(acc[1]));
+  }
+}
+
+// small case: one thread
+template <int NP>
+__global__ void k_shf_serial(ShFoldJob<NP> J) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  F29<FrP> x[NP], acc[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) x[p] = F29<FrP>::from_l9(J.x[p]), acc[p] = F29<FrP>::zero();
+  for (size_t i = J.L; i-- > 0;) {
+    sh_step<NP>(shf_coef(J.src, i), x, acc);
+#pragma unroll
+    for (int p = 0; p < NP; p++) J.s[p][i] = from29(canon29(acc[p]));
+  }
+}
+
+// h = sum_j g[j] c[j] (P sources of n[j] coefficients, g Montgomery) scanned
+// over its first L coefficients at NP points: s[p][i] for i < L.
+template <int NP>
+struct ShFoldIn {
+  const Fr* c[SHF_P];
+  size_t n[SHF_P];
+  Fr g[SHF_P];
+  int P;
+  size_t L;
+  Fr x[NP];
+  Fr* s[NP];
+};
+
+// Two routes, the same bits either way: the fused scan above, or the unfused
+// composition - h into scratch by k_lincomb, then suffix_horner<NP>.
+// QG_FOLD_FUSED (read per call) selects: 1 the fused scan, 0 the composition.
+// Unset is the composition: measured at 2^22 entries (profiles/fold_open.json,
+// DESIGN section 5 "Folded opening") the fused scan's region is 0.653 ms
+// against 0.642 ms, beyond the spread of the repeated medians (0.009 ms; an
+// earlier visit on another box: 0.642 against 0.618) - its two strided source
+// reads per pass cost more than the coalesced k_lincomb pass and the 256 MB
+// it writes and reads back.
+template <int NP>
+static void suffix_horner_fold(qg_ctx* ctx, const ShFoldIn<NP>& in) {
+  static_assert(NP == 1 || NP == 2, "one or two points");
+  if (in.L == 0) return;
+  QG_CHECK(in.P >= 1 && in.P <= SHF_P, QG_ERR_ASSERT, "folded scan of one to four sources");
+  const char* fe = getenv("QG_FOLD_FUSED");
+  if (!(fe && atoi(fe) != 0)) {
+    // h over [0, L): between two consecutive source lengths the live sources
+    // are a fixed subset, one k_lincomb launch each (a source never read past
+    // its end); a stretch with no live source is 0
+    Fr* h = ctx->scratch_as<Fr>("fold_h", in.L);
+    size_t a = 0;
+    while (a < in.L) {
+      size_t b = in.L;
+      const Fr* src[SHF_P];
+      Fr g[SHF_P];
+      size_t m = 0;
+      for (int j = 0; j < in.P; j++) {
+        const size_t nj = std::min(in.n[j], in.L);
+        if (nj > a) src[m] = in.c[j] + a, g[m] = in.g[j], m++, b = std::min(b, nj);
+      }
+      if (m) lincomb_queue(ctx, src, g, m, b - a, h + a);
+      else QG_HIP(hipMemsetAsync(h + a, 0, (b - a) * sizeof(Fr), ctx->stream));
+      a = b;
+    }
+    ShIn<NP> one{h, in.L, {}, {}};
+    for (int p = 0; p < NP; p++) one.x[p] = in.x[p], one.s[p] = in.s[p];
+    return suffix_horner<NP>(ctx, {one});
+  }
+  ShFoldJob<NP> j{};
+  j.src.P = in.P;
+  j.src.one0 = in.g[0] == Fr::one() ? 1 : 0;
+  for (int q = 0; q < in.P; q++) {
+    j.src.c[q] = in.c[q], j.src.n[q] = std::min(in.n[q], in.L);
+    j.src.g[q] = x261_of(in.g[q]);
+  }
+  j.L = in.L;
+  for (int p = 0; p < NP; p++) j.x[p] = x261_of(in.x[p]), j.s[p] = in.s[p];
+  if (in.L <= (size_t)SH_B) {
+    hipLaunchKernelGGL(k_shf_serial<NP>, dim3(1), dim3(64), 0, ctx->stream, j);
+    QG_LAUNCH_CHECK();
+    return;
+  }
+  const size_t nch = (in.L + SH_B - 1) / SH_B;
+  j.nch = nch;
+  std::vector<ShIn<1>> up;
+  for (int p = 0; p < NP; p++) {  // the chunk slots of suffix_horner's job 0
+    Fr* A = ctx->scratch_as<Fr>("sh_A0_" + std::to_string(p), nch);
+    Fr* T = ctx->scratch_as<Fr>("sh_T0_" + std::to_string(p), nch);
+    j.A[p] = A, j.T[p] = T;
+    up.push_back({A, nch, {fpow_small(in.x[p], SH_B)}, {T}});
+  }
+  const dim3 grid((unsigned)div_up(nch, ML_BLOCK));
+  hipLaunchKernelGGL(k_shf_local<NP>, grid, dim3(ML_BLOCK), 0, ctx->stream, j);
+  QG_LAUNCH_CHECK();
+  suffix_horner_many(ctx, up, 1);
+  hipLaunchKernelGGL(k_shf_apply<NP>, grid, dim3(ML_BLOCK), 0, ctx->stream, j);
+  QG_LAUNCH_CHECK();
+}
+
 
 // ---------------------------------------------------------------- polynomial evaluation
 // DensePolynomial::evaluate (kzg.rs:78) as a reduction: sum_i c_i x^i of up to
@@ -2173,19 +2353,27 @@ static void mle_open_batch_sharded(qg_ctx* ctx, const qg_srs* srs,
 // after those synchronizations.  Inside a batch the bucketing of MSM i + 1
 // runs on the side stream beside MSM i's accumulation, and the batch pays one
 // set of reduction launches and one host round trip (msm.hip).  A sharded
-// context runs mle_open_batch_sharded.
-static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
-                                  const std::vector<MleOpenItem>& items, uint8_t state[32],
-                                  qg_mle_proof* outs) {
+// context runs mle_open_batch_sharded.  Steps 1 and 2 (open_batch_front) and
+// the per-item part of step 3 (open_batch_item_step) are shared with the
+// folded opening below.
+
+// What steps 1 and 2 leave, read back after their one synchronization.
+struct OpenFront {
+  const unsigned long long* h_len = nullptr;  // [2k]: the vector's, [2k + 1]: S's
+  const Fr* h_eval = nullptr;
+  std::string memo_in;
+  std::vector<std::string> lt_key;
+  std::vector<char> lt_known;
+  std::vector<Fr*> dS;
+  std::vector<size_t> Sn;
+  std::vector<G1Affine> s_comm;
+  std::vector<size_t> Lt, Lq;  // Lq: the length the quotients use (Lt unless faulted)
+};
+
+static OpenFront open_batch_front(qg_ctx* ctx, const qg_srs* srs,
+                                  const std::vector<MleOpenItem>& items) {
   const size_t K = items.size();
-  if (K == 0) return;
-  if (ctx->sharded) {
-    // QG_OPEN_BATCH_SHARDED=0: a sharded context opens item by item (A/B runs)
-    const char* sb = getenv("QG_OPEN_BATCH_SHARDED");
-    if (!(sb && atoi(sb) == 0)) return mle_open_batch_sharded(ctx, srs, items, state, outs);
-    for (size_t k = 0; k < K; k++) mle_open_batch_sharded(ctx, srs, {items[k]}, state, &outs[k]);
-    return;
-  }
+  OpenFront F;
   unsigned long long* h_len = reinterpret_cast<unsigned long long*>(
       ctx->pinned_get("mleb_len_h", 2 * K * sizeof(unsigned long long)));
   unsigned long long* d_len = ctx->scratch_as<unsigned long long>("mleb_len", 2 * K);
@@ -2197,12 +2385,15 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
   // allocation id and offset).  The memo holds the last opened vector's key and
   // length: item k reuses it when flagged and item k - 1 (item 0: the memo
   // from before this call) opened the same vector
-  std::string& lt_memo = ctx->arena.memo["mle_poly_len"];
-  const std::string memo_in = lt_memo;
-  std::vector<std::string> lt_key(K);
-  std::vector<char> lt_known(K, 0);
-  std::vector<Fr*> dS(K, nullptr);
-  std::vector<size_t> Sn(K, 0), s_msm(K, 0);
+  F.memo_in = ctx->arena.memo["mle_poly_len"];
+  const std::string& memo_in = F.memo_in;
+  std::vector<std::string>& lt_key = F.lt_key;
+  std::vector<char>& lt_known = F.lt_known;
+  std::vector<Fr*>& dS = F.dS;
+  std::vector<size_t>& Sn = F.Sn;
+  lt_key.resize(K), lt_known.assign(K, 0), dS.assign(K, nullptr), Sn.assign(K, 0);
+  F.Lt.resize(K), F.Lq.resize(K);
+  std::vector<size_t> s_msm(K, 0);
   bool s_trim_first = false;
   for (size_t k = 0; k < K; k++) {
     const MleOpenItem& it = items[k];
@@ -2242,38 +2433,66 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
       }
   }
   std::vector<const Fr*> sp(dS.begin(), dS.end());
-  const std::vector<G1Affine> s_comm = msm_device_batch(ctx, srs, sp, s_msm);
+  F.s_comm = msm_device_batch(ctx, srs, sp, s_msm);
   ctx->sync();  // (drained already unless every MSM was empty)
+  F.h_len = h_len, F.h_eval = h_eval;
+  return F;
+}
+
+// item k's transcript step (mlpcs.rs:100-107), in item order: its trimmed
+// length (memo or device value), the memo for the next item, the evaluation
+// and s_comm into the proof
+static OpenChallenge open_batch_item_step(qg_ctx* ctx, OpenFront& F,
+                                          const std::vector<MleOpenItem>& items, size_t k,
+                                          uint8_t state[32], uint64_t evaluation_out[4],
+                                          uint64_t s_comm_xy[8], uint8_t* s_comm_inf) {
+  const MleOpenItem& it = items[k];
+  if (F.lt_known[k]) {
+    F.Lt[k] = k == 0 ? (size_t)std::stoull(F.memo_in.substr(F.lt_key[k].size())) : F.Lt[k - 1];
+    F.Lq[k] = F.Lt[k];
+  } else {
+    F.Lt[k] = (size_t)F.h_len[2 * k];
+    F.Lq[k] = fault_short_trim(ctx, F.Lt[k]);
+  }
+  ctx->arena.memo["mle_poly_len"] = it.id ? F.lt_key[k] + std::to_string(F.Lt[k]) : std::string();
+  const Fr evaluation = F.h_eval[k];
+  const OpenChallenge ch =
+      open_transcript_step(state, it.point, it.nvars, evaluation, F.s_comm[k]);
+  fr_export(evaluation, evaluation_out);
+  g1_export(F.s_comm[k], s_comm_xy, s_comm_inf);
+  return ch;
+}
+
+static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
+                                  const std::vector<MleOpenItem>& items, uint8_t state[32],
+                                  qg_mle_proof* outs) {
+  const size_t K = items.size();
+  if (K == 0) return;
+  if (ctx->sharded) {
+    // QG_OPEN_BATCH_SHARDED=0: a sharded context opens item by item (A/B runs)
+    const char* sb = getenv("QG_OPEN_BATCH_SHARDED");
+    if (!(sb && atoi(sb) == 0)) return mle_open_batch_sharded(ctx, srs, items, state, outs);
+    for (size_t k = 0; k < K; k++) mle_open_batch_sharded(ctx, srs, {items[k]}, state, &outs[k]);
+    return;
+  }
+  OpenFront F = open_batch_front(ctx, srs, items);
   // the transcript steps in item order (mlpcs.rs:100-107)
   std::vector<Fr> rs(K), rinv(K);
-  std::vector<size_t> Lt(K), Lq(K);  // Lq: the length the quotients use (Lt unless faulted)
   for (size_t k = 0; k < K; k++) {
-    const MleOpenItem& it = items[k];
-    if (lt_known[k]) {
-      Lt[k] = k == 0 ? (size_t)std::stoull(memo_in.substr(lt_key[k].size())) : Lt[k - 1];
-      Lq[k] = Lt[k];
-    } else {
-      Lt[k] = (size_t)h_len[2 * k];
-      Lq[k] = fault_short_trim(ctx, Lt[k]);
-    }
-    lt_memo = it.id ? lt_key[k] + std::to_string(Lt[k]) : std::string();
-    const Fr evaluation = h_eval[k];
-    const OpenChallenge ch =
-        open_transcript_step(state, it.point, it.nvars, evaluation, s_comm[k]);
+    const OpenChallenge ch = open_batch_item_step(ctx, F, items, k, state, outs[k].evaluation,
+                                                  outs[k].s_comm_xy, &outs[k].s_comm_inf);
     rs[k] = ch.r, rinv[k] = ch.r_inv;
-    fr_export(evaluation, outs[k].evaluation);
-    g1_export(s_comm[k], outs[k].s_comm_xy, &outs[k].s_comm_inf);
   }
   // every item's four quotients (mlpcs.rs:108-113; job 4k + i is item k's
   // OPEN_QNAME[i]), then all 4K commitments
   std::vector<QuotJob> jobs;
   for (size_t k = 0; k < K; k++) {
-    const size_t slen = fault_short_trim(ctx, (size_t)h_len[2 * k + 1]);
+    const size_t slen = fault_short_trim(ctx, (size_t)F.h_len[2 * k + 1]);
     const Open4 o4 = open4(outs[k]);
-    jobs.push_back({items[k].poly, items[k].n, Lq[k], rs[k], o4.o[0]});
-    jobs.push_back({items[k].poly, items[k].n, Lq[k], rinv[k], o4.o[1]});
-    jobs.push_back({dS[k], Sn[k], slen, rs[k], o4.o[2]});
-    jobs.push_back({dS[k], Sn[k], slen, rinv[k], o4.o[3]});
+    jobs.push_back({items[k].poly, items[k].n, F.Lq[k], rs[k], o4.o[0]});
+    jobs.push_back({items[k].poly, items[k].n, F.Lq[k], rinv[k], o4.o[1]});
+    jobs.push_back({F.dS[k], F.Sn[k], slen, rs[k], o4.o[2]});
+    jobs.push_back({F.dS[k], F.Sn[k], slen, rinv[k], o4.o[3]});
   }
   const QuotStage st = quotients_queue(ctx, jobs, 4);
   st.fit(srs);
@@ -2282,6 +2501,181 @@ static void mle_open_batch_device(qg_ctx* ctx, const qg_srs* srs,
   open_batch_trim_scratch(ctx, K);  // (before a failed check leaves the call)
   st.settle(ctx, OPEN_QNAME);
   st.store(pis);
+}
+
+// ---------------------------------------------------------------- folded opening
+// f and S are opened at the same two points, so with gamma drawn after the
+// four values y one quotient per point serves both: the quotient of
+// h = f + gamma S at x is q_f + gamma q_S, checked against C_f + gamma s_comm
+// (the same-point batching of GWC / PLONK; no counterpart in the reference,
+// DESIGN section 5).  Per opening 3 MSMs (S, W_r, W_inv) instead of 5, and two
+// quotient vectors instead of four.
+static const char* const FOLD_QNAME[2] = {"folded at r", "folded at 1/r"};
+static const char* const FOLD_XNAME[2] = {"combination at xs[0]", "combination at xs[1]"};
+
+// The check of one folded scan's quotients at sigma.  ev: the P source values
+// p_j(sigma) (over the untrimmed lengths), then the nq quotient values.
+// hs = sum_j g_j ev[j]; per point j: yh = yv ? yv[2j] + g_1 yv[2j + 1] (the
+// values of the evaluation kernel: y_f + gamma y_S) : the scan's own s_0;
+// w[j] = hs - yh != q_j(sigma) (sigma - x_j), or s_0 != yh.  has_q == 0 (the
+// trimmed length was 0): hs == 0 over the untrimmed lengths and yh == 0.
+struct FoldFin {
+  const Fr* ev;
+  int P, nq, has_q;
+  Fr g[SHF_P];
+  Fr d[2];  // sigma - x_j
+  const Fr* yv;
+  const Fr* s0[2];
+  uint32_t* w;
+};
+__global__ void k_fold_check_fin(FoldFin f) {
+  const int j = threadIdx.x;
+  if (blockIdx.x != 0 || j >= 2) return;
+  uint32_t bad = 0;
+  if (j < f.nq) {
+    Fr hs = Fr::zero();
+    for (int q = 0; q < f.P; q++) hs = hs + f.g[q] * f.ev[q];
+    if (f.has_q) {
+      const Fr s0 = *f.s0[j];
+      const Fr yh = f.yv ? f.yv[2 * j] + f.g[1] * f.yv[2 * j + 1] : s0;
+      const Fr r = hs - yh - f.ev[f.P + j] * f.d[j];
+      bad = (r.is_zero() && s0 == yh) ? 0u : 1u;
+    } else {
+      const Fr yh = f.yv ? f.yv[2 * j] + f.g[1] * f.yv[2 * j + 1] : Fr::zero();
+      bad = (hs.is_zero() && yh.is_zero()) ? 0u : 1u;
+    }
+  }
+  f.w[j] = bad;
+}
+
+// One folded scan with everything around it, queued: h = sum_j g[j] p_j over
+// L = its trimmed length (the caller's: the largest trimmed source length) at
+// nx points into s[.], the test fault, and kzg.rs:85's check into d_w[0..2)
+// (pn[j]: the untrimmed source lengths; yv as in FoldFin).
+struct FoldScan {
+  const Fr* p[SHF_P];
+  size_t pn[SHF_P], pl[SHF_P];  // untrimmed / trimmed lengths
+  Fr g[SHF_P];
+  int P;
+  size_t L;
+  Fr x[2];
+  int nx;
+  Fr* s[2];
+};
+static void fold_scan_queue(qg_ctx* ctx, const FoldScan& fs, const Fr* d_yv, uint32_t* d_w) {
+  if (fs.L) {
+    QgTimed tm(ctx, "kzg_division");
+    if (fs.nx == 2) {
+      ShFoldIn<2> in{};
+      for (int j = 0; j < fs.P; j++) in.c[j] = fs.p[j], in.n[j] = fs.pl[j], in.g[j] = fs.g[j];
+      in.P = fs.P, in.L = fs.L;
+      for (int p = 0; p < 2; p++) in.x[p] = fs.x[p], in.s[p] = fs.s[p];
+      suffix_horner_fold<2>(ctx, in);
+    } else {
+      ShFoldIn<1> in{};
+      for (int j = 0; j < fs.P; j++) in.c[j] = fs.p[j], in.n[j] = fs.pl[j], in.g[j] = fs.g[j];
+      in.P = fs.P, in.L = fs.L, in.x[0] = fs.x[0], in.s[0] = fs.s[0];
+      suffix_horner_fold<1>(ctx, in);
+    }
+  }
+  if (fs.L)
+    for (int p = 0; p < fs.nx; p++) fault_quotient(ctx, fs.s[p] + 1, fs.L - 1);
+  if (!d_w) return;
+  QgTimed tm(ctx, "kzg_open_check");
+  const Fr sigma = ctx->open_sigma;
+  std::vector<EvIn> in;
+  for (int j = 0; j < fs.P; j++) in.push_back({fs.p[j], fs.pn[j], 0});
+  if (fs.L)
+    for (int p = 0; p < fs.nx; p++) in.push_back({fs.s[p] + 1, fs.L - 1, 0});
+  Fr* d_ev = ctx->scratch_as<Fr>("open_ck_ev", 8);
+  poly_eval_queue(ctx, in, sigma, d_ev);
+  FoldFin f{};
+  f.ev = d_ev, f.P = fs.P, f.nq = fs.nx, f.has_q = fs.L ? 1 : 0;
+  for (int j = 0; j < fs.P; j++) f.g[j] = fs.g[j];
+  for (int p = 0; p < fs.nx; p++) f.d[p] = sigma - fs.x[p], f.s0[p] = fs.s[p];
+  f.yv = d_yv, f.w = d_w;
+  hipLaunchKernelGGL(k_fold_check_fin, dim3(1), dim3(64), 0, ctx->stream, f);
+  QG_LAUNCH_CHECK();
+}
+
+// The folded form of mle_open_batch_device, single context.  The first half
+// is the same (open_batch_front).  Then per item, in item order: the
+// transcript step, the four values y = (f(r), f(1/r), S(r), S(1/r)) by the
+// evaluation kernel over the untrimmed vectors (region "fold_eval"), one host
+// round trip - Fiat-Shamir forces it: gamma_k needs item k's y and item
+// k + 1's r needs gamma_k's transcript state -, the four appends, gamma_k, and
+// the folded scan queued.  All 2K quotient commitments are ONE MSM batch.
+static void mle_open_folded_batch_device(qg_ctx* ctx, const qg_srs* srs,
+                                         const std::vector<MleOpenItem>& items,
+                                         uint8_t state[32], qg_mle_proof_folded* outs) {
+  const size_t K = items.size();
+  if (K == 0) return;
+  memset(outs, 0, K * sizeof *outs);
+  OpenFront F = open_batch_front(ctx, srs, items);
+  const bool check = open_check_on();
+  Fr* d_y = ctx->scratch_as<Fr>("fold_y", 4);
+  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("fold_y_h", 4 * sizeof(Fr)));
+  uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 2 * K) : nullptr;
+  uint32_t* h_w =
+      reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 2 * K * sizeof(uint32_t)));
+  size_t nmax = 0;
+  for (const MleOpenItem& it : items) nmax = std::max(nmax, std::max(it.n, (size_t)1 << it.nvars));
+  poly_eval_reserve(ctx, 4, nmax);
+  std::vector<const Fr*> qs(2 * K, nullptr);
+  std::vector<size_t> qns(2 * K, 0);
+  std::vector<uint8_t> checked(check ? 2 * K : 0, CK_NONE);
+  for (size_t k = 0; k < K; k++) {
+    const MleOpenItem& it = items[k];
+    const OpenChallenge ch = open_batch_item_step(ctx, F, items, k, state, outs[k].evaluation,
+                                                  outs[k].s_comm_xy, &outs[k].s_comm_inf);
+    const size_t slen = fault_short_trim(ctx, (size_t)F.h_len[2 * k + 1]);
+    {
+      // d_y = f(r), S(r), f(1/r), S(1/r)
+      QgTimed tm(ctx, "fold_eval");
+      const std::vector<EvIn> two = {{it.poly, it.n, 0}, {F.dS[k], F.Sn[k], 0}};
+      poly_eval_queue(ctx, two, ch.r, d_y);
+      poly_eval_queue(ctx, two, ch.r_inv, d_y + 2);
+      QG_HIP(hipMemcpyAsync(h_y, d_y, 4 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ctx->sync();
+    const Fr y[4] = {h_y[0], h_y[2], h_y[1], h_y[3]};  // OPEN_QNAME order
+    for (int i = 0; i < 4; i++) {
+      uint8_t b32[32];
+      fr_to_bytes(y[i], b32);
+      transcript_append(state, b32, 32);
+      fr_export(y[i], outs[k].y[i]);
+    }
+    const Fr gamma = transcript_draw_fr(state);
+    const size_t Lh = std::max(F.Lq[k], slen);
+    QG_CHECK(Lh <= srs->n + 1, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+    FoldScan fs{};
+    fs.p[0] = it.poly, fs.pn[0] = it.n, fs.pl[0] = F.Lq[k], fs.g[0] = Fr::one();
+    fs.p[1] = F.dS[k], fs.pn[1] = F.Sn[k], fs.pl[1] = slen, fs.g[1] = gamma;
+    fs.P = 2, fs.L = Lh, fs.nx = 2, fs.x[0] = ch.r, fs.x[1] = ch.r_inv;
+    for (int p = 0; p < 2; p++) {
+      fs.s[p] = Lh ? ctx->scratch_as<Fr>("open_s#" + std::to_string(2 * k + p), Lh) : nullptr;
+      qs[2 * k + p] = Lh ? fs.s[p] + 1 : nullptr;
+      qns[2 * k + p] = Lh ? Lh - 1 : 0;
+    }
+    fold_scan_queue(ctx, fs, check ? d_y : nullptr, check ? d_w + 2 * k : nullptr);
+    if (check) {
+      QG_HIP(hipMemcpyAsync(h_w + 2 * k, d_w + 2 * k, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                            ctx->stream));
+      const uint8_t c = Lh ? CK_QUOT : (it.n || F.Sn[k]) ? CK_ZERO : CK_NONE;
+      checked[2 * k] = checked[2 * k + 1] = c;
+    }
+  }
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
+  ctx->sync();  // (drained already unless every quotient was empty)
+  open_batch_trim_scratch(ctx, K);  // (before a failed check leaves the call)
+  if (check) {
+    std::vector<uint32_t> bad(h_w, h_w + 2 * K);
+    open_check_settle(ctx, bad, checked, 2, FOLD_QNAME);
+  }
+  for (size_t k = 0; k < K; k++) {
+    g1_export(pis[2 * k], outs[k].w_xy, &outs[k].w_inf);
+    g1_export(pis[2 * k + 1], outs[k].w_inv_xy, &outs[k].w_inv_inf);
+  }
 }
 
 // a single opening is a batch of one
@@ -2651,6 +3045,124 @@ int qg_mle_open_dev_ex(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_
     OpenCall call(ctx);
     mle_open_device(ctx, srs, poly->d, n, point, nvars, state, out,
                     (flags & QG_OPEN_UNCHANGED) != 0, poly->alloc_id, poly->base_off);
+  });
+}
+
+// The folded entries are single-context: decided before OpenCall (collective on
+// a sharded context) and before any device work.
+static void fold_entry_checks(qg_ctx* ctx, const char* what) {
+  QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
+           std::string(what) + " is not supported on a sharded context (communicator "
+           "attached): the folded opening runs on a single context");
+}
+
+int qg_mle_open_folded_batch_dev(qg_ctx* ctx, const qg_srs* srs, const qg_mle_open_item* items,
+                                 size_t k, uint8_t state[32], qg_mle_proof_folded* outs) {
+  if (!ctx || !srs || (!items && k) || !state || (!outs && k)) return QG_ERR_INVALID;
+  for (size_t i = 0; i < k; i++)
+    if (!items[i].poly || items[i].n > items[i].poly->n || (!items[i].point && items[i].nvars) ||
+        items[i].nvars > 30 || (items[i].flags & ~(uint32_t)QG_OPEN_UNCHANGED))
+      return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    fold_entry_checks(ctx, "qg_mle_open_folded_batch_dev");
+    QG_CHECK(k <= 256, QG_ERR_UNSUPPORTED, "too many openings in one batch (at most 256)");
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    std::vector<MleOpenItem> v(k);
+    for (size_t i = 0; i < k; i++)
+      v[i] = {items[i].poly->d, items[i].n, items[i].point, items[i].nvars,
+              (items[i].flags & QG_OPEN_UNCHANGED) != 0, items[i].poly->alloc_id,
+              items[i].poly->base_off};
+    mle_open_folded_batch_device(ctx, srs, v, state, outs);
+  });
+}
+
+int qg_mle_open_folded_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* poly, size_t n,
+                           const uint64_t* point, size_t nvars, uint8_t state[32], uint32_t flags,
+                           qg_mle_proof_folded* out) {
+  if (!ctx || !srs || !poly || n > poly->n || (!point && nvars) || !state || !out ||
+      (flags & ~(uint32_t)QG_OPEN_UNCHANGED))
+    return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    fold_entry_checks(ctx, "qg_mle_open_folded_dev");
+    QG_CHECK(nvars <= 30, QG_ERR_INVALID, "too many variables");
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    mle_open_folded_batch_device(ctx, srs,
+                                 {{poly->d, n, point, nvars, (flags & QG_OPEN_UNCHANGED) != 0,
+                                   poly->alloc_id, poly->base_off}},
+                                 state, out);
+  });
+}
+
+int qg_kzg_open_lincomb_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* const* polys,
+                            const size_t* lens, const uint64_t* coeffs, size_t P,
+                            const uint64_t* xs, size_t nx, qg_kzg_opening* outs) {
+  if (!ctx || !srs || !polys || !lens || !coeffs || !xs || !outs || P < 1 || P > (size_t)SHF_P ||
+      nx < 1 || nx > 2)
+    return QG_ERR_INVALID;
+  for (size_t j = 0; j < P; j++)
+    if (!polys[j] || lens[j] > polys[j]->n) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    fold_entry_checks(ctx, "qg_kzg_open_lincomb_dev");
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    // KZG::open trims what it is given (kzg.rs:77): the scan runs over the
+    // largest trimmed source length (zero tail coefficients of h beyond its own
+    // degree only append zero quotient coefficients)
+    unsigned long long* d_len = ctx->scratch_as<unsigned long long>("fold_len", SHF_P);
+    unsigned long long h_len[SHF_P] = {0, 0, 0, 0};
+    QG_HIP(hipMemsetAsync(d_len, 0, SHF_P * sizeof(unsigned long long), ctx->stream));
+    for (size_t j = 0; j < P; j++) trim_launch(ctx, polys[j]->d, lens[j], d_len + j);
+    QG_HIP(hipMemcpyAsync(h_len, d_len, sizeof h_len, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    FoldScan fs{};
+    fs.P = (int)P, fs.nx = (int)nx;
+    size_t nmax = 0;
+    for (size_t j = 0; j < P; j++) {
+      fs.p[j] = polys[j]->d, fs.pn[j] = lens[j];
+      fs.pl[j] = fault_short_trim(ctx, (size_t)h_len[j]);
+      fs.g[j] = fr_import(coeffs + 4 * j);
+      fs.L = std::max(fs.L, fs.pl[j]);
+      nmax = std::max(nmax, lens[j]);
+    }
+    const bool check = open_check_on();
+    std::vector<const Fr*> qs(nx, nullptr);
+    std::vector<size_t> qns(nx, 0);
+    Fr* d_y = ctx->scratch_as<Fr>("open_y", 2);
+    Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("open_y_h", 2 * sizeof(Fr)));
+    uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 2) : nullptr;
+    uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 2 * sizeof(uint32_t)));
+    if (check) poly_eval_reserve(ctx, 6, nmax);
+    QG_HIP(hipMemsetAsync(d_y, 0, 2 * sizeof(Fr), ctx->stream));
+    for (size_t p = 0; p < nx; p++) {
+      fs.x[p] = fr_import(xs + 4 * p);
+      fs.s[p] = fs.L ? ctx->scratch_as<Fr>("open_s#" + std::to_string(p), fs.L) : nullptr;
+      qs[p] = fs.L ? fs.s[p] + 1 : nullptr, qns[p] = fs.L ? fs.L - 1 : 0;
+    }
+    fold_scan_queue(ctx, fs, nullptr, d_w);
+    for (size_t p = 0; p < nx; p++)
+      if (fs.L)
+        QG_HIP(hipMemcpyAsync(d_y + p, fs.s[p], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    QG_HIP(hipMemcpyAsync(h_y, d_y, 2 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    if (check)
+      QG_HIP(hipMemcpyAsync(h_w, d_w, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    // kzg_open_device's order: the check settles before the degree is judged
+    ctx->sync();
+    if (check) {
+      const uint8_t c = fs.L ? CK_QUOT : nmax ? CK_ZERO : CK_NONE;
+      open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + nx), std::vector<uint8_t>(nx, c), nx,
+                        FOLD_XNAME);
+    }
+    for (size_t n : qns)
+      QG_CHECK(n <= srs->n, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+    const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
+    ctx->sync();
+    for (size_t p = 0; p < nx; p++) {
+      fr_export(fs.x[p], outs[p].x);
+      fr_export(h_y[p], outs[p].y);
+      g1_export(pis[p], outs[p].proof_xy, &outs[p].proof_inf);
+    }
   });
 }
 

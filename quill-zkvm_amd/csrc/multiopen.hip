@@ -222,6 +222,21 @@ void entry_checks(qg_ctx* ctx, const char* what) {
 }
 
 }  // namespace
+
+// out[x] = sum_{j<P} coeffs[j] src[j][x] for x < n, queued on the context
+// stream (coeffs Montgomery; the folded opening's unfused route, mlpcs.hip)
+void lincomb_queue(qg_ctx* ctx, const Fr* const* src, const Fr* coeffs, size_t P, size_t n,
+                   Fr* out) {
+  QG_CHECK(P >= 1 && P <= (size_t)MO_PMAX, QG_ERR_ASSERT, "lincomb of 1 to 16 vectors");
+  if (n == 0) return;
+  LinArgs a{};
+  a.P = (uint32_t)P;
+  for (size_t j = 0; j < P; j++) a.src[j] = src[j], a.c[j] = to29(times32(coeffs[j]));
+  QgTimed tm(ctx, "lincomb");
+  hipLaunchKernelGGL(k_lincomb, dim3(div_up(n, MO_BLOCK)), dim3(MO_BLOCK), 0, ctx->stream, a, n,
+                     out);
+  QG_LAUNCH_CHECK();
+}
 }  // namespace qg
 
 extern "C" {

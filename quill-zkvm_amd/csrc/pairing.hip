@@ -571,6 +571,71 @@ void mle_verify_impl(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t com
   *ok = lhs == rhs ? 1 : 0;
 }
 
+// The folded opening's verifier (no counterpart in the reference; the prover
+// is mlpcs.hip's mle_open_folded_batch_device).  The transcript is replayed
+// in full - point, evaluation, s_comm, r, the four y, gamma - before anything
+// is judged, so `state` always ends as the prover's.  defer == nullptr: the two
+// pairing checks run here; otherwise the two claims go to defer[0..2).
+void mle_verify_folded_impl(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                            const uint64_t* point, size_t nvars,
+                            const qg_mle_proof_folded* proof, uint8_t state[32],
+                            qg_kzg_claim* defer, int* ok) {
+  const Vk v = vk_in(vk);
+  const G1Affine comm = g1_in(comm_xy, comm_inf);
+  const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
+  const G1Affine w = g1_in(proof->w_xy, proof->w_inf);
+  const G1Affine w_inv = g1_in(proof->w_inv_xy, proof->w_inv_inf);
+  std::vector<Fr> r(nvars);
+  std::vector<uint8_t> msg(8 + 32 * nvars);
+  u64_to_bytes(nvars, msg.data());
+  for (size_t i = 0; i < nvars; i++) {
+    r[i] = fr_import(point + 4 * i);
+    fr_to_bytes(r[i], msg.data() + 8 + 32 * i);
+  }
+  transcript_append(state, msg.data(), msg.size());
+  uint8_t b32[32], b64[64];
+  const Fr evaluation = fr_import(proof->evaluation);
+  fr_to_bytes(evaluation, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr x = transcript_draw_fr(state);
+  QG_CHECK(!x.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  const Fr x_inv = finv(x);
+  // the four y are bound before gamma is drawn
+  Fr y[4];
+  for (int i = 0; i < 4; i++) {
+    y[i] = fr_import(proof->y[i]);
+    fr_to_bytes(y[i], b32);
+    transcript_append(state, b32, 32);
+  }
+  const Fr gamma = transcript_draw_fr(state);
+  // C_h = comm + gamma s_comm; the two claims at r and 1/r
+  const G1Affine pts[2] = {comm, s_comm};
+  const Fr sc[2] = {Fr::one(), gamma};
+  const G1Affine c_h = msm_host_naive(pts, sc, 2);
+  qg_kzg_opening op[2];
+  memset(op, 0, sizeof op);
+  fr_export(x, op[0].x);
+  fr_export(y[0] + gamma * y[2], op[0].y);
+  g1_export(w, op[0].proof_xy, &op[0].proof_inf);
+  fr_export(x_inv, op[1].x);
+  fr_export(y[1] + gamma * y[3], op[1].y);
+  g1_export(w_inv, op[1].proof_xy, &op[1].proof_inf);
+  *ok = 0;
+  if (defer) {
+    claim_out(c_h, op[0], defer + 0);
+    claim_out(c_h, op[1], defer + 1);
+  } else if (!kzg_verify_abi(v, c_h, op[0]) || !kzg_verify_abi(v, c_h, op[1])) {
+    return;
+  }
+  // the inner-product equation (mlpcs.rs:153-160) on the four y
+  const Fr pr_r = eval_pr(r, x), pr_r_inv = eval_pr(r, x_inv);
+  const Fr lhs = y[0] * pr_r_inv + y[1] * pr_r;
+  const Fr rhs = x * y[2] + x_inv * y[3] + from_u64<FrP>(2) * evaluation;
+  *ok = lhs == rhs ? 1 : 0;
+}
+
 // InnerProductProof::verify (ipa.rs:160-202).  defer == nullptr: the six
 // pairing checks first, a failure returns before the transcript is touched;
 // otherwise the six pairs go to defer[0..6) and the transcript always advances.
@@ -712,6 +777,32 @@ int qg_mle_verify_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t 
     return QG_ERR_INVALID;
   try {
     mle_verify_impl(vk, comm_xy, comm_inf, point, nvars, proof, state, out, ok);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_mle_verify_folded(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                         const uint64_t* point, size_t nvars, const qg_mle_proof_folded* proof,
+                         uint8_t state[32], int* ok) {
+  if (!vk || !comm_xy || (!point && nvars) || !proof || !state || !ok) return QG_ERR_INVALID;
+  try {
+    mle_verify_folded_impl(vk, comm_xy, comm_inf, point, nvars, proof, state, nullptr, ok);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_mle_verify_folded_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
+                               const uint64_t* point, size_t nvars,
+                               const qg_mle_proof_folded* proof, uint8_t state[32],
+                               qg_kzg_claim out[2], int* ok) {
+  if (!vk || !comm_xy || (!point && nvars) || !proof || !state || !out || !ok)
+    return QG_ERR_INVALID;
+  try {
+    mle_verify_folded_impl(vk, comm_xy, comm_inf, point, nvars, proof, state, out, ok);
     return QG_OK;
   } catch (const Error& e) {
     return e.code;

@@ -51,6 +51,14 @@ class MleProof(C.Structure):
                 ("s_opening", KzgOpening), ("s_opening_inv", KzgOpening)]
 
 
+class MleProofFolded(C.Structure):
+    _fields_ = [("evaluation", C.c_uint64 * 4), ("s_comm_xy", C.c_uint64 * 8),
+                ("s_comm_inf", C.c_uint8), ("_pad", C.c_uint8 * 7),
+                ("y", (C.c_uint64 * 4) * 4),
+                ("w_xy", C.c_uint64 * 8), ("w_inf", C.c_uint8), ("_pad1", C.c_uint8 * 7),
+                ("w_inv_xy", C.c_uint64 * 8), ("w_inv_inf", C.c_uint8), ("_pad2", C.c_uint8 * 7)]
+
+
 class IpaProof(C.Structure):
     _fields_ = [("inner_product", C.c_uint64 * 4), ("s_comm_xy", C.c_uint64 * 8),
                 ("s_comm_inf", C.c_uint8), ("_pad", C.c_uint8 * 7),
@@ -158,6 +166,17 @@ PROTOTYPES = {
                                      C.POINTER(MleProof)]),
     "qg_mle_open_batch_dev": (C.c_int, [P, P, C.POINTER(MleOpenItem), SZ, U8P,
                                         C.POINTER(MleProof)]),
+    "qg_mle_open_folded_dev": (C.c_int, [P, P, P, SZ, U64P, SZ, U8P, C.c_uint32,
+                                         C.POINTER(MleProofFolded)]),
+    "qg_mle_open_folded_batch_dev": (C.c_int, [P, P, C.POINTER(MleOpenItem), SZ, U8P,
+                                               C.POINTER(MleProofFolded)]),
+    "qg_mle_verify_folded": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, SZ,
+                                       C.POINTER(MleProofFolded), U8P, C.POINTER(C.c_int)]),
+    "qg_mle_verify_folded_defer": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, SZ,
+                                             C.POINTER(MleProofFolded), U8P, C.POINTER(KzgClaim),
+                                             C.POINTER(C.c_int)]),
+    "qg_kzg_open_lincomb_dev": (C.c_int, [P, P, C.POINTER(P), C.POINTER(SZ), U64P, SZ, U64P, SZ,
+                                          C.POINTER(KzgOpening)]),
     "qg_ipa_prove": (C.c_int, [P, P, U64P, SZ, U64P, SZ, U8P, C.POINTER(IpaProof)]),
     "qg_ipa_prove_dev": (C.c_int, [P, P, P, SZ, P, SZ, U8P, C.POINTER(IpaProof)]),
     "qg_ipa_verify": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,

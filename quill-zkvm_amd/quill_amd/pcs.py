@@ -10,8 +10,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (IpaProof, KzgClaim, KzgOpening, KzgVk, MleOpenItem, MleProof, QuillGpuError,
-                   check, lib)
+from ._lib import (IpaProof, KzgClaim, KzgOpening, KzgVk, MleOpenItem, MleProof, MleProofFolded,
+                   QuillGpuError, check, lib)
 from .device import Device, DeviceVec, Srs
 from .field import (fq_from_mont_limbs, fr_array, fr_c, fr_from_mont_limbs, g1_from_abi,
                     g1_to_abi, g2_from_abi, g2_to_abi, u64p)
@@ -127,6 +127,57 @@ class MLEvalProof:
 
     def evaluation_claim(self):
         return EvaluationClaim(self.point(), self.evaluation)
+
+
+@dataclass
+class FoldedMLEvalProof:
+    """The folded ML opening (no counterpart in the reference; DESIGN section
+    5): f and S are opened at the same two points r and 1/r, so one quotient
+    per point, of f + gamma S, serves both.  y_* are the four values the
+    transcript absorbs before gamma is drawn; w, w_inv the two quotient
+    commitments.  The verifier derives the opening points and folded values."""
+    evaluation_point: list
+    evaluation: int
+    s_comm: object
+    y_poly: int
+    y_poly_inv: int
+    y_s: int
+    y_s_inv: int
+    w: object
+    w_inv: object
+
+    def verify(self, commitment, kzg: "KZG", transcript: Transcript) -> bool:
+        """qg_mle_verify_folded (or two claims of a deferring view's batch)"""
+        return kzg.verify(commitment, self, transcript)
+
+    def point(self):
+        return list(self.evaluation_point)
+
+    def evaluation_claim(self):
+        return EvaluationClaim(self.point(), self.evaluation)
+
+
+_FOLDED_Y = ("y_poly", "y_poly_inv", "y_s", "y_s_inv")
+_FOLDED_CLAIMS = ("folded at r", "folded at 1/r")
+
+
+def _folded_proof_c(p: FoldedMLEvalProof) -> MleProofFolded:
+    c = MleProofFolded()
+    C.memmove(c.evaluation, fr_c(p.evaluation), 32)
+    for fld, pt in (("s_comm", p.s_comm), ("w", p.w), ("w_inv", p.w_inv)):
+        xy, inf = g1_to_abi(pt)
+        C.memmove(getattr(c, fld + "_xy"), xy, 64)
+        setattr(c, fld + "_inf", inf)
+    for i, name in enumerate(_FOLDED_Y):
+        C.memmove(c.y[i], fr_c(getattr(p, name)), 32)
+    return c
+
+
+def _folded_proof(pt, o: MleProofFolded) -> FoldedMLEvalProof:
+    return FoldedMLEvalProof(list(pt), fr_from_mont_limbs(list(o.evaluation)),
+                             g1_from_abi(o.s_comm_xy, o.s_comm_inf),
+                             *[fr_from_mont_limbs(list(o.y[i])) for i in range(4)],
+                             g1_from_abi(o.w_xy, o.w_inf), g1_from_abi(o.w_inv_xy, o.w_inv_inf))
 
 
 def _ipa_proof_c(p: "InnerProductProof") -> IpaProof:
@@ -356,12 +407,24 @@ class KZG:
                                   C.byref(ok)))
         return bool(ok.value)
 
-    # MultilinearPCS::verify == MLEvalProof::verify (lib.rs:35-40, mlpcs.rs:126-161)
-    def verify(self, commitment, proof: MLEvalProof, transcript: Transcript) -> bool:
+    def folding(self) -> "FoldingKZG":
+        """a view of this key whose open, open_dev and open_batch_dev return
+        folded openings (FoldingKZG): pass it wherever a prover takes `pcs`.
+        Single-context only."""
+        return FoldingKZG(self)
+
+    # MultilinearPCS::verify == MLEvalProof::verify (lib.rs:35-40, mlpcs.rs:126-161);
+    # a FoldedMLEvalProof goes to the folded verifier
+    def verify(self, commitment, proof, transcript: Transcript) -> bool:
         xy, inf = g1_to_abi(commitment)
         pt = proof.evaluation_point
         arr = fr_array(pt) if len(pt) else np.zeros((1, 4), dtype=np.uint64)
         ok = C.c_int()
+        if isinstance(proof, FoldedMLEvalProof):
+            check(lib().qg_mle_verify_folded(C.byref(self._vk()), xy, inf, u64p(arr), len(pt),
+                                             C.byref(_folded_proof_c(proof)),
+                                             transcript.c_state(), C.byref(ok)))
+            return bool(ok.value)
         check(lib().qg_mle_verify(C.byref(self._vk()), xy, inf, u64p(arr), len(pt),
                                   C.byref(_mle_proof_c(proof)), transcript.c_state(),
                                   C.byref(ok)))
@@ -403,6 +466,20 @@ class KZG:
         check(lib().qg_kzg_open(self.dev.h, self.srs.h, u64p(arr), len(poly), fr_c(x),
                                 C.byref(out)), self.dev.h)
         return _opening(out)
+
+    def open_lincomb_dev(self, vecs, lens, coeffs, xs) -> list:
+        """KZG::open of sum_j coeffs[j] vecs[j][:lens[j]] at the one or two
+        points xs, the combination formed inside the quotient scan
+        (qg_kzg_open_lincomb_dev; the folded opening's building block)"""
+        P, nx = len(vecs), len(xs)
+        hs = (C.c_void_p * max(P, 1))(*[v.h.value for v in vecs])
+        ls = (C.c_size_t * max(P, 1))(*lens)
+        cs = fr_array(coeffs) if P else np.zeros((1, 4), dtype=np.uint64)
+        xa = fr_array(xs) if nx else np.zeros((1, 4), dtype=np.uint64)
+        outs = (KzgOpening * max(nx, 1))()
+        check(lib().qg_kzg_open_lincomb_dev(self.dev.h, self.srs.h if self.srs else None, hs, ls,
+                                            u64p(cs), P, u64p(xa), nx, outs), self.dev.h)
+        return [_opening(outs[i]) for i in range(nx)]
 
     # MultilinearPCS::open == MLEvalProof::prove (mlpcs.rs:83-124, 191-198)
     def open_dev(self, vec, n, eval_point, transcript: Transcript,
@@ -482,6 +559,69 @@ class KZG:
                            _opening(out.s_opening), _opening(out.s_opening_inv))
 
 
+class FoldingKZG:
+    """The folded ML opening as a view of a KZG key (KZG.folding()): open,
+    open_dev and open_batch_dev return FoldedMLEvalProofs (qg_mle_open_folded_dev
+    / _batch_dev: 3 MSMs and 2 KZG claims per opening instead of 5 and 4); every
+    other attribute is the key's.  KZG.verify and DeferringKZG.verify take the
+    proofs as they take MLEvalProofs."""
+
+    def __init__(self, base: "KZG"):
+        if base.dev is not None and (base.dev.world > 1 or base.dev.comm_info()["sharded"]):
+            raise ValueError("the folded opening is not supported on a sharded device "
+                             "(communicator attached)")
+        self.base = base
+
+    def __getattr__(self, name):
+        return getattr(self.base, name)
+
+    def folding(self) -> "FoldingKZG":
+        return self
+
+    def open_dev(self, vec, n, eval_point, transcript: Transcript,
+                 unchanged: bool = False) -> FoldedMLEvalProof:
+        pt = fr_array(eval_point) if len(eval_point) else np.zeros((1, 4), dtype=np.uint64)
+        out = MleProofFolded()
+        dev = self.base.dev
+        check(lib().qg_mle_open_folded_dev(dev.h, self.base.srs_for(n).h, vec.h, n, u64p(pt),
+                                           len(eval_point), transcript.c_state(),
+                                           1 if unchanged else 0, C.byref(out)), dev.h)
+        return _folded_proof(eval_point, out)
+
+    def open_batch_dev(self, items, transcript: Transcript) -> list:
+        """K folded openings [(vec, n, eval_point, unchanged), ...] in one call:
+        the same proofs and transcript as K successive open_dev calls"""
+        if len(items) <= 1:
+            return [self.open_dev(v, n, pt, transcript, unch) for v, n, pt, unch in items]
+        k = len(items)
+        arr = (MleOpenItem * k)()
+        pts = []
+        for i, (vec, n, pt, unch) in enumerate(items):
+            a = fr_array(pt) if len(pt) else np.zeros((1, 4), dtype=np.uint64)
+            pts.append(a)  # kept alive through the call
+            arr[i] = MleOpenItem(vec.h.value, n, a.ctypes.data_as(C.POINTER(C.c_uint64)), len(pt),
+                                 1 if unch else 0, 0)
+        outs = (MleProofFolded * k)()
+        dev = self.base.dev
+        check(lib().qg_mle_open_folded_batch_dev(dev.h, self.base.srs.h, arr, k,
+                                                 transcript.c_state(), outs), dev.h)
+        return [_folded_proof(pt, o) for (_, _, pt, _), o in zip(items, outs)]
+
+    def open_multi(self, polys, claims, transcript: Transcript):
+        from .multiopen import MultiOpenProof
+        return MultiOpenProof.prove(polys, claims, self, transcript)
+
+    def open(self, poly, eval_point, transcript: Transcript,
+             unchanged: bool = False) -> FoldedMLEvalProof:
+        if isinstance(poly, DeviceVec):
+            return self.open_dev(poly, len(poly), eval_point, transcript, unchanged)
+        vec = DeviceVec.from_list(self.base.dev, list(poly) if len(poly) else [0])
+        try:
+            return self.open_dev(vec, len(poly), eval_point, transcript)
+        finally:
+            vec.close()
+
+
 _MLE_OPENINGS = ("poly_opening", "poly_opening_inv", "s_opening", "s_opening_inv")
 
 
@@ -540,10 +680,17 @@ class DeferringKZG:
         self._push(opening, (None,), (_claim_c(commitment, opening),))
         return True
 
-    def verify(self, commitment, proof: MLEvalProof, transcript: Transcript) -> bool:
+    def verify(self, commitment, proof, transcript: Transcript) -> bool:
         xy, inf = g1_to_abi(commitment)
         pt = proof.evaluation_point
         arr = fr_array(pt) if len(pt) else np.zeros((1, 4), dtype=np.uint64)
+        if isinstance(proof, FoldedMLEvalProof):
+            ok, out = C.c_int(), (KzgClaim * 2)()
+            check(lib().qg_mle_verify_folded_defer(C.byref(self.base._vk()), xy, inf, u64p(arr),
+                                                   len(pt), C.byref(_folded_proof_c(proof)),
+                                                   transcript.c_state(), out, C.byref(ok)))
+            self._push(proof, _FOLDED_CLAIMS, out)
+            return bool(ok.value)
         ok, out = C.c_int(), (KzgClaim * 4)()
         check(lib().qg_mle_verify_defer(C.byref(self.base._vk()), xy, inf, u64p(arr), len(pt),
                                         C.byref(_mle_proof_c(proof)), transcript.c_state(), out,

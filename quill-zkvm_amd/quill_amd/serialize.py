@@ -33,6 +33,15 @@ Structs (field order of the reference):
   HyperPlonkProof        witness_commitment, trace_proofs (proof.rs:27-30)
   MultiOpenProof         evaluations (Vec<Fr>), sumcheck, opening (multiopen.py;
                          no counterpart in the reference)
+  FoldedMLEvalProof      evaluation_point, evaluation, s_comm, y_poly, y_poly_inv,
+                         y_s, y_s_inv, w, w_inv (pcs.py; no counterpart in the
+                         reference): 256 bytes after s_comm where MLEvalProof
+                         has 512
+
+A proof made with a folding key (KZG.folding()) holds a FoldedMLEvalProof at
+every ML-opening position.  serialize() dispatches on the opening's type; the
+two forms carry no tag, so deserialize() takes the expected opening type as
+`opening=` (default MLEvalProof: exactly the format above).
 
 A TraceProof made with multi_open=True carries `multi_openings` instead of the
 five opening fields: after permutation_check_proof comes ONE flag byte, 0xFF
@@ -53,7 +62,7 @@ from .field import P_MOD, R_MOD
 from .hyperplonk import SumcheckProof, ZeroCheckProof
 from .logup import MultisetEqualityProof, PermutationCheckProof
 from .multiopen import MultiOpenProof
-from .pcs import InnerProductProof, KZGOpeningProof, MLEvalProof
+from .pcs import FoldedMLEvalProof, InnerProductProof, KZGOpeningProof, MLEvalProof
 from .proof import HyperPlonkProof, TraceProof
 
 _INF, _NEG = 0x40, 0x80
@@ -90,7 +99,11 @@ def _kzg_opening(o: KZGOpeningProof) -> bytes:
     return _fr(o.x) + _fr(o.y) + _g1(o.proof)
 
 
-def _mle(p: MLEvalProof) -> bytes:
+def _mle(p) -> bytes:
+    if isinstance(p, FoldedMLEvalProof):
+        return (_vec(list(p.evaluation_point), _fr) + _fr(p.evaluation) + _g1(p.s_comm)
+                + _fr(p.y_poly) + _fr(p.y_poly_inv) + _fr(p.y_s) + _fr(p.y_s_inv)
+                + _g1(p.w) + _g1(p.w_inv))
     return (_vec(list(p.evaluation_point), _fr) + _fr(p.evaluation) + _g1(p.s_comm)
             + _kzg_opening(p.poly_opening) + _kzg_opening(p.poly_opening_inv)
             + _kzg_opening(p.s_opening) + _kzg_opening(p.s_opening_inv))
@@ -140,6 +153,7 @@ def _hyperplonk(p: HyperPlonkProof) -> bytes:
 
 
 _ENCODERS = [(HyperPlonkProof, _hyperplonk), (TraceProof, _trace), (MLEvalProof, _mle),
+             (FoldedMLEvalProof, _mle),
              (InnerProductProof, _ipa), (MultiOpenProof, _multiopen),
              (SumcheckProof, _sumcheck), (ZeroCheckProof, _zerocheck),
              (MultisetEqualityProof, _multiset),
@@ -157,8 +171,9 @@ def serialize(obj) -> bytes:
 
 # ---------------------------------------------------------------- readers
 class _Reader:
-    def __init__(self, b: bytes):
+    def __init__(self, b: bytes, opening=MLEvalProof):
         self.b, self.o = memoryview(bytes(b)), 0
+        self.folded = opening is FoldedMLEvalProof
 
     def take(self, n: int) -> bytes:
         if self.o + n > len(self.b):
@@ -205,6 +220,9 @@ class _Reader:
     def mle(self):
         pt = self.vec(self.fr)
         ev, s = self.fr(), self.g1()
+        if self.folded:
+            y = [self.fr() for _ in range(4)]
+            return FoldedMLEvalProof(pt, ev, s, *y, self.g1(), self.g1())
         return MLEvalProof(pt, ev, s, self.kzg_opening(), self.kzg_opening(),
                            self.kzg_opening(), self.kzg_opening())
 
@@ -252,15 +270,21 @@ _DECODERS = {HyperPlonkProof: "hyperplonk", TraceProof: "trace", MLEvalProof: "m
              MultisetEqualityProof: "multiset", KZGOpeningProof: "kzg_opening"}
 
 
-def deserialize(cls, data: bytes):
-    """CanonicalDeserialize::deserialize_uncompressed (Validate::Yes)"""
+def deserialize(cls, data: bytes, opening=MLEvalProof):
+    """CanonicalDeserialize::deserialize_uncompressed (Validate::Yes).
+    opening=FoldedMLEvalProof: every ML-opening position of the proof decodes
+    as a folded opening (a proof made with KZG.folding())."""
+    if opening not in (MLEvalProof, FoldedMLEvalProof):
+        raise TypeError(f"no ML opening format {getattr(opening, '__name__', opening)}")
+    if cls is FoldedMLEvalProof:
+        cls, opening = MLEvalProof, FoldedMLEvalProof
     if cls is PermutationCheckProof:
-        r = _Reader(data)
+        r = _Reader(data, opening)
         out = PermutationCheckProof(r.multiset())
     else:
         if cls not in _DECODERS:
             raise TypeError(f"no wire format for {cls.__name__}")
-        r = _Reader(data)
+        r = _Reader(data, opening)
         out = getattr(r, _DECODERS[cls])()
     if r.o != len(r.b):
         raise ValueError("trailing bytes after the proof")
