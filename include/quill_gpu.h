@@ -450,6 +450,68 @@ int qg_ipa_prove(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf, c
 int qg_ipa_prove_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf, const qg_buf* g,
                      size_t ng, uint8_t state[32], qg_ipa_proof* out);
 
+/* ---- folded inner-product argument (opt-in; no counterpart in the reference).
+ * InnerProductProof::prove opens three polynomials, f, g and S, each at r and
+ * 1/r (the TODO at ipa.rs:86).  Three polynomials opened at the same point need
+ * one quotient: with gamma drawn after the six values, (h - h(x))/(X - x) for
+ * h = f + gamma g + gamma^2 S is one KZG claim against
+ * C_f + gamma C_g + gamma^2 s_comm (the folded ML opening's batching with three
+ * sources).  Per proof 3 MSMs instead of 7, 2 KZG claims instead of 6, 2
+ * quotient vectors instead of 6, and a smaller proof.
+ * Prover: as InnerProductProof::prove up to r (inner_product over the common
+ * prefix, S of the zero-padded pair, s_comm over the trimmed S; append
+ * inner_product, s_comm; draw r; r = 0 is QG_ERR_ASSERT);
+ * y = (f(r), f(1/r), g(r), g(1/r), S(r), S(1/r)) over the untrimmed vectors,
+ * appended as six Fr in that order; draw gamma (not redrawn when 0); nothing
+ * further is absorbed.  h over L_h = max(trimmed lengths of f, g, S)
+ * coefficients, a missing coefficient counting as 0; w = commit((h - h(r))/
+ * (X - r)), w_inv the same at 1/r, each over L_h - 1 coefficients (L_h = 0:
+ * both the identity, all y 0).  The proof carries no opening x and no folded
+ * y: the verifier derives both. */
+typedef struct qg_ipa_proof_folded {
+  uint64_t inner_product[4];
+  uint64_t s_comm_xy[8];
+  uint8_t s_comm_inf;
+  uint8_t _pad[7];
+  uint64_t y[6][4]; /* f at r, f at 1/r, g at r, g at 1/r, S at r, S at 1/r */
+  uint64_t w_xy[8];
+  uint8_t w_inf;
+  uint8_t _pad1[7];
+  uint64_t w_inv_xy[8];
+  uint8_t w_inv_inf;
+  uint8_t _pad2[7];
+} qg_ipa_proof_folded;
+/* The folded form of qg_ipa_prove_dev on a single context.  The first half is
+ * qg_ipa_prove_dev's (same launches).  Then the six values by the evaluation
+ * kernel (timed region "fold_eval": one two-point pass over f, g and S,
+ * qg_poly_eval2_dev's kernel, or with QG_EVAL_PAIRED=0 - read per call; 1 or
+ * unset: the former - two qg_poly_eval_dev passes; identical proofs, and the
+ * former measured faster), one host round
+ * trip (gamma needs the six values), the assertion of ipa.rs:94-100 on them
+ * ("Inner product verification equation failed", QG_ERR_ASSERT), one folded
+ * scan over three sources (QG_FOLD_FUSED as for qg_mle_open_folded_dev) and one
+ * MSM batch of the two quotients.  Both quotients are checked like every
+ * opening's ("open_checks" rises by 2 per proof): at the context's sigma,
+ * sum_q gamma^q p_q(sigma) - sum_q gamma^q y_q == q(sigma)(sigma - x), and the
+ * scan's own h(x) equals sum_q gamma^q y_q; a failure is QG_ERR_ASSERT
+ * "Polynomial division failed: opening 0 of 1, quotient j (folded at r)" or
+ * "(folded at 1/r)".  QG_OPEN_CHECK=0 and qg_debug_open_fault act as on the
+ * other opening paths.
+ * QG_ERR_INVALID: the argument checks of qg_ipa_prove_dev (null handles, a
+ * length beyond the buffer, nf == 0 && ng == 0), S or L_h - 1 beyond the SRS
+ * ("Polynomial degree exceeds max degree").  QG_ERR_UNSUPPORTED: a context with
+ * a communicator attached ("sharded" in qg_last_error), before any device work
+ * or collective.  Like qg_ipa_prove, the call transforms f in the scratch the
+ * ML opening keeps its transform in. */
+int qg_ipa_prove_folded_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf,
+                            const qg_buf* g, size_t ng, uint8_t state[32],
+                            qg_ipa_proof_folded* out);
+/* Same for host vectors: uploads, then the same path (argument checks of
+ * qg_ipa_prove). */
+int qg_ipa_prove_folded(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf,
+                        const uint64_t* g, size_t ng, uint8_t state[32],
+                        qg_ipa_proof_folded* out);
+
 /* ---------------------------------------------------------------- verifiers (host) */
 /* BN254 G2 affine points on the D-type twist E'/Fq2 (y^2 = x^3 + 3/(9 + u)):
  * x.c0, x.c1, y.c0, y.c1, each 4 u64 Montgomery limbs (like G1's Fq). */
@@ -579,6 +641,26 @@ int qg_mle_verify_folded(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t
 int qg_mle_verify_folded_defer(const qg_kzg_vk* vk, const uint64_t comm_xy[8], uint8_t comm_inf,
                                const uint64_t* point, size_t nvars,
                                const qg_mle_proof_folded* proof, uint8_t state[32],
+                               qg_kzg_claim out[2], int* ok);
+/* The folded inner-product argument's verifier (host, no context) against the
+ * commitments to f (comm1) and g (comm2).  gamma comes from the replay, so the
+ * KZG checks cannot run first as in qg_ipa_verify: BOTH forms replay first -
+ * inner_product, s_comm; draw r (r = 0 is QG_ERR_ASSERT, as in qg_ipa_verify);
+ * the proof's six y; draw gamma - and `state` ALWAYS advances to the prover's
+ * final state, whatever the verdict (qg_ipa_verify leaves it untouched when an
+ * opening fails).  Then C_h = comm1 + gamma comm2 + gamma^2 s_comm
+ * (qg_g1_lincomb's host code), the two KZG claims (C_h, r, y[0] + gamma y[2] +
+ * gamma^2 y[4], w) and (C_h, 1/r, y[1] + gamma y[3] + gamma^2 y[5], w_inv), and
+ * the equation of ipa.rs:198-201 on the six y.  *ok = 0 when either claim or
+ * the equation fails.  Every point must be on the curve (QG_ERR_INVALID).  The
+ * _defer form skips the two pairing checks and hands the two claims out for
+ * qg_kzg_verify_batch; *ok then reports the equation alone. */
+int qg_ipa_verify_folded(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                         const uint64_t comm2_xy[8], uint8_t comm2_inf,
+                         const qg_ipa_proof_folded* proof, uint8_t state[32], int* ok);
+int qg_ipa_verify_folded_defer(const qg_kzg_vk* vk, const uint64_t comm1_xy[8],
+                               uint8_t comm1_inf, const uint64_t comm2_xy[8], uint8_t comm2_inf,
+                               const qg_ipa_proof_folded* proof, uint8_t state[32],
                                qg_kzg_claim out[2], int* ok);
 
 /* Building blocks of the opening, exposed for testing and for callers that
@@ -931,6 +1013,17 @@ int qg_ctx_counter(const qg_ctx* ctx, const char* name, uint64_t* value);
  * kernel's grid. */
 int qg_poly_eval_dev(qg_ctx* ctx, const qg_buf* poly, size_t n, const uint64_t x[4],
                      uint64_t shift, uint64_t out[4]);
+/* The same at two points with one pass over each vector: out[P i + j] =
+ * sum_{k < lens[j]} polys[j][k] * xs[i]^k for i < 2, j < P (xs: 2 Fr, out: 2 P
+ * Fr, Montgomery), the same bits as 2 P qg_poly_eval_dev calls.  A thread of
+ * the kernel loads each coefficient of its strip once and runs one Horner
+ * chain per point.  The folded inner-product argument's six values come from
+ * it unless QG_EVAL_PAIRED=0.  Limits: 1 <= P <= 8; anything else, null
+ * pointers and a length beyond its buffer included, is QG_ERR_INVALID.
+ * QG_ERR_UNSUPPORTED on a context with a communicator attached ("sharded" in
+ * qg_last_error).  QG_EVAL_BLOCKS as above. */
+int qg_poly_eval2_dev(qg_ctx* ctx, const qg_buf* const* polys, const size_t* lens, size_t P,
+                      const uint64_t* xs, uint64_t* out);
 /* TEST ONLY (like qg_selftest_inverse): arms a one-shot fault that the next
  * opening call on this context consumes, so the tests can show that the
  * quotient check catches it; afterwards the context is clean.  kind 0 disarms;

@@ -631,6 +631,157 @@ static void poly_eval_reserve(qg_ctx* ctx, size_t jobs, size_t nmax) {
   ctx->scratch_as<Fr>("ev_part", std::min<size_t>(jobs, EV_MAXJ) * ((nmax + EV_SPAN - 1) / EV_SPAN) + 1);
 }
 
+// The same reduction at NP points in one pass (the folded inner-product
+// argument evaluates f, g and S at r and 1/r): a thread loads each coefficient
+// of its strip once and runs NP independent Horner chains; the shuffle tree,
+// the LDS stage and the span stage carry all NP values.  The points, their
+// strip powers and the strip length are the launch's (every job of a launch
+// shares them), so EV_MAXJ jobs still fit the kernel arguments.  LAST: the span
+// stage - chain p reads its own span values c[p] and multiplies by sh[p].
+// The bounds per chain are k_poly_eval's; stored values are canonical, so the
+// output equals NP poly_eval_queue calls bit for bit whatever the strips.
+template <int NP>
+struct EvJobN {
+  const Fr* c[NP];  // first stage: c[0] (one vector); span stage: one per point
+  size_t n;
+  L9 sh[NP];        // span stage: x_p^shift 2^261
+  Fr* out[NP];      // out[p][g] = value of span g at x_p; span stage: out[p][0]
+};
+template <int NP>
+struct EvJobsN {
+  L9 x[NP];      // x_p 2^261 mod p
+  L9 xp[NP][7];  // x_p^(S 2^k) 2^261, k = 0..6
+  size_t S;      // strip length (>= 1)
+  EvJobN<NP> j[EV_MAXJ];
+};
+
+template <int NP, bool LAST>
+__global__ void __launch_bounds__(EV_T) __attribute__((amdgpu_waves_per_eu(4)))
+k_poly_eval_np(EvJobsN<NP> jb) {
+  const EvJobN<NP>& J = jb.j[blockIdx.y];
+  __shared__ uint32_t lds[NP][EV_T / 64][9];
+  F29<FrP> x[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) x[p] = F29<FrP>::from_l9(jb.x[p]);
+  const size_t span = jb.S * EV_T;
+  const size_t nspans = (J.n + span - 1) / span;
+  if (LAST && nspans == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int p = 0; p < NP; p++) J.out[p][0] = Fr::zero();
+  }
+  for (size_t g = blockIdx.x; g < nspans; g += gridDim.x) {  // block-uniform
+    const size_t s = g * span + (size_t)threadIdx.x * jb.S;
+    F29<FrP> acc[NP];
+#pragma unroll
+    for (int p = 0; p < NP; p++) acc[p] = F29<FrP>::zero();
+    if (s < J.n) {
+      const size_t e = jb.S < J.n - s ? s + jb.S : J.n;
+#pragma unroll 2
+      for (size_t i = e; i-- > s;) {
+        const F29<FrP> c0 = to29(J.c[0][i]);
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+          const F29<FrP> c = LAST && p ? to29(J.c[p][i]) : c0;
+          acc[p] = red2p29(add29(c, mul29(x[p], acc[p])));
+        }
+      }
+    }
+    // lane l += x^(S m) * lane (l + m), m = 1, 2, .., 32, per chain
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+#pragma unroll
+      for (int p = 0; p < NP; p++) {
+        const F29<FrP> o = shfl_down29(acc[p], 1 << k);
+        acc[p] = red2p29(add29(acc[p], mul29(F29<FrP>::from_l9(jb.xp[p][k]), o)));
+      }
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+      for (int p = 0; p < NP; p++)
+#pragma unroll
+        for (int i = 0; i < 9; i++) lds[p][wid][i] = acc[p].l[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < NP) {  // thread p finishes chain p
+      const int p = threadIdx.x;
+      const F29<FrP> pw = F29<FrP>::from_l9(jb.xp[p][6]);  // x_p^(64 S)
+      F29<FrP> r = F29<FrP>::zero();
+      for (int w = EV_T / 64 - 1; w >= 0; w--) {
+        F29<FrP> v;
+#pragma unroll
+        for (int i = 0; i < 9; i++) v.l[i] = lds[p][w][i];
+        r = red2p29(add29(v, mul29(pw, r)));
+      }
+      if (LAST) r = mul29(F29<FrP>::from_l9(J.sh[p]), r);
+      J.out[p][g] = from29(canon29(r));
+    }
+    __syncthreads();
+  }
+}
+
+// d_out[P i + j] = sum_{k < n_j} c_j[k] xs[i]^(shift_j + k), P = in.size(), i < 2:
+// poly_eval_queue at two points with one pass over each vector.  QG_EVAL_BLOCKS
+// as there.
+static void poly_eval2_queue(qg_ctx* ctx, const std::vector<EvIn>& in, const Fr xs[2],
+                             Fr* d_out) {
+  constexpr int NP = 2;
+  const char* eb = getenv("QG_EVAL_BLOCKS");
+  const size_t cap = eb && atoi(eb) > 0 ? (size_t)atoi(eb) : 4096;
+  const size_t P = in.size();
+  auto strip_powers = [](Fr b, L9 (&o)[7]) {  // b^(2^k), k = 0..6
+    for (int k = 0; k < 7; k++, b = b * b) o[k] = x261_of(b);
+  };
+  size_t need = 1;
+  for (size_t b = 0; b < P; b += EV_MAXJ) {
+    size_t tot = 0;
+    for (size_t q = b; q < std::min(P, b + EV_MAXJ); q++) tot += (in[q].n + EV_SPAN - 1) / EV_SPAN;
+    need = std::max(need, tot);
+  }
+  Fr* part = ctx->scratch_as<Fr>("ev_part", NP * need);
+  for (size_t b = 0; b < P; b += EV_MAXJ) {
+    const size_t nj = std::min<size_t>(EV_MAXJ, P - b);
+    size_t nsp[EV_MAXJ], off[EV_MAXJ], tot = 0, maxsp = 0;
+    for (size_t q = 0; q < nj; q++) {
+      nsp[q] = (in[b + q].n + EV_SPAN - 1) / EV_SPAN;
+      off[q] = tot;
+      tot += nsp[q];
+      maxsp = std::max(maxsp, nsp[q]);
+    }
+    EvJobsN<NP> j1{}, j2{};
+    j1.S = EV_S;
+    j2.S = std::max<size_t>(1, (maxsp + EV_T - 1) / EV_T);  // one block covers every job's spans
+    Fr X[NP];
+    for (int p = 0; p < NP; p++) {
+      j1.x[p] = x261_of(xs[p]);
+      strip_powers(fpow_small(xs[p], EV_S), j1.xp[p]);
+      X[p] = fpow_small(xs[p], EV_SPAN);
+      j2.x[p] = x261_of(X[p]);
+      strip_powers(fpow_small(X[p], j2.S), j2.xp[p]);
+    }
+    for (size_t q = 0; q < nj; q++) {
+      const EvIn& I = in[b + q];
+      EvJobN<NP>& a = j1.j[q];
+      EvJobN<NP>& z = j2.j[q];
+      a.n = I.n, z.n = nsp[q];
+      for (int p = 0; p < NP; p++) {
+        a.c[p] = I.c, a.out[p] = part + p * need + off[q];
+        z.c[p] = a.out[p], z.sh[p] = x261_of(fpow_small(xs[p], I.shift));
+        z.out[p] = d_out + p * P + b + q;
+      }
+    }
+    if (maxsp) {
+      hipLaunchKernelGGL((k_poly_eval_np<NP, false>),
+                         dim3((unsigned)std::min(maxsp, cap), (unsigned)nj), dim3(EV_T), 0,
+                         ctx->stream, j1);
+      QG_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((k_poly_eval_np<NP, true>), dim3(1, (unsigned)nj), dim3(EV_T), 0,
+                       ctx->stream, j2);
+    QG_LAUNCH_CHECK();
+  }
+}
+
 // ---------------------------------------------------------------- quotient check
 // KZG::open asserts q (X - x) == p - y after its division (kzg.rs:85,
 // "Polynomial division failed").  Here: p(sigma) - y == q(sigma) (sigma - x) at
@@ -2515,8 +2666,10 @@ static const char* const FOLD_XNAME[2] = {"combination at xs[0]", "combination a
 
 // The check of one folded scan's quotients at sigma.  ev: the P source values
 // p_j(sigma) (over the untrimmed lengths), then the nq quotient values.
-// hs = sum_j g_j ev[j]; per point j: yh = yv ? yv[2j] + g_1 yv[2j + 1] (the
-// values of the evaluation kernel: y_f + gamma y_S) : the scan's own s_0;
+// hs = sum_q g_q ev[q]; per point j: yh = yv ? sum_q g_q yv[P j + q] (the
+// values of the evaluation kernel, P per point: y_f + gamma y_S for the ML
+// opening, y_f + gamma y_g + gamma^2 y_S for the inner-product argument) : the
+// scan's own s_0;
 // w[j] = hs - yh != q_j(sigma) (sigma - x_j), or s_0 != yh.  has_q == 0 (the
 // trimmed length was 0): hs == 0 over the untrimmed lengths and yh == 0.
 struct FoldFin {
@@ -2535,14 +2688,16 @@ __global__ void k_fold_check_fin(FoldFin f) {
   if (j < f.nq) {
     Fr hs = Fr::zero();
     for (int q = 0; q < f.P; q++) hs = hs + f.g[q] * f.ev[q];
+    Fr yv = Fr::zero();
+    if (f.yv)
+      for (int q = 0; q < f.P; q++) yv = yv + f.g[q] * f.yv[f.P * j + q];
     if (f.has_q) {
       const Fr s0 = *f.s0[j];
-      const Fr yh = f.yv ? f.yv[2 * j] + f.g[1] * f.yv[2 * j + 1] : s0;
+      const Fr yh = f.yv ? yv : s0;
       const Fr r = hs - yh - f.ev[f.P + j] * f.d[j];
       bad = (r.is_zero() && s0 == yh) ? 0u : 1u;
     } else {
-      const Fr yh = f.yv ? f.yv[2 * j] + f.g[1] * f.yv[2 * j + 1] : Fr::zero();
-      bad = (hs.is_zero() && yh.is_zero()) ? 0u : 1u;
+      bad = (hs.is_zero() && yv.is_zero()) ? 0u : 1u;
     }
   }
   f.w[j] = bad;
@@ -2748,8 +2903,20 @@ static void ipa_check_equation(const Fr y[6], const Fr& r, const Fr& r_inv, cons
            QG_ERR_ASSERT, "Inner product verification equation failed");
 }
 
-static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_t nf,
-                             const Fr* dg, size_t ng, uint8_t state[32], qg_ipa_proof* out) {
+// What the first half of the argument leaves (ipa.rs:59-83), shared with the
+// folded form below: S and its length, the trimmed lengths the quotients use,
+// and the challenge; inner_product and s_comm are in the proof already.
+struct IpaFront {
+  Fr* dS;
+  size_t Sn;
+  Fr ip;
+  size_t Lf, Lg, Ls;
+  OpenChallenge ch;
+};
+
+static IpaFront ipa_front(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_t nf, const Fr* dg,
+                          size_t ng, uint8_t state[32], uint64_t ip_out[4], uint64_t s_comm_xy[8],
+                          uint8_t* s_comm_inf) {
   const size_t M = nf > ng ? nf : ng;  // >= 1 (the caller's check)
   const size_t Sn = M - 1;
   unsigned long long* h_len = reinterpret_cast<unsigned long long*>(
@@ -2786,12 +2953,20 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
   const size_t Lg = fault_short_trim(ctx, (size_t)h_len[1]);
   const size_t Ls = fault_short_trim(ctx, (size_t)h_len[2]);
   const OpenChallenge ch = ipa_transcript_step(state, ip, s_comm);
-  fr_export(ip, out->inner_product);
-  g1_export(s_comm, out->s_comm_xy, &out->s_comm_inf);
+  fr_export(ip, ip_out);
+  g1_export(s_comm, s_comm_xy, s_comm_inf);
+  return {dS, Sn, ip, Lf, Lg, Ls, ch};
+}
+
+static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_t nf,
+                             const Fr* dg, size_t ng, uint8_t state[32], qg_ipa_proof* out) {
+  const IpaFront F = ipa_front(ctx, srs, df, nf, dg, ng, state, out->inner_product,
+                               out->s_comm_xy, &out->s_comm_inf);
+  const OpenChallenge& ch = F.ch;
   // six KZG::open (ipa.rs:87-92): the quotients (job 2p + i: polynomial p of
   // f, g, S at r, 1/r), then their commitments as one MSM batch
-  const Fr* polys[3] = {df, dg, dS};
-  const size_t ns[3] = {nf, ng, Sn}, lts[3] = {Lf, Lg, Ls};
+  const Fr* polys[3] = {df, dg, F.dS};
+  const size_t ns[3] = {nf, ng, F.Sn}, lts[3] = {F.Lf, F.Lg, F.Ls};
   const Open6 o6 = open6(*out);
   std::vector<QuotJob> jobs;
   for (int i = 0; i < 6; i++)
@@ -2802,7 +2977,93 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
   ctx->sync();  // (drained already unless every quotient was empty)
   st.settle(ctx, IPA_QNAME);
   st.store(pis);
-  ipa_check_equation(st.h_y, ch.r, ch.r_inv, ip);
+  ipa_check_equation(st.h_y, ch.r, ch.r_inv, F.ip);
+}
+
+// ---------------------------------------------------------------- folded inner-product argument
+// f, g and S are opened at the same two points, so with gamma drawn after the
+// six values y one quotient per point serves all three: the quotient of
+// h = f + gamma g + gamma^2 S at x, checked against C_f + gamma C_g +
+// gamma^2 s_comm (the folded ML opening's batching at P = 3; no counterpart in
+// the reference).  3 MSMs (S, W_r, W_inv) instead of 7, two
+// quotient vectors instead of six.  The first half is ipa_front; then the six
+// values over the untrimmed vectors (region "fold_eval"), one host round trip,
+// the six appends and gamma, one folded scan and one MSM batch.
+// The values come from one two-point pass over each vector (poly_eval2_queue)
+// or from two single passes (poly_eval_queue at r, then at 1/r): the same
+// bits.  QG_EVAL_PAIRED (read per call) selects: 1 the two-point kernel, 0 the
+// two single calls.  Unset is the two-point kernel: measured
+// (profiles/fold_ipa.json, DESIGN section 5 "Folded inner-product argument")
+// its fold_eval region is 0.147 ms against 0.177 ms at 2^20 coefficients and
+// 0.345 against 0.384 ms at 2^22, both beyond the spread of the repeated
+// medians (0.010 and 0.022 ms).
+static constexpr bool EVAL_PAIRED_DEFAULT = true;
+static bool eval_paired_on() {
+  const char* e = getenv("QG_EVAL_PAIRED");
+  return e ? atoi(e) != 0 : EVAL_PAIRED_DEFAULT;
+}
+
+static void ipa_prove_folded_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_t nf,
+                                    const Fr* dg, size_t ng, uint8_t state[32],
+                                    qg_ipa_proof_folded* out) {
+  memset(out, 0, sizeof *out);
+  const IpaFront F = ipa_front(ctx, srs, df, nf, dg, ng, state, out->inner_product,
+                               out->s_comm_xy, &out->s_comm_inf);
+  const OpenChallenge& ch = F.ch;
+  const bool check = open_check_on();
+  Fr* d_y = ctx->scratch_as<Fr>("ipaf_y", 6);
+  Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("ipaf_y_h", 6 * sizeof(Fr)));
+  uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 2) : nullptr;
+  uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 2 * sizeof(uint32_t)));
+  poly_eval_reserve(ctx, EV_MAXJ, nf > ng ? nf : ng);
+  {
+    // d_y[3 i + p] = polynomial p of f, g, S at r (i = 0), 1/r (i = 1)
+    QgTimed tm(ctx, "fold_eval");
+    const std::vector<EvIn> three = {{df, nf, 0}, {dg, ng, 0}, {F.dS, F.Sn, 0}};
+    if (eval_paired_on()) {
+      const Fr xs[2] = {ch.r, ch.r_inv};
+      poly_eval2_queue(ctx, three, xs, d_y);
+    } else {
+      poly_eval_queue(ctx, three, ch.r, d_y);
+      poly_eval_queue(ctx, three, ch.r_inv, d_y + 3);
+    }
+    QG_HIP(hipMemcpyAsync(h_y, d_y, 6 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  ctx->sync();
+  Fr y[6];  // IPA_QNAME order
+  for (int i = 0; i < 6; i++) y[i] = h_y[3 * (i & 1) + (i >> 1)];
+  ipa_check_equation(y, ch.r, ch.r_inv, F.ip);
+  for (int i = 0; i < 6; i++) {
+    uint8_t b32[32];
+    fr_to_bytes(y[i], b32);
+    transcript_append(state, b32, 32);
+    fr_export(y[i], out->y[i]);
+  }
+  const Fr gamma = transcript_draw_fr(state);
+  const size_t Lh = std::max(F.Lf, std::max(F.Lg, F.Ls));
+  QG_CHECK(Lh <= srs->n + 1, QG_ERR_INVALID, "Polynomial degree exceeds max degree");
+  FoldScan fs{};
+  fs.p[0] = df, fs.pn[0] = nf, fs.pl[0] = F.Lf, fs.g[0] = Fr::one();
+  fs.p[1] = dg, fs.pn[1] = ng, fs.pl[1] = F.Lg, fs.g[1] = gamma;
+  fs.p[2] = F.dS, fs.pn[2] = F.Sn, fs.pl[2] = F.Ls, fs.g[2] = gamma * gamma;
+  fs.P = 3, fs.L = Lh, fs.nx = 2, fs.x[0] = ch.r, fs.x[1] = ch.r_inv;
+  std::vector<const Fr*> qs(2, nullptr);
+  std::vector<size_t> qns(2, 0);
+  for (int p = 0; p < 2; p++) {
+    fs.s[p] = Lh ? ctx->scratch_as<Fr>("open_s#" + std::to_string(p), Lh) : nullptr;
+    qs[p] = Lh ? fs.s[p] + 1 : nullptr;
+    qns[p] = Lh ? Lh - 1 : 0;
+  }
+  fold_scan_queue(ctx, fs, check ? d_y : nullptr, d_w);
+  if (check)
+    QG_HIP(hipMemcpyAsync(h_w, d_w, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qns);
+  ctx->sync();  // (drained already unless both quotients were empty)
+  if (check)
+    open_check_settle(ctx, std::vector<uint32_t>(h_w, h_w + 2),
+                      std::vector<uint8_t>(2, Lh ? CK_QUOT : CK_ZERO), 2, FOLD_QNAME);
+  g1_export(pis[0], out->w_xy, &out->w_inf);
+  g1_export(pis[1], out->w_inv_xy, &out->w_inv_inf);
 }
 
 // The local geometry of a sharded inner-product argument, decided from this
@@ -3206,6 +3467,60 @@ int qg_ipa_prove_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf,
     OpenCall call(ctx);
     if (ctx->sharded) ipa_prove_sharded(ctx, srs, f->d, g->d, nf, nvars, state, out);
     else ipa_prove_device(ctx, srs, f->d, nf, g->d, ng, state, out);
+  });
+}
+
+// The folded entries: qg_ipa_prove[_dev]'s argument checks; a sharded context
+// is refused before OpenCall (collective there) and before any device work.
+int qg_ipa_prove_folded(qg_ctx* ctx, const qg_srs* srs, const uint64_t* f, size_t nf,
+                        const uint64_t* g, size_t ng, uint8_t state[32],
+                        qg_ipa_proof_folded* out) {
+  if (!ctx || !srs || (!f && nf) || (!g && ng) || !state || !out) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    fold_entry_checks(ctx, "qg_ipa_prove_folded");
+    QG_CHECK(nf || ng, QG_ERR_INVALID, "inner-product argument of two empty polynomials");
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    Fr* df = ctx->scratch_as<Fr>("ipa_f", nf ? nf : 1);
+    Fr* dg = ctx->scratch_as<Fr>("ipa_g", ng ? ng : 1);
+    fr_upload(ctx, df, f, nf);
+    fr_upload(ctx, dg, g, ng);
+    ipa_prove_folded_device(ctx, srs, df, nf, dg, ng, state, out);
+  });
+}
+
+int qg_ipa_prove_folded_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* f, size_t nf,
+                            const qg_buf* g, size_t ng, uint8_t state[32],
+                            qg_ipa_proof_folded* out) {
+  if (!ctx || !srs || !f || !g || nf > f->n || ng > g->n || !state || !out) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    QG_CHECK(nf || ng, QG_ERR_INVALID, "inner-product argument of two empty polynomials");
+    fold_entry_checks(ctx, "qg_ipa_prove_folded_dev");
+    QG_HIP(hipSetDevice(ctx->device));
+    OpenCall call(ctx);
+    ipa_prove_folded_device(ctx, srs, f->d, nf, g->d, ng, state, out);
+  });
+}
+
+int qg_poly_eval2_dev(qg_ctx* ctx, const qg_buf* const* polys, const size_t* lens, size_t P,
+                      const uint64_t* xs, uint64_t* out) {
+  if (!ctx || !polys || !lens || !xs || !out || P < 1 || P > (size_t)EV_MAXJ)
+    return QG_ERR_INVALID;
+  for (size_t j = 0; j < P; j++)
+    if (!polys[j] || lens[j] > polys[j]->n) return QG_ERR_INVALID;
+  return qg_guard(ctx, [&] {
+    QG_CHECK(!ctx->sharded, QG_ERR_UNSUPPORTED,
+             "qg_poly_eval2_dev is not supported on a sharded context (communicator attached)");
+    QG_HIP(hipSetDevice(ctx->device));
+    Fr* d = ctx->scratch_as<Fr>("ev2_out", 2 * EV_MAXJ);
+    std::vector<EvIn> in;
+    for (size_t j = 0; j < P; j++) in.push_back({polys[j]->d, lens[j], 0});
+    const Fr x2[2] = {fr_import(xs), fr_import(xs + 4)};
+    poly_eval2_queue(ctx, in, x2, d);
+    Fr r[2 * EV_MAXJ];
+    QG_HIP(hipMemcpyAsync(r, d, 2 * P * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    for (size_t k = 0; k < 2 * P; k++) fr_export(r[k], out + 4 * k);
   });
 }
 

@@ -681,6 +681,63 @@ void ipa_verify_impl(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t co
   *ok = lhs == rhs ? 1 : 0;
 }
 
+// The folded inner-product argument's verifier (no counterpart in the
+// reference; the prover is mlpcs.hip's ipa_prove_folded_device).  gamma comes
+// from the replay, so the transcript is replayed in full - inner_product,
+// s_comm, r, the six y, gamma - before anything is judged, and `state` always
+// ends as the prover's.  defer == nullptr: the two pairing checks run here;
+// otherwise the two claims go to defer[0..2).
+void ipa_verify_folded_impl(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                            const uint64_t comm2_xy[8], uint8_t comm2_inf,
+                            const qg_ipa_proof_folded* proof, uint8_t state[32],
+                            qg_kzg_claim* defer, int* ok) {
+  const Vk v = vk_in(vk);
+  const G1Affine comm1 = g1_in(comm1_xy, comm1_inf), comm2 = g1_in(comm2_xy, comm2_inf);
+  const G1Affine s_comm = g1_in(proof->s_comm_xy, proof->s_comm_inf);
+  const G1Affine w = g1_in(proof->w_xy, proof->w_inf);
+  const G1Affine w_inv = g1_in(proof->w_inv_xy, proof->w_inv_inf);
+  uint8_t b32[32], b64[64];
+  const Fr ip = fr_import(proof->inner_product);
+  fr_to_bytes(ip, b32);
+  transcript_append(state, b32, 32);
+  g1_serialize(s_comm, b64);
+  transcript_append(state, b64, 64);
+  const Fr r = transcript_draw_fr(state);
+  QG_CHECK(!r.is_zero(), QG_ERR_ASSERT, "challenge r = 0");
+  const Fr r_inv = finv(r);
+  // the six y are bound before gamma is drawn
+  Fr y[6];
+  for (int i = 0; i < 6; i++) {
+    y[i] = fr_import(proof->y[i]);
+    fr_to_bytes(y[i], b32);
+    transcript_append(state, b32, 32);
+  }
+  const Fr gamma = transcript_draw_fr(state), gamma2 = gamma * gamma;
+  // C_h = comm1 + gamma comm2 + gamma^2 s_comm; the two claims at r and 1/r
+  const G1Affine pts[3] = {comm1, comm2, s_comm};
+  const Fr sc[3] = {Fr::one(), gamma, gamma2};
+  const G1Affine c_h = msm_host_naive(pts, sc, 3);
+  qg_kzg_opening op[2];
+  memset(op, 0, sizeof op);
+  fr_export(r, op[0].x);
+  fr_export(y[0] + gamma * y[2] + gamma2 * y[4], op[0].y);
+  g1_export(w, op[0].proof_xy, &op[0].proof_inf);
+  fr_export(r_inv, op[1].x);
+  fr_export(y[1] + gamma * y[3] + gamma2 * y[5], op[1].y);
+  g1_export(w_inv, op[1].proof_xy, &op[1].proof_inf);
+  *ok = 0;
+  if (defer) {
+    claim_out(c_h, op[0], defer + 0);
+    claim_out(c_h, op[1], defer + 1);
+  } else if (!kzg_verify_abi(v, c_h, op[0]) || !kzg_verify_abi(v, c_h, op[1])) {
+    return;
+  }
+  // ipa.rs:198-201 on the six y
+  const Fr lhs = y[0] * y[3] + y[1] * y[2];
+  const Fr rhs = r * y[4] + r_inv * y[5] + from_u64<FrP>(2) * ip;
+  *ok = lhs == rhs ? 1 : 0;
+}
+
 }  // namespace
 
 // the whole key is validated (g1 on the curve, both G2 points in the subgroup)
@@ -827,6 +884,32 @@ int qg_ipa_verify_defer(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t
   if (!vk || !comm1_xy || !comm2_xy || !proof || !state || !out || !ok) return QG_ERR_INVALID;
   try {
     ipa_verify_impl(vk, comm1_xy, comm1_inf, comm2_xy, comm2_inf, proof, state, out, ok);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_ipa_verify_folded(const qg_kzg_vk* vk, const uint64_t comm1_xy[8], uint8_t comm1_inf,
+                         const uint64_t comm2_xy[8], uint8_t comm2_inf,
+                         const qg_ipa_proof_folded* proof, uint8_t state[32], int* ok) {
+  if (!vk || !comm1_xy || !comm2_xy || !proof || !state || !ok) return QG_ERR_INVALID;
+  try {
+    ipa_verify_folded_impl(vk, comm1_xy, comm1_inf, comm2_xy, comm2_inf, proof, state, nullptr,
+                           ok);
+    return QG_OK;
+  } catch (const Error& e) {
+    return e.code;
+  }
+}
+
+int qg_ipa_verify_folded_defer(const qg_kzg_vk* vk, const uint64_t comm1_xy[8],
+                               uint8_t comm1_inf, const uint64_t comm2_xy[8], uint8_t comm2_inf,
+                               const qg_ipa_proof_folded* proof, uint8_t state[32],
+                               qg_kzg_claim out[2], int* ok) {
+  if (!vk || !comm1_xy || !comm2_xy || !proof || !state || !out || !ok) return QG_ERR_INVALID;
+  try {
+    ipa_verify_folded_impl(vk, comm1_xy, comm1_inf, comm2_xy, comm2_inf, proof, state, out, ok);
     return QG_OK;
   } catch (const Error& e) {
     return e.code;

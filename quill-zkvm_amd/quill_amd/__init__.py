@@ -8,8 +8,8 @@ from ._lib import LIB_PATH, QuillGpuError, lib  # noqa: F401
 from .device import Device, DeviceVec, Srs  # noqa: F401
 from .hyperplonk import (SumcheckProof, VirtualPolyExpr, VirtualPolynomialStore,  # noqa: F401
                          ZeroCheckProof)
-from .pcs import (KZG, DeferringKZG, EvaluationClaim, FoldedMLEvalProof,  # noqa: F401
-                  FoldingKZG, InnerProductProof, KZGOpeningProof, MLEvalProof, g1_lincomb, g2_generator, g2_mul, pairing)
+from .pcs import (KZG, DeferringKZG, EvaluationClaim, FoldedInnerProductProof,  # noqa: F401
+                  FoldedMLEvalProof, FoldingKZG, InnerProductProof, KZGOpeningProof, MLEvalProof, g1_lincomb, g2_generator, g2_mul, pairing)
 from .transcript import Transcript  # noqa: F401
 from .logup import (LookupMode, LookupProof, MultisetEqualityProof,  # noqa: F401
                     PermutationCheckProof, SetInclusionProof, expr_column,

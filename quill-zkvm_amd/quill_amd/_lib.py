@@ -67,6 +67,14 @@ class IpaProof(C.Structure):
                 ("s_opening", KzgOpening), ("s_opening_inv", KzgOpening)]
 
 
+class IpaProofFolded(C.Structure):
+    _fields_ = [("inner_product", C.c_uint64 * 4), ("s_comm_xy", C.c_uint64 * 8),
+                ("s_comm_inf", C.c_uint8), ("_pad", C.c_uint8 * 7),
+                ("y", (C.c_uint64 * 4) * 6),
+                ("w_xy", C.c_uint64 * 8), ("w_inf", C.c_uint8), ("_pad1", C.c_uint8 * 7),
+                ("w_inv_xy", C.c_uint64 * 8), ("w_inv_inf", C.c_uint8), ("_pad2", C.c_uint8 * 7)]
+
+
 class KzgClaim(C.Structure):
     _fields_ = [("comm_xy", C.c_uint64 * 8), ("comm_inf", C.c_uint8), ("_pad", C.c_uint8 * 7),
                 ("opening", KzgOpening)]
@@ -181,6 +189,15 @@ PROTOTYPES = {
     "qg_ipa_prove_dev": (C.c_int, [P, P, P, SZ, P, SZ, U8P, C.POINTER(IpaProof)]),
     "qg_ipa_verify": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,
                                 C.POINTER(IpaProof), U8P, C.POINTER(C.c_int)]),
+    "qg_ipa_prove_folded": (C.c_int, [P, P, U64P, SZ, U64P, SZ, U8P,
+                                      C.POINTER(IpaProofFolded)]),
+    "qg_ipa_prove_folded_dev": (C.c_int, [P, P, P, SZ, P, SZ, U8P, C.POINTER(IpaProofFolded)]),
+    "qg_ipa_verify_folded": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,
+                                       C.POINTER(IpaProofFolded), U8P, C.POINTER(C.c_int)]),
+    "qg_ipa_verify_folded_defer": (C.c_int, [C.POINTER(KzgVk), U64P, C.c_uint8, U64P, C.c_uint8,
+                                             C.POINTER(IpaProofFolded), U8P, C.POINTER(KzgClaim),
+                                             C.POINTER(C.c_int)]),
+    "qg_poly_eval2_dev": (C.c_int, [P, C.POINTER(P), C.POINTER(SZ), SZ, U64P, U64P]),
     "qg_kzg_batch_fold": (C.c_int, [C.POINTER(KzgVk), C.POINTER(KzgClaim), SZ, U8P, U64P, U8P,
                                     U64P, U8P]),
     "qg_kzg_batch_fold_dev": (C.c_int, [P, C.POINTER(KzgVk), C.POINTER(KzgClaim), SZ, U8P, U64P,

@@ -153,6 +153,18 @@ class Device:
         check(lib().qg_ctx_phase_split(self.h, arr, k, out), self.h)
         return {n: out[i] for i, n in enumerate(names)}
 
+    def poly_eval2(self, polys, lens, xs) -> list:
+        """[[p_j(xs[i]) for j] for i in (0, 1)] over the first lens[j] entries of
+        the DeviceVecs polys[j], each vector read once (qg_poly_eval2_dev)"""
+        from .field import fr_from_mont_limbs
+        k = len(polys)
+        hs = (C.c_void_p * max(k, 1))(*[v.h.value for v in polys])
+        ls = (C.c_size_t * max(k, 1))(*lens)
+        out = (C.c_uint64 * (8 * max(k, 1)))()
+        check(lib().qg_poly_eval2_dev(self.h, hs, ls, k, u64p(fr_array(xs)), out), self.h)
+        vals = [fr_from_mont_limbs(list(out)[4 * i:4 * i + 4]) for i in range(2 * k)]
+        return [vals[:k], vals[k:]]
+
     # ---- device math building blocks (mlpcs.rs / ipa.rs / eq_eval.rs) ----
     def eq_table_dev(self, point, out: "DeviceVec" = None) -> "DeviceVec":
         """fast_eq_eval_hypercube (eq_eval.rs:6-31) into a device vector"""

@@ -10,8 +10,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (IpaProof, KzgClaim, KzgOpening, KzgVk, MleOpenItem, MleProof, MleProofFolded,
-                   QuillGpuError, check, lib)
+from ._lib import (IpaProof, IpaProofFolded, KzgClaim, KzgOpening, KzgVk, MleOpenItem, MleProof,
+                   MleProofFolded, QuillGpuError, check, lib)
 from .device import Device, DeviceVec, Srs
 from .field import (fq_from_mont_limbs, fr_array, fr_c, fr_from_mont_limbs, g1_from_abi,
                     g1_to_abi, g2_from_abi, g2_to_abi, u64p)
@@ -253,6 +253,87 @@ class InnerProductProof:
                                   C.byref(_ipa_proof_c(self)), transcript.c_state(),
                                   C.byref(ok)))
         return bool(ok.value)
+
+
+_IPA_FOLDED_Y = ("y_f", "y_f_inv", "y_g", "y_g_inv", "y_s", "y_s_inv")
+
+
+@dataclass
+class FoldedInnerProductProof:
+    """The folded inner-product argument (no counterpart in the reference;
+    DESIGN section 5): f, g and S are opened at the same two points r and 1/r,
+    so one quotient per point, of f + gamma g + gamma^2 S, serves all three.
+    y_* are the six values the transcript absorbs before gamma is drawn; w,
+    w_inv the two quotient commitments.  The verifier derives the opening
+    points and folded values."""
+    inner_product: int
+    s_comm: object
+    y_f: int
+    y_f_inv: int
+    y_g: int
+    y_g_inv: int
+    y_s: int
+    y_s_inv: int
+    w: object
+    w_inv: object
+
+    @classmethod
+    def prove(cls, poly1, poly2, kzg, transcript: Transcript) -> "FoldedInnerProductProof":
+        """qg_ipa_prove_folded_dev when both operands are DeviceVecs, else
+        qg_ipa_prove_folded on two host vectors; `kzg` is a KZG or its
+        FoldingKZG view.  Like InnerProductProof.prove, the commitments to
+        poly1 and poly2 are the caller's to absorb beforehand.  Single-context
+        only: a Device with a communicator raises ValueError."""
+        dev = kzg.dev
+        if dev.world > 1 or dev.comm_info()["sharded"]:
+            raise ValueError("the folded inner-product argument is not supported on a sharded "
+                             "device (communicator attached)")
+        out = IpaProofFolded()
+        n = max(len(poly1), len(poly2))
+        if isinstance(poly1, DeviceVec) and isinstance(poly2, DeviceVec):
+            rc = lib().qg_ipa_prove_folded_dev(dev.h, kzg.srs_for(n).h, poly1.h, len(poly1),
+                                               poly2.h, len(poly2), transcript.c_state(),
+                                               C.byref(out))
+        else:
+            if isinstance(poly1, DeviceVec) or isinstance(poly2, DeviceVec):
+                raise QuillGpuError(-1, "FoldedInnerProductProof.prove: both operands on the "
+                                        "device, or both on the host")
+            a = fr_array(poly1) if len(poly1) else np.zeros((1, 4), dtype=np.uint64)
+            b = fr_array(poly2) if len(poly2) else np.zeros((1, 4), dtype=np.uint64)
+            rc = lib().qg_ipa_prove_folded(dev.h, kzg.srs_for(n).h, u64p(a), len(poly1), u64p(b),
+                                           len(poly2), transcript.c_state(), C.byref(out))
+        check(rc, dev.h)
+        return cls(fr_from_mont_limbs(list(out.inner_product)),
+                   g1_from_abi(out.s_comm_xy, out.s_comm_inf),
+                   *[fr_from_mont_limbs(list(out.y[i])) for i in range(6)],
+                   g1_from_abi(out.w_xy, out.w_inf), g1_from_abi(out.w_inv_xy, out.w_inv_inf))
+
+    def verify(self, comm1, comm2, kzg, transcript: Transcript) -> bool:
+        """qg_ipa_verify_folded: the transcript is replayed first (gamma comes
+        from it) and always advances to the prover's final state, whatever the
+        verdict.  With a deferring view (KZG.deferring) the two claims join the
+        view's batch and only the equation's verdict returns."""
+        if isinstance(kzg, DeferringKZG):
+            return kzg.verify_inner_product(comm1, comm2, self, transcript)
+        xy1, inf1 = g1_to_abi(comm1)
+        xy2, inf2 = g1_to_abi(comm2)
+        ok = C.c_int()
+        check(lib().qg_ipa_verify_folded(C.byref(kzg._vk()), xy1, inf1, xy2, inf2,
+                                         C.byref(_ipa_folded_proof_c(self)),
+                                         transcript.c_state(), C.byref(ok)))
+        return bool(ok.value)
+
+
+def _ipa_folded_proof_c(p: FoldedInnerProductProof) -> IpaProofFolded:
+    c = IpaProofFolded()
+    C.memmove(c.inner_product, fr_c(p.inner_product), 32)
+    for fld, pt in (("s_comm", p.s_comm), ("w", p.w), ("w_inv", p.w_inv)):
+        xy, inf = g1_to_abi(pt)
+        C.memmove(getattr(c, fld + "_xy"), xy, 64)
+        setattr(c, fld + "_inf", inf)
+    for i, name in enumerate(_IPA_FOLDED_Y):
+        C.memmove(c.y[i], fr_c(getattr(p, name)), 32)
+    return c
 
 
 class KZG:
@@ -698,10 +779,16 @@ class DeferringKZG:
         self._push(proof, _MLE_OPENINGS, out)
         return bool(ok.value)
 
-    def verify_inner_product(self, comm1, comm2, proof: InnerProductProof,
-                             transcript: Transcript) -> bool:
+    def verify_inner_product(self, comm1, comm2, proof, transcript: Transcript) -> bool:
         xy1, inf1 = g1_to_abi(comm1)
         xy2, inf2 = g1_to_abi(comm2)
+        if isinstance(proof, FoldedInnerProductProof):
+            ok, out = C.c_int(), (KzgClaim * 2)()
+            check(lib().qg_ipa_verify_folded_defer(C.byref(self.base._vk()), xy1, inf1, xy2, inf2,
+                                                   C.byref(_ipa_folded_proof_c(proof)),
+                                                   transcript.c_state(), out, C.byref(ok)))
+            self._push(proof, _FOLDED_CLAIMS, out)
+            return bool(ok.value)
         ok, out = C.c_int(), (KzgClaim * 6)()
         check(lib().qg_ipa_verify_defer(C.byref(self.base._vk()), xy1, inf1, xy2, inf2,
                                         C.byref(_ipa_proof_c(proof)), transcript.c_state(), out,

@@ -37,6 +37,9 @@ Structs (field order of the reference):
                          y_s, y_s_inv, w, w_inv (pcs.py; no counterpart in the
                          reference): 256 bytes after s_comm where MLEvalProof
                          has 512
+  FoldedInnerProductProof  inner_product, s_comm, y_f, y_f_inv, y_g, y_g_inv,
+                         y_s, y_s_inv, w, w_inv (pcs.py; no counterpart in the
+                         reference): 416 bytes where InnerProductProof has 864
 
 A proof made with a folding key (KZG.folding()) holds a FoldedMLEvalProof at
 every ML-opening position.  serialize() dispatches on the opening's type; the
@@ -62,7 +65,8 @@ from .field import P_MOD, R_MOD
 from .hyperplonk import SumcheckProof, ZeroCheckProof
 from .logup import MultisetEqualityProof, PermutationCheckProof
 from .multiopen import MultiOpenProof
-from .pcs import FoldedMLEvalProof, InnerProductProof, KZGOpeningProof, MLEvalProof
+from .pcs import (FoldedInnerProductProof, FoldedMLEvalProof, InnerProductProof, KZGOpeningProof,
+                  MLEvalProof)
 from .proof import HyperPlonkProof, TraceProof
 
 _INF, _NEG = 0x40, 0x80
@@ -116,6 +120,12 @@ def _ipa(p: InnerProductProof) -> bytes:
             + _kzg_opening(p.s_opening) + _kzg_opening(p.s_opening_inv))
 
 
+def _ipa_folded(p: FoldedInnerProductProof) -> bytes:
+    return (_fr(p.inner_product) + _g1(p.s_comm)
+            + _fr(p.y_f) + _fr(p.y_f_inv) + _fr(p.y_g) + _fr(p.y_g_inv) + _fr(p.y_s)
+            + _fr(p.y_s_inv) + _g1(p.w) + _g1(p.w_inv))
+
+
 def _sumcheck(p: SumcheckProof) -> bytes:
     return _u64(p.num_vars) + _fr(p.claimed_sum) + _vec(list(p.r_polys), _poly)
 
@@ -154,7 +164,8 @@ def _hyperplonk(p: HyperPlonkProof) -> bytes:
 
 _ENCODERS = [(HyperPlonkProof, _hyperplonk), (TraceProof, _trace), (MLEvalProof, _mle),
              (FoldedMLEvalProof, _mle),
-             (InnerProductProof, _ipa), (MultiOpenProof, _multiopen),
+             (InnerProductProof, _ipa), (FoldedInnerProductProof, _ipa_folded),
+             (MultiOpenProof, _multiopen),
              (SumcheckProof, _sumcheck), (ZeroCheckProof, _zerocheck),
              (MultisetEqualityProof, _multiset),
              (PermutationCheckProof, lambda p: _multiset(p.multiset_equality_proof)),
@@ -230,6 +241,11 @@ class _Reader:
         ip, s = self.fr(), self.g1()
         return InnerProductProof(ip, s, *[self.kzg_opening() for _ in range(6)])
 
+    def ipa_folded(self):
+        ip, s = self.fr(), self.g1()
+        y = [self.fr() for _ in range(6)]
+        return FoldedInnerProductProof(ip, s, *y, self.g1(), self.g1())
+
     def sumcheck(self):
         nv, cs = self.u64(), self.fr()
         return SumcheckProof(nv, cs, self.vec(lambda: self.vec(self.fr)))
@@ -265,7 +281,8 @@ class _Reader:
 
 
 _DECODERS = {HyperPlonkProof: "hyperplonk", TraceProof: "trace", MLEvalProof: "mle",
-             InnerProductProof: "ipa", MultiOpenProof: "multiopen",
+             InnerProductProof: "ipa", FoldedInnerProductProof: "ipa_folded",
+             MultiOpenProof: "multiopen",
              SumcheckProof: "sumcheck", ZeroCheckProof: "zerocheck",
              MultisetEqualityProof: "multiset", KZGOpeningProof: "kzg_opening"}
 
