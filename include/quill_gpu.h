@@ -483,10 +483,10 @@ typedef struct qg_ipa_proof_folded {
 } qg_ipa_proof_folded;
 /* The folded form of qg_ipa_prove_dev on a single context.  The first half is
  * qg_ipa_prove_dev's (same launches).  Then the six values by the evaluation
- * kernel (timed region "fold_eval": one two-point pass over f, g and S,
- * qg_poly_eval2_dev's kernel, or with QG_EVAL_PAIRED=0 - read per call; 1 or
- * unset: the former - two qg_poly_eval_dev passes; identical proofs, and the
- * former measured faster), one host round
+ * kernel (timed region "fold_eval": one two-point pass over f, g and S, as
+ * qg_poly_eval2_dev, or with QG_EVAL_PAIRED=0 - read per call; 1 or unset:
+ * the former - two one-point passes of the same kernel, as qg_poly_eval_dev;
+ * identical proofs, and the former measured faster), one host round
  * trip (gamma needs the six values), the assertion of ipa.rs:94-100 on them
  * ("Inner product verification equation failed", QG_ERR_ASSERT), one folded
  * scan over three sources (QG_FOLD_FUSED as for qg_mle_open_folded_dev) and one
@@ -1015,9 +1015,10 @@ int qg_poly_eval_dev(qg_ctx* ctx, const qg_buf* poly, size_t n, const uint64_t x
                      uint64_t shift, uint64_t out[4]);
 /* The same at two points with one pass over each vector: out[P i + j] =
  * sum_{k < lens[j]} polys[j][k] * xs[i]^k for i < 2, j < P (xs: 2 Fr, out: 2 P
- * Fr, Montgomery), the same bits as 2 P qg_poly_eval_dev calls.  A thread of
- * the kernel loads each coefficient of its strip once and runs one Horner
- * chain per point.  The folded inner-product argument's six values come from
+ * Fr, Montgomery), the same bits as 2 P qg_poly_eval_dev calls.  It is the
+ * same kernel, built for two points: a thread loads each coefficient of its
+ * strip once and runs one Horner chain per point (qg_poly_eval_dev: one
+ * chain).  The folded inner-product argument's six values come from
  * it unless QG_EVAL_PAIRED=0.  Limits: 1 <= P <= 8; anything else, null
  * pointers and a length beyond its buffer included, is QG_ERR_INVALID.
  * QG_ERR_UNSUPPORTED on a context with a communicator attached ("sharded" in

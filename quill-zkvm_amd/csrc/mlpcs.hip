@@ -493,172 +493,45 @@ static void suffix_horner_fold(qg_ctx* ctx, const ShFoldIn<NP>& in) {
 
 // ---------------------------------------------------------------- polynomial evaluation
 // DensePolynomial::evaluate (kzg.rs:78) as a reduction: sum_i c_i x^i of up to
-// EV_MAXJ vectors per launch (blockIdx.y = job, like ShJobs) in the 29-bit
-// limbs of k_sh_local.  A thread runs Horner over a contiguous strip of S
-// coefficients; a block combines its 256 strip values with powers of x^S
-// (shuffle tree inside a wave: lane l takes x^(S 2^k) times lane l + 2^k;
-// then the four wave values through LDS) and writes one value per block span
-// (256 S coefficients); a grid-stride loop covers the spans.  The last stage
-// is the same kernel over the span values (x -> x^span, one block), which also
-// multiplies by x^shift (a slice's sigma-power offset).  One Fr product per
-// coefficient against the 32 bytes it reads: multiply-bound.
+// EV_MAXJ vectors per launch (blockIdx.y = job, like ShJobs) at NP points in
+// one pass, in the 29-bit limbs of k_sh_local.  A thread loads each
+// coefficient of a contiguous strip of S once and runs NP independent Horner
+// chains (the folded inner-product argument evaluates f, g and S at r and
+// 1/r); a block combines its 256 strip values with powers of x^S (shuffle tree
+// inside a wave: lane l takes x^(S 2^k) times lane l + 2^k; then the four wave
+// values through LDS) and writes one value per point and block span (256 S
+// coefficients); a grid-stride loop covers the spans.  The last stage (LAST)
+// is the same kernel over the span values (x -> x^span, one block): chain p
+// reads its own span values c[p] and multiplies by x_p^shift (a slice's
+// sigma-power offset).  The points, their strip powers and the strip length
+// are the launch's - every job of a launch shares them, so EV_MAXJ jobs fit the
+// kernel arguments.  One Fr product per coefficient and point against the 32
+// bytes read: multiply-bound.  Stored values are canonical, so no
+// output bit depends on the strip geometry.
 static constexpr int EV_S = 32;    // first-stage thread strip
 static constexpr int EV_T = 256;   // threads per block
 static constexpr size_t EV_SPAN = (size_t)EV_S * EV_T;  // first-stage block span
 static constexpr int EV_MAXJ = 8;
-struct EvJob {
-  const Fr* c;  // coefficients (arkworks form)
-  size_t n;
-  size_t S;     // strip length (>= 1)
-  L9 x;         // x 2^261 mod p
-  L9 xp[7];     // x^(S 2^k) 2^261, k = 0..6
-  L9 sh;        // last stage: (first-stage x)^shift 2^261
-  int last;
-  Fr* out;      // out[g] = value of span g (arkworks form); last stage: out[0]
-};
-struct EvJobs {
-  EvJob j[EV_MAXJ];
-};
-
-__global__ void __launch_bounds__(EV_T) k_poly_eval(EvJobs jb) {
-  const EvJob& J = jb.j[blockIdx.y];
-  __shared__ uint32_t lds[EV_T / 64][9];
-  const F29<FrP> x = F29<FrP>::from_l9(J.x);
-  const size_t span = J.S * EV_T;
-  const size_t nspans = (J.n + span - 1) / span;
-  if (J.last && nspans == 0 && blockIdx.x == 0 && threadIdx.x == 0) J.out[0] = Fr::zero();
-  for (size_t g = blockIdx.x; g < nspans; g += gridDim.x) {  // block-uniform
-    const size_t s = g * span + (size_t)threadIdx.x * J.S;
-    F29<FrP> acc = F29<FrP>::zero();
-    if (s < J.n) {
-      const size_t e = J.S < J.n - s ? s + J.S : J.n;
-#pragma unroll 4
-      for (size_t i = e; i-- > s;) acc = red2p29(add29(to29(J.c[i]), mul29(x, acc)));
-    }
-    // lane l += x^(S m) * lane (l + m), m = 1, 2, .., 32: lane 0 ends with the
-    // wave's 64 strips (a strip past n is 0)
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const F29<FrP> o = shfl_down29(acc, 1 << k);
-      acc = red2p29(add29(acc, mul29(F29<FrP>::from_l9(J.xp[k]), o)));
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 9; i++) lds[wid][i] = acc.l[i];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const F29<FrP> pw = F29<FrP>::from_l9(J.xp[6]);  // x^(64 S)
-      F29<FrP> r = F29<FrP>::zero();
-      for (int w = EV_T / 64 - 1; w >= 0; w--) {
-        F29<FrP> v;
-#pragma unroll
-        for (int i = 0; i < 9; i++) v.l[i] = lds[w][i];
-        r = red2p29(add29(v, mul29(pw, r)));
-      }
-      if (J.last) r = mul29(F29<FrP>::from_l9(J.sh), r);
-      J.out[g] = from29(canon29(r));
-    }
-    __syncthreads();
-  }
-}
-
-struct EvIn {
-  const Fr* c;
-  size_t n;
-  uint64_t shift;
-};
-
-// d_out[j] = sum_{i < n_j} c_j[i] x^(shift_j + i), queued on the context stream
-// (x Montgomery).  QG_EVAL_BLOCKS=<k> caps the first stage's grid (read per
-// call: tests make the grid-stride loop wrap at a small length).
-static void poly_eval_queue(qg_ctx* ctx, const std::vector<EvIn>& in, const Fr& x, Fr* d_out) {
-  const char* eb = getenv("QG_EVAL_BLOCKS");
-  const size_t cap = eb && atoi(eb) > 0 ? (size_t)atoi(eb) : 4096;
-  const L9 x261 = x261_of(x);
-  const Fr X = fpow_small(x, EV_SPAN);
-  const L9 X261 = x261_of(X);
-  auto strip_powers = [](Fr b, L9 (&o)[7]) {  // b^(2^k), k = 0..6
-    for (int k = 0; k < 7; k++, b = b * b) o[k] = x261_of(b);
-  };
-  L9 xp1[7];
-  strip_powers(fpow_small(x, EV_S), xp1);
-  // the span values of one launch: one slot, sized once per call for its
-  // largest launch (a slot that grows drains the streams; callers that queue
-  // several calls reserve it first, poly_eval_reserve)
-  size_t need = 1;
-  for (size_t b = 0; b < in.size(); b += EV_MAXJ) {
-    size_t tot = 0;
-    for (size_t q = b; q < std::min(in.size(), b + EV_MAXJ); q++)
-      tot += (in[q].n + EV_SPAN - 1) / EV_SPAN;
-    need = std::max(need, tot);
-  }
-  Fr* part = ctx->scratch_as<Fr>("ev_part", need);
-  for (size_t b = 0; b < in.size(); b += EV_MAXJ) {
-    const size_t nj = std::min<size_t>(EV_MAXJ, in.size() - b);
-    size_t nsp[EV_MAXJ], off[EV_MAXJ], tot = 0, maxsp = 0;
-    for (size_t q = 0; q < nj; q++) {
-      nsp[q] = (in[b + q].n + EV_SPAN - 1) / EV_SPAN;
-      off[q] = tot;
-      tot += nsp[q];
-      maxsp = std::max(maxsp, nsp[q]);
-    }
-    EvJobs j1{}, j2{};
-    for (size_t q = 0; q < nj; q++) {
-      const EvIn& I = in[b + q];
-      EvJob& a = j1.j[q];
-      a.c = I.c, a.n = I.n, a.S = EV_S, a.x = x261, a.last = 0, a.out = part + off[q];
-      for (int k = 0; k < 7; k++) a.xp[k] = xp1[k];
-      EvJob& z = j2.j[q];
-      z.c = part + off[q], z.n = nsp[q], z.S = std::max<size_t>(1, (nsp[q] + EV_T - 1) / EV_T);
-      z.x = X261, z.sh = x261_of(fpow_small(x, I.shift)), z.last = 1, z.out = d_out + b + q;
-      strip_powers(fpow_small(X, z.S), z.xp);
-    }
-    if (maxsp) {
-      hipLaunchKernelGGL(k_poly_eval, dim3((unsigned)std::min(maxsp, cap), (unsigned)nj),
-                         dim3(EV_T), 0, ctx->stream, j1);
-      QG_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_poly_eval, dim3(1, (unsigned)nj), dim3(EV_T), 0, ctx->stream, j2);
-    QG_LAUNCH_CHECK();
-  }
-}
-
-// ev_part for later poly_eval_queue calls of at most `jobs` vectors of at most
-// `nmax` coefficients per launch (a batch reserves for its largest item up front)
-static void poly_eval_reserve(qg_ctx* ctx, size_t jobs, size_t nmax) {
-  ctx->scratch_as<Fr>("ev_part", std::min<size_t>(jobs, EV_MAXJ) * ((nmax + EV_SPAN - 1) / EV_SPAN) + 1);
-}
-
-// The same reduction at NP points in one pass (the folded inner-product
-// argument evaluates f, g and S at r and 1/r): a thread loads each coefficient
-// of its strip once and runs NP independent Horner chains; the shuffle tree,
-// the LDS stage and the span stage carry all NP values.  The points, their
-// strip powers and the strip length are the launch's (every job of a launch
-// shares them), so EV_MAXJ jobs still fit the kernel arguments.  LAST: the span
-// stage - chain p reads its own span values c[p] and multiplies by sh[p].
-// The bounds per chain are k_poly_eval's; stored values are canonical, so the
-// output equals NP poly_eval_queue calls bit for bit whatever the strips.
 template <int NP>
-struct EvJobN {
-  const Fr* c[NP];  // first stage: c[0] (one vector); span stage: one per point
+struct EvJob {
+  const Fr* c[NP];  // coefficients (arkworks form); first stage: c[0], span stage: one per point
   size_t n;
   L9 sh[NP];        // span stage: x_p^shift 2^261
   Fr* out[NP];      // out[p][g] = value of span g at x_p; span stage: out[p][0]
 };
 template <int NP>
-struct EvJobsN {
+struct EvJobs {
   L9 x[NP];      // x_p 2^261 mod p
   L9 xp[NP][7];  // x_p^(S 2^k) 2^261, k = 0..6
   size_t S;      // strip length (>= 1)
-  EvJobN<NP> j[EV_MAXJ];
+  EvJob<NP> j[EV_MAXJ];
 };
 
 template <int NP, bool LAST>
 __global__ void __launch_bounds__(EV_T) __attribute__((amdgpu_waves_per_eu(4)))
-k_poly_eval_np(EvJobsN<NP> jb) {
-  const EvJobN<NP>& J = jb.j[blockIdx.y];
+k_poly_eval(EvJobs<NP> jb) {
+  constexpr int EV_UNROLL = NP == 1 ? 4 : 2;  // of the strip loop, by measurement
+  const EvJob<NP>& J = jb.j[blockIdx.y];
   __shared__ uint32_t lds[NP][EV_T / 64][9];
   F29<FrP> x[NP];
 #pragma unroll
@@ -676,7 +549,7 @@ k_poly_eval_np(EvJobsN<NP> jb) {
     for (int p = 0; p < NP; p++) acc[p] = F29<FrP>::zero();
     if (s < J.n) {
       const size_t e = jb.S < J.n - s ? s + jb.S : J.n;
-#pragma unroll 2
+#pragma unroll EV_UNROLL
       for (size_t i = e; i-- > s;) {
         const F29<FrP> c0 = to29(J.c[0][i]);
 #pragma unroll
@@ -686,7 +559,8 @@ k_poly_eval_np(EvJobsN<NP> jb) {
         }
       }
     }
-    // lane l += x^(S m) * lane (l + m), m = 1, 2, .., 32, per chain
+    // lane l += x^(S m) * lane (l + m), m = 1, 2, .., 32, per chain: lane 0 ends
+    // with the wave's 64 strips (a strip past n is 0)
 #pragma unroll
     for (int k = 0; k < 6; k++) {
 #pragma unroll
@@ -720,66 +594,84 @@ k_poly_eval_np(EvJobsN<NP> jb) {
   }
 }
 
-// d_out[P i + j] = sum_{k < n_j} c_j[k] xs[i]^(shift_j + k), P = in.size(), i < 2:
-// poly_eval_queue at two points with one pass over each vector.  QG_EVAL_BLOCKS
-// as there.
-static void poly_eval2_queue(qg_ctx* ctx, const std::vector<EvIn>& in, const Fr xs[2],
-                             Fr* d_out) {
-  constexpr int NP = 2;
+struct EvIn {
+  const Fr* c;
+  size_t n;
+  uint64_t shift;
+};
+
+static size_t ev_spans(size_t n) { return (n + EV_SPAN - 1) / EV_SPAN; }
+
+// d_out[P i + j] = sum_{k < n_j} c_j[k] xs[i]^(shift_j + k), P = in.size(),
+// i < NP (xs Montgomery), queued on the context stream: per EV_MAXJ vectors one
+// first-stage and one span-stage launch.  QG_EVAL_BLOCKS=<k> caps the first
+// stage's grid (read per call: tests make the grid-stride loop wrap at a small
+// length).
+template <int NP>
+static void poly_eval_queue(qg_ctx* ctx, const std::vector<EvIn>& in, const Fr (&xs)[NP],
+                            Fr* d_out) {
   const char* eb = getenv("QG_EVAL_BLOCKS");
   const size_t cap = eb && atoi(eb) > 0 ? (size_t)atoi(eb) : 4096;
   const size_t P = in.size();
   auto strip_powers = [](Fr b, L9 (&o)[7]) {  // b^(2^k), k = 0..6
     for (int k = 0; k < 7; k++, b = b * b) o[k] = x261_of(b);
   };
+  // the span values of one launch, NP rows of `need`: one slot, sized once per
+  // call for its largest launch (a slot that grows drains the streams; callers
+  // that queue several calls reserve it first, poly_eval_reserve)
   size_t need = 1;
   for (size_t b = 0; b < P; b += EV_MAXJ) {
     size_t tot = 0;
-    for (size_t q = b; q < std::min(P, b + EV_MAXJ); q++) tot += (in[q].n + EV_SPAN - 1) / EV_SPAN;
+    for (size_t q = b; q < std::min(P, b + EV_MAXJ); q++) tot += ev_spans(in[q].n);
     need = std::max(need, tot);
   }
   Fr* part = ctx->scratch_as<Fr>("ev_part", NP * need);
   for (size_t b = 0; b < P; b += EV_MAXJ) {
     const size_t nj = std::min<size_t>(EV_MAXJ, P - b);
-    size_t nsp[EV_MAXJ], off[EV_MAXJ], tot = 0, maxsp = 0;
-    for (size_t q = 0; q < nj; q++) {
-      nsp[q] = (in[b + q].n + EV_SPAN - 1) / EV_SPAN;
-      off[q] = tot;
-      tot += nsp[q];
-      maxsp = std::max(maxsp, nsp[q]);
-    }
-    EvJobsN<NP> j1{}, j2{};
+    size_t maxsp = 0;
+    for (size_t q = 0; q < nj; q++) maxsp = std::max(maxsp, ev_spans(in[b + q].n));
+    EvJobs<NP> j1{}, j2{};
     j1.S = EV_S;
     j2.S = std::max<size_t>(1, (maxsp + EV_T - 1) / EV_T);  // one block covers every job's spans
-    Fr X[NP];
     for (int p = 0; p < NP; p++) {
-      j1.x[p] = x261_of(xs[p]);
+      const Fr X = fpow_small(xs[p], EV_SPAN);
+      j1.x[p] = x261_of(xs[p]), j2.x[p] = x261_of(X);
       strip_powers(fpow_small(xs[p], EV_S), j1.xp[p]);
-      X[p] = fpow_small(xs[p], EV_SPAN);
-      j2.x[p] = x261_of(X[p]);
-      strip_powers(fpow_small(X[p], j2.S), j2.xp[p]);
+      strip_powers(fpow_small(X, j2.S), j2.xp[p]);
     }
+    size_t off = 0;
     for (size_t q = 0; q < nj; q++) {
       const EvIn& I = in[b + q];
-      EvJobN<NP>& a = j1.j[q];
-      EvJobN<NP>& z = j2.j[q];
-      a.n = I.n, z.n = nsp[q];
+      EvJob<NP>& a = j1.j[q];
+      EvJob<NP>& z = j2.j[q];
+      a.n = I.n, z.n = ev_spans(I.n);
       for (int p = 0; p < NP; p++) {
-        a.c[p] = I.c, a.out[p] = part + p * need + off[q];
+        a.c[p] = I.c, a.out[p] = part + p * need + off;
         z.c[p] = a.out[p], z.sh[p] = x261_of(fpow_small(xs[p], I.shift));
         z.out[p] = d_out + p * P + b + q;
       }
+      off += z.n;
     }
     if (maxsp) {
-      hipLaunchKernelGGL((k_poly_eval_np<NP, false>),
+      hipLaunchKernelGGL((k_poly_eval<NP, false>),
                          dim3((unsigned)std::min(maxsp, cap), (unsigned)nj), dim3(EV_T), 0,
                          ctx->stream, j1);
       QG_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((k_poly_eval_np<NP, true>), dim3(1, (unsigned)nj), dim3(EV_T), 0,
+    hipLaunchKernelGGL((k_poly_eval<NP, true>), dim3(1, (unsigned)nj), dim3(EV_T), 0,
                        ctx->stream, j2);
     QG_LAUNCH_CHECK();
   }
+}
+
+// ev_part for later poly_eval_queue<np> calls of at most `jobs` vectors of at
+// most `nmax` coefficients per launch (a batch reserves for its largest item up
+// front).  A call needs np rows of max(1, sum of its launch's span counts) <=
+// jobs * ev_spans(nmax) values, which is what this allocates, so no such call
+// grows the slot (the arena reallocates only for a larger request).
+static void poly_eval_reserve(qg_ctx* ctx, size_t jobs, size_t nmax, int np) {
+  ctx->scratch_as<Fr>("ev_part",
+                      np * std::max<size_t>(1, std::min<size_t>(jobs, EV_MAXJ) * ev_spans(nmax)));
 }
 
 // ---------------------------------------------------------------- quotient check
@@ -844,7 +736,7 @@ static void open_check_queue(qg_ctx* ctx, const OpenCk ck[4], uint32_t* d_w) {
     f.d[i] = sigma - ck[i].x;
   }
   Fr* d_ev = ctx->scratch_as<Fr>("open_ck_ev", 8);
-  if (!in.empty()) poly_eval_queue(ctx, in, sigma, d_ev);
+  if (!in.empty()) poly_eval_queue(ctx, in, {sigma}, d_ev);
   f.ev = d_ev;
   f.w = d_w;
   hipLaunchKernelGGL(k_open_check_fin, dim3(1), dim3(64), 0, ctx->stream, f);
@@ -1766,8 +1658,9 @@ static QuotStage quotients_queue(qg_ctx* ctx, const std::vector<QuotJob>& jobs, 
   uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", G * st.wpg) : nullptr;
   uint32_t* h_w =
       reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", G * st.wpg * sizeof(uint32_t)));
-  // the evaluation's span scratch at its largest before anything is queued
-  if (check) poly_eval_reserve(ctx, 6, nmax);
+  // the evaluation's span scratch at its largest before anything is queued:
+  // open_check_queue evaluates up to four p and four q at sigma
+  if (check) poly_eval_reserve(ctx, 8, nmax, 1);
   if (check) st.checked.assign(J, CK_NONE);
   QG_HIP(hipMemsetAsync(d_y, 0, J * sizeof(Fr), ctx->stream));
   for (size_t g = 0; g < G; g++) {
@@ -1930,7 +1823,7 @@ static std::vector<Fr> quotients_sharded(qg_ctx* ctx, const qg_srs* srs,
       in[p_at(j)] = {jobs[j].p, jobs[j].L, off};
       in[q_at(j)] = {qs[j], qn[j], off};
     }
-    poly_eval_queue(ctx, in, ctx->open_sigma, d_ev);
+    poly_eval_queue(ctx, in, {ctx->open_sigma}, d_ev);
   }
   const std::vector<G1Affine> pis = msm_device_batch(ctx, srs, qs, qn);
   std::vector<uint32_t> bad(J, 0);
@@ -2743,7 +2636,7 @@ static void fold_scan_queue(qg_ctx* ctx, const FoldScan& fs, const Fr* d_yv, uin
   if (fs.L)
     for (int p = 0; p < fs.nx; p++) in.push_back({fs.s[p] + 1, fs.L - 1, 0});
   Fr* d_ev = ctx->scratch_as<Fr>("open_ck_ev", 8);
-  poly_eval_queue(ctx, in, sigma, d_ev);
+  poly_eval_queue(ctx, in, {sigma}, d_ev);
   FoldFin f{};
   f.ev = d_ev, f.P = fs.P, f.nq = fs.nx, f.has_q = fs.L ? 1 : 0;
   for (int j = 0; j < fs.P; j++) f.g[j] = fs.g[j];
@@ -2775,7 +2668,7 @@ static void mle_open_folded_batch_device(qg_ctx* ctx, const qg_srs* srs,
       reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 2 * K * sizeof(uint32_t)));
   size_t nmax = 0;
   for (const MleOpenItem& it : items) nmax = std::max(nmax, std::max(it.n, (size_t)1 << it.nvars));
-  poly_eval_reserve(ctx, 4, nmax);
+  poly_eval_reserve(ctx, 4, nmax, 1);  // fold_eval: {f, S}; the check: {f, S, W_r, W_inv}
   std::vector<const Fr*> qs(2 * K, nullptr);
   std::vector<size_t> qns(2 * K, 0);
   std::vector<uint8_t> checked(check ? 2 * K : 0, CK_NONE);
@@ -2788,8 +2681,8 @@ static void mle_open_folded_batch_device(qg_ctx* ctx, const qg_srs* srs,
       // d_y = f(r), S(r), f(1/r), S(1/r)
       QgTimed tm(ctx, "fold_eval");
       const std::vector<EvIn> two = {{it.poly, it.n, 0}, {F.dS[k], F.Sn[k], 0}};
-      poly_eval_queue(ctx, two, ch.r, d_y);
-      poly_eval_queue(ctx, two, ch.r_inv, d_y + 2);
+      poly_eval_queue(ctx, two, {ch.r}, d_y);
+      poly_eval_queue(ctx, two, {ch.r_inv}, d_y + 2);
       QG_HIP(hipMemcpyAsync(h_y, d_y, 4 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     }
     ctx->sync();
@@ -2989,14 +2882,17 @@ static void ipa_prove_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df, size_
 // quotient vectors instead of six.  The first half is ipa_front; then the six
 // values over the untrimmed vectors (region "fold_eval"), one host round trip,
 // the six appends and gamma, one folded scan and one MSM batch.
-// The values come from one two-point pass over each vector (poly_eval2_queue)
-// or from two single passes (poly_eval_queue at r, then at 1/r): the same
+// The values come from one two-point pass over each vector (poly_eval_queue<2>)
+// or from two single passes (poly_eval_queue<1> at r, then at 1/r): the same
 // bits.  QG_EVAL_PAIRED (read per call) selects: 1 the two-point kernel, 0 the
 // two single calls.  Unset is the two-point kernel: measured
 // (profiles/fold_ipa.json, DESIGN section 5 "Folded inner-product argument")
 // its fold_eval region is 0.147 ms against 0.177 ms at 2^20 coefficients and
 // 0.345 against 0.384 ms at 2^22, both beyond the spread of the repeated
-// medians (0.010 and 0.022 ms).
+// medians (0.010 and 0.022 ms).  With the one-point kernel an instance of the
+// same template the single calls came down to 0.154 and 0.355 ms
+// (profiles/eval_unify.json), within the spread of the two-point kernel's
+// 0.154 and 0.345, which reads each vector once and stays the default.
 static constexpr bool EVAL_PAIRED_DEFAULT = true;
 static bool eval_paired_on() {
   const char* e = getenv("QG_EVAL_PAIRED");
@@ -3015,17 +2911,18 @@ static void ipa_prove_folded_device(qg_ctx* ctx, const qg_srs* srs, const Fr* df
   Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("ipaf_y_h", 6 * sizeof(Fr)));
   uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 2) : nullptr;
   uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 2 * sizeof(uint32_t)));
-  poly_eval_reserve(ctx, EV_MAXJ, nf > ng ? nf : ng);
+  // fold_eval: {f, g, S} at two points, six rows of spans; the check's
+  // {f, g, S, W_r, W_inv} at sigma are five
+  poly_eval_reserve(ctx, 3, nf > ng ? nf : ng, 2);
   {
     // d_y[3 i + p] = polynomial p of f, g, S at r (i = 0), 1/r (i = 1)
     QgTimed tm(ctx, "fold_eval");
     const std::vector<EvIn> three = {{df, nf, 0}, {dg, ng, 0}, {F.dS, F.Sn, 0}};
     if (eval_paired_on()) {
-      const Fr xs[2] = {ch.r, ch.r_inv};
-      poly_eval2_queue(ctx, three, xs, d_y);
+      poly_eval_queue(ctx, three, {ch.r, ch.r_inv}, d_y);
     } else {
-      poly_eval_queue(ctx, three, ch.r, d_y);
-      poly_eval_queue(ctx, three, ch.r_inv, d_y + 3);
+      poly_eval_queue(ctx, three, {ch.r}, d_y);
+      poly_eval_queue(ctx, three, {ch.r_inv}, d_y + 3);
     }
     QG_HIP(hipMemcpyAsync(h_y, d_y, 6 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -3182,7 +3079,7 @@ int qg_poly_eval_dev(qg_ctx* ctx, const qg_buf* poly, size_t n, const uint64_t x
   return qg_guard(ctx, [&] {
     QG_HIP(hipSetDevice(ctx->device));
     Fr* d = ctx->scratch_as<Fr>("ev_out", 1);
-    poly_eval_queue(ctx, {{poly->d, n, shift}}, fr_import(x), d);
+    poly_eval_queue(ctx, {{poly->d, n, shift}}, {fr_import(x)}, d);
     Fr r;
     QG_HIP(hipMemcpyAsync(&r, d, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
@@ -3394,7 +3291,7 @@ int qg_kzg_open_lincomb_dev(qg_ctx* ctx, const qg_srs* srs, const qg_buf* const*
     Fr* h_y = reinterpret_cast<Fr*>(ctx->pinned_get("open_y_h", 2 * sizeof(Fr)));
     uint32_t* d_w = check ? ctx->scratch_as<uint32_t>("open_ck_w", 2) : nullptr;
     uint32_t* h_w = reinterpret_cast<uint32_t*>(ctx->pinned_get("open_ck_h", 2 * sizeof(uint32_t)));
-    if (check) poly_eval_reserve(ctx, 6, nmax);
+    if (check) poly_eval_reserve(ctx, P + nx, nmax, 1);
     QG_HIP(hipMemsetAsync(d_y, 0, 2 * sizeof(Fr), ctx->stream));
     for (size_t p = 0; p < nx; p++) {
       fs.x[p] = fr_import(xs + 4 * p);
@@ -3515,8 +3412,7 @@ int qg_poly_eval2_dev(qg_ctx* ctx, const qg_buf* const* polys, const size_t* len
     Fr* d = ctx->scratch_as<Fr>("ev2_out", 2 * EV_MAXJ);
     std::vector<EvIn> in;
     for (size_t j = 0; j < P; j++) in.push_back({polys[j]->d, lens[j], 0});
-    const Fr x2[2] = {fr_import(xs), fr_import(xs + 4)};
-    poly_eval2_queue(ctx, in, x2, d);
+    poly_eval_queue(ctx, in, {fr_import(xs), fr_import(xs + 4)}, d);
     Fr r[2 * EV_MAXJ];
     QG_HIP(hipMemcpyAsync(r, d, 2 * P * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();

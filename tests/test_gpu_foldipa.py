@@ -3,7 +3,8 @@
   * the two-point evaluation kernel (qg_poly_eval2_dev) against qg_poly_eval_dev
     per polynomial and point, bit for bit, at the strip and span edges of the
     kernel (strip 32, span 8192), with the grid-stride loop wrapped
-    (QG_EVAL_BLOCKS=1) and at the operand edges of x;
+    (QG_EVAL_BLOCKS=1) and at the operand edges of x, and - both being
+    instances of one kernel - against the oracle's Horner at the same edges;
   * qg_ipa_prove_folded[_dev] against the restatement
     (tests/foldipa_restatement.py), proof and transcript state bit for bit, on
     every route: QG_FOLD_FUSED unset / 1 and QG_EVAL_PAIRED 0 / 1;
@@ -114,6 +115,16 @@ def test_eval2_is_the_oracles_horner(dev, srcs):
     coeffs = srcs[0].to_list(33)
     xs = XPAIRS["r,1/r"]
     assert dev.poly_eval2(srcs[:1], [33], xs) == [[o.poly_eval(coeffs, x)] for x in xs]
+
+
+@pytest.mark.parametrize("xs", ["r,1/r", "p-1,random"])
+def test_eval2_matches_oracle_horner(dev, srcs, xs):
+    """independent of qg_poly_eval_dev, which is an instance of the same kernel"""
+    import oracle_c as oc
+    arr = srcs[0].to_numpy()
+    for n in LENGTHS:
+        want = [[oc.fr_horner(arr[:n], x) if n else 0] for x in XPAIRS[xs]]
+        assert dev.poly_eval2(srcs[:1], [n], XPAIRS[xs]) == want, n
 
 
 def test_eval2_grid_stride_wraps(dev, srcs):

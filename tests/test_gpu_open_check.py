@@ -94,6 +94,27 @@ def test_evaluate_zero_tail_and_views(dev):
     v.close()
 
 
+def test_evaluate_span_stage_strip_of_two(dev):
+    """More than 256 first-stage spans (n > 2^21) is the smallest shape whose span
+    stage leaves strip length 1: 2^21 + 8193 coefficients are 258 spans, strip 2.
+    In the two-point call a 33-coefficient job (one span) shares that launch's
+    strip length."""
+    import oracle_c as oc
+    from quill_amd import DeviceVec
+    n = (1 << 21) + 8193
+    v = DeviceVec(dev, n).fill_random(0xE7A3)
+    w = DeviceVec(dev, 33).fill_random(0xE7A4)
+    arr = v.to_numpy()
+    xs = (random.Random(0xE7A5).randrange(2, R), R - 1)
+    one = [v.evaluate(x, n) for x in xs]
+    assert one == [oc.fr_horner(arr, x) for x in xs]
+    assert dev.poly_eval2([v, w], [n, 33], xs) == [[y, w.evaluate(x)] for x, y in zip(xs, one)]
+    with env("QG_EVAL_BLOCKS", "2"):  # 129 spans per block
+        assert [v.evaluate(x, n) for x in xs] == one
+    v.close()
+    w.close()
+
+
 def test_evaluate_rejects_a_length_past_the_buffer(dev):
     from quill_amd import DeviceVec
     from quill_amd._lib import QuillGpuError
